@@ -2,6 +2,14 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload D] [--path fused|reference]
                     [--moving-camera] [--grad-mode owner|replicated] [--bands equal|cost]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line: `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` and the per-step statistics of the same timed steps.  Everything else the
+bench can measure or check -- per-entry-point GPU times and `roofline`, the measured copy bandwidth, `other_workloads`
+and the secondary paths, `cpu_baseline`, `parity`, and for N > 1 the in-run check of the sharded frame and the second
+gradient mode -- runs only with --full.  --dump-outputs DIR writes what the last timed step computed (image, culling
+mask, uv and the parameter gradients; a fixed, seeded sample of rows for the per-Gaussian tensors) as DIR/<name>.npy.
 
 A step = one pass of the hot path over one frame: rasterize() forward + full backward to dense
 parameter gradients.  Inputs (Gaussian parameters, camera, grad_image) are resident
@@ -30,7 +38,7 @@ vs ref") is reported in the `parity` object.  --moving-camera gives every step i
 visible set and the instance count change per frame; frame_counters then reports how often the speculative
 emit/sort capacity missed and how many tiles the prefix sort had to repair.
 
-Prints ONE JSON line with the contract fields plus
+Prints ONE JSON line with the contract fields plus, with --full,
   roofline      dominant entry point: algorithmic bytes / its mean GPU duration (events on the launch
                 stream, recorded inside the timed region) against the 8 TB/s HBM peak, next to the measured
                 device-copy bandwidth of this GPU, the pixel-splat evaluation rate E/s and a VALU issue view;
@@ -90,8 +98,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="D", choices=["A", "B", "C", "D"])
     ap.add_argument("--path", default="auto", choices=["auto", "fused", "reference"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--also", default="B,C", help="comma-separated extra workloads to time after the headline one "
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: per-entry GPU times and "
+                    "roofline, copy bandwidth, --also workloads and secondary paths, CPU baseline, parity against the "
+                    "CPU oracle; with N > 1 the in-run sharded-frame check and both gradient modes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / "
+                    "float64, at most 64 MB: a fixed, seeded sample of rows of the per-Gaussian tensors)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity check")
+    ap.add_argument("--also", default="B,C", help="--full: comma-separated extra workloads to time after the headline one "
                     "(reported under other_workloads with their own roofline sub-objects; default B,C = BASELINE.json "
                     "configs[1] and configs[2], ~0.5 s; --also '' for a profile that holds one workload only)")
     ap.add_argument("--grad-mode", default="owner", choices=["owner", "replicated"],
@@ -119,14 +134,18 @@ def parse():
                     help="multi-GPU: equal contiguous tile-row bands, or bands balanced by the previous frame's "
                     "per-row instance counts")
     ap.add_argument("--single-mode", action="store_true",
-                    help="multi-GPU: time only --grad-mode (default: both modes, the other one as a secondary number)")
-    ap.add_argument("--no-copy-bandwidth", action="store_true")
+                    help="multi-GPU with --full: time only --grad-mode (default with --full: both modes, the other one "
+                    "as a secondary number; a plain run times --grad-mode only)")
+    ap.add_argument("--no-copy-bandwidth", action="store_true", help="--full: skip the device-copy bandwidth")
     ap.add_argument("--train-loop", type=int, default=0, metavar="ITERS",
                     help="also run a synthetic training loop shaped like BASELINE.json configs[4] (7000 iterations: "
                     "0.14 M Gaussians growing to ~1.5 M under the reference's density-control schedule, 24 cameras, "
                     "SSIM+L1 loss, Adam, SH bands growing to degree 3) and report its wall time under train_loop; "
                     "never part of the headline value")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def cpu_baseline(workload, budget_s):
@@ -420,6 +439,8 @@ def main():
             image, mask, uv = forward(poses[i])
             image.backward(grad_image)
             stats["V"] = uv.shape[0]
+            if args.dump_outputs:   # (only then: holding them would keep one more frame's buffers alive)
+                stats["outputs"] = (image, mask, uv)
             return image
 
         return step, dict(stats=stats, rast=rast, holder=holder)
@@ -445,19 +466,24 @@ def main():
         # back up -- 1.80, 1.46, 1.455, 1.44 ... 1.37 ms at workload D (scripts/step_spread.py,
         # profiles/r06/step_spread.json).  A 20-step timed region that starts behind a gc.collect() and the event
         # bookkeeping measured mostly that ramp (the driver's min / median / max 1.379 / 1.421 / 1.562 of round 5).
-        _hip.reserve_events(2 * 16 * max(args.warmup, 1) + 2 * 16 * args.steps)
+        # A plain run (no --full) brackets no entry point at all: the per-entry table and `roofline` are --full's.
+        if args.full:
+            _hip.reserve_events(2 * 16 * max(args.warmup, 1) + 2 * 16 * args.steps)
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
         gc.collect()
         gc.disable()   # no collector pause inside the timed region
-        _hip.enable_timing(True)
+        if args.full:
+            _hip.enable_timing(True)
         for _ in range(args.warmup):
             step(i)
             i += 1
-        table = _hip.collect_timing()
-        _hip.enable_timing(False)
-        per_entry = {k: (sum(v) / len(v), len(v) / max(args.warmup, 1)) for k, v in table.items() if v}
-        ranked = [k for k in per_entry if k.startswith("gs_")]   # rccl_* regions are reported, not ranked
-        dom = max(ranked, key=lambda k: per_entry[k][0] * per_entry[k][1]) if ranked else None
+        per_entry, dom = {}, None
+        if args.full:
+            table = _hip.collect_timing()
+            _hip.enable_timing(False)
+            per_entry = {k: (sum(v) / len(v), len(v) / max(args.warmup, 1)) for k, v in table.items() if v}
+            ranked = [k for k in per_entry if k.startswith("gs_")]   # rccl_* regions are reported, not ranked
+            dom = max(ranked, key=lambda k: per_entry[k][0] * per_entry[k][1]) if ranked else None
         if fused_mod is not None:
             fused_mod.reset_counters()
         # (reading the warm-up's events above synchronised and took the host a moment: a few untimed frames bring the
@@ -468,7 +494,8 @@ def main():
         if fused_mod is not None:
             fused_mod.reset_counters()
         barrier()
-        _hip.enable_timing(True, only=dom)   # dom None (W = 0): every entry point, as in the warm-up
+        if args.full:
+            _hip.enable_timing(True, only=dom)   # dom None (W = 0): every entry point, as in the warm-up
         t0 = time.perf_counter()
         marks[0].record()
         for k in range(args.steps):
@@ -477,8 +504,10 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
         gc.enable()
-        timing = _hip.collect_timing()
-        _hip.enable_timing(False)
+        timing = {}
+        if args.full:
+            timing = _hip.collect_timing()
+            _hip.enable_timing(False)
         for k, v in timing.items():   # measured inside the timed region: replaces the warm-up figure
             if v:
                 per_entry[k] = (sum(v) / len(v), len(v) / args.steps)
@@ -497,7 +526,7 @@ def main():
     modes = {}
     if sharded:
         order = [args.grad_mode] + [m for m in ("owner", "replicated") if m != args.grad_mode]
-        if args.single_mode:
+        if args.single_mode or not args.full:
             order = order[:1]
         fallback = {"owner": "owner_python"}   # tried only when the mode before it failed
         ok_all = True
@@ -511,7 +540,7 @@ def main():
                 if os.environ.get("GS_BENCH_INJECT_FAILURE") == mode:   # exercises the fallback order in tests
                     raise RuntimeError(f"injected failure of mode {mode}")
                 step, info = make_mode(mode)
-                if sharded_check is None:
+                if sharded_check is None and args.full:
                     sharded_check = check_sharded_frame(mode, step, info, g, cam, poses[0], grad_image, bg, fused_mod,
                                                         DEFAULTS, world, rank, dev)
                 ms, per_step, timing, counters = timed(step)
@@ -543,69 +572,71 @@ def main():
     value = P / (ms_per_step * 1e-3) / 1e6
     timing = run["timing"]
 
-    # measured counts of the timed scene (first pose)
-    S = int(_count_instances(g, poses[args.spinup_steps + args.warmup], cam, DEFAULTS, dev)) if rank == 0 else 0
     V = int(run["info"]["stats"]["V"])
-    n_coeff = (deg + 1) ** 2
-    alg = algorithmic_bytes(N, V, S, P, n_coeff)
-    per_entry = timing["per_entry"]   # {entry: (mean ms per call, calls per step)}
-    kernels_only = [k for k in per_entry if k.startswith("gs_")]   # rccl_* regions are reported, not ranked
-    dom = timing["dominant"] if timing["dominant"] in per_entry else (
-        max(kernels_only, key=lambda k: per_entry[k][0] * per_entry[k][1]) if kernels_only else None)
-    # HBM bytes per launch from the PMC passes (FETCH_SIZE / WRITE_SIZE collected in their own rocprofv3
-    # runs and corrected for gfx950: scripts/pmc_passes.sh, scripts/make_traffic_json.py) -- a committed
-    # profile of this workload, NOT measured by this run: tagged with its source
-    traffic, traffic_source = {}, None
-    for rel in (f"profiles/r06/hbm_traffic_{args.workload}.json", f"profiles/r05/hbm_traffic_{args.workload}.json",
-                f"profiles/r04/hbm_traffic_{args.workload}.json",
-                f"profiles/r03/hbm_traffic_{args.workload}.json",
-                f"profiles/r02/hbm_traffic_{args.workload}.json",
-                f"profiles/r01_hbm_traffic_{args.workload}.json"):
-        tpath = os.path.join(ROOT, rel)
-        if world == 1 and path == "fused" and os.path.exists(tpath):
-            traffic = {k: v["hbm_bytes"] for k, v in json.load(open(tpath))["entries"].items()}
-            traffic_source = rel
-            break
-    copy_gbs = measure_copy_bandwidth(dev) if rank == 0 and not args.no_copy_bandwidth else None
-    roofline = None
-    if dom is not None:
-        dur_ms = per_entry[dom][0]
-        a = alg.get(ENTRY_ALIAS.get(dom, dom))
-        if a is not None and world > 1:
-            a = a / world   # each rank's launch covers its share of the tiles
-        ach = (a / (dur_ms * 1e-3) / 1e9) if a else None
-        # pixel-splat evaluations: E = sum over tiles of 256 x (splats in the tile's list)
-        E = 256.0 * S
-        roofline = {
-            "bound": "hbm", "kernel": dom, "achieved": round(ach, 2) if ach else None, "peak": HBM_PEAK_GBS,
-            "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 5) if ach else None,
-            "traffic": traffic.get(dom, traffic.get(ENTRY_ALIAS.get(dom, dom))), "traffic_source": traffic_source,
-            "launch_ms": round(dur_ms, 4), "algorithmic_bytes": int(a) if a else None,
-            "frame_algorithmic_bytes": int(alg["frame"]),
-            "frame_frac": round(alg["frame"] / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-            "hbm_copy_gbs_measured": round(copy_gbs, 1) if copy_gbs else None,
-            "hbm_copy_kernel": "float4 grid-stride stream copy, non-temporal (gs_stream_copy), 1 GiB, read + written bytes",
-            "hbm_achievable_gbs_guide": HBM_ACHIEVABLE_GBS,
-            "frame_frac_of_achievable": round(alg["frame"] / (ms_per_step * 1e-3) / 1e9 / HBM_ACHIEVABLE_GBS, 5),
-            "frame_frac_of_measured_copy": (round(alg["frame"] / (ms_per_step * 1e-3) / 1e9 / copy_gbs, 5)
-                                            if copy_gbs else None),
-            "pixel_splat_evaluations_per_frame": int(E),
-            "pixel_splat_evaluations_per_s": round(E / (ms_per_step * 1e-3), 1),
-            "entry_ms_per_step": {k: round(v[0] * v[1], 4) for k, v in sorted(per_entry.items())},
-            "entry_ms_source": ("the dominant entry: HIP events inside the timed region; the others: events over the %d "
-                                "warm-up frames of the same run" % args.warmup),
-            "valu": valu_roofline(dom, dur_ms, args.workload) if world == 1 else None,
-        }
+    S, roofline, other, cpu, parity, ranks = None, None, {}, None, None, None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *run["info"]["stats"]["outputs"], run["info"]["holder"])
+    if args.full:
+        # measured counts of the timed scene (first pose)
+        S = int(_count_instances(g, poses[args.spinup_steps + args.warmup], cam, DEFAULTS, dev)) if rank == 0 else 0
+        n_coeff = (deg + 1) ** 2
+        alg = algorithmic_bytes(N, V, S, P, n_coeff)
+        per_entry = timing["per_entry"]   # {entry: (mean ms per call, calls per step)}
+        kernels_only = [k for k in per_entry if k.startswith("gs_")]   # rccl_* regions are reported, not ranked
+        dom = timing["dominant"] if timing["dominant"] in per_entry else (
+            max(kernels_only, key=lambda k: per_entry[k][0] * per_entry[k][1]) if kernels_only else None)
+        # HBM bytes per launch from the PMC passes (FETCH_SIZE / WRITE_SIZE collected in their own rocprofv3
+        # runs and corrected for gfx950: scripts/pmc_passes.sh, scripts/make_traffic_json.py) -- a committed
+        # profile of this workload, NOT measured by this run: tagged with its source
+        traffic, traffic_source = {}, None
+        for rel in (f"profiles/r06/hbm_traffic_{args.workload}.json", f"profiles/r05/hbm_traffic_{args.workload}.json",
+                    f"profiles/r04/hbm_traffic_{args.workload}.json",
+                    f"profiles/r03/hbm_traffic_{args.workload}.json",
+                    f"profiles/r02/hbm_traffic_{args.workload}.json",
+                    f"profiles/r01_hbm_traffic_{args.workload}.json"):
+            tpath = os.path.join(ROOT, rel)
+            if world == 1 and path == "fused" and os.path.exists(tpath):
+                traffic = {k: v["hbm_bytes"] for k, v in json.load(open(tpath))["entries"].items()}
+                traffic_source = rel
+                break
+        copy_gbs = measure_copy_bandwidth(dev) if rank == 0 and not args.no_copy_bandwidth else None
+        if dom is not None:
+            dur_ms = per_entry[dom][0]
+            a = alg.get(ENTRY_ALIAS.get(dom, dom))
+            if a is not None and world > 1:
+                a = a / world   # each rank's launch covers its share of the tiles
+            ach = (a / (dur_ms * 1e-3) / 1e9) if a else None
+            # pixel-splat evaluations: E = sum over tiles of 256 x (splats in the tile's list)
+            E = 256.0 * S
+            roofline = {
+                "bound": "hbm", "kernel": dom, "achieved": round(ach, 2) if ach else None, "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 5) if ach else None,
+                "traffic": traffic.get(dom, traffic.get(ENTRY_ALIAS.get(dom, dom))), "traffic_source": traffic_source,
+                "launch_ms": round(dur_ms, 4), "algorithmic_bytes": int(a) if a else None,
+                "frame_algorithmic_bytes": int(alg["frame"]),
+                "frame_frac": round(alg["frame"] / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                "hbm_copy_gbs_measured": round(copy_gbs, 1) if copy_gbs else None,
+                "hbm_copy_kernel": "float4 grid-stride stream copy, non-temporal (gs_stream_copy), 1 GiB, read + written bytes",
+                "hbm_achievable_gbs_guide": HBM_ACHIEVABLE_GBS,
+                "frame_frac_of_achievable": round(alg["frame"] / (ms_per_step * 1e-3) / 1e9 / HBM_ACHIEVABLE_GBS, 5),
+                "frame_frac_of_measured_copy": (round(alg["frame"] / (ms_per_step * 1e-3) / 1e9 / copy_gbs, 5)
+                                                if copy_gbs else None),
+                "pixel_splat_evaluations_per_frame": int(E),
+                "pixel_splat_evaluations_per_s": round(E / (ms_per_step * 1e-3), 1),
+                "entry_ms_per_step": {k: round(v[0] * v[1], 4) for k, v in sorted(per_entry.items())},
+                "entry_ms_source": ("the dominant entry: HIP events inside the timed region; the others: events over the %d "
+                                    "warm-up frames of the same run" % args.warmup),
+                "valu": valu_roofline(dom, dur_ms, args.workload) if world == 1 else None,
+            }
 
-    other = {}
-    if world == 1 and not args.force_sharded and path == "fused":
-        for name in [w for w in args.also.split(",") if w and w != args.workload]:
-            other[name] = _time_workload(name, fused_mod, dev, steps=max(5, args.steps), warmup=max(3, args.warmup))
-        if args.also:
-            try:
-                other["secondary_paths_B"] = _time_secondary(dev)
-            except Exception as e:   # noqa: BLE001 -- secondary numbers must not cost the headline line
-                other["secondary_paths_B"] = {"error": str(e)[:200]}
+        if world == 1 and not args.force_sharded and path == "fused":
+            for name in [w for w in args.also.split(",") if w and w != args.workload]:
+                other[name] = _time_workload(name, fused_mod, dev, steps=max(5, args.steps), warmup=max(3, args.warmup))
+            if args.also:
+                try:
+                    other["secondary_paths_B"] = _time_secondary(dev)
+                except Exception as e:   # noqa: BLE001 -- secondary numbers must not cost the headline line
+                    other["secondary_paths_B"] = {"error": str(e)[:200]}
 
     train_ops = None
     if args.train_ops and rank == 0 and world == 1:
@@ -624,25 +655,23 @@ def main():
         train_loop["well_posed_problem"] = {k: line_extra[k] for k in ("iterations", "wall_s", "n_start", "n_end",
                                                                         "quality_trace", "convergence", "cameras")}
 
-    cpu = None
-    parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(args.workload, args.cpu_seconds)
-        if path == "fused":
-            parity = parity_check(args.workload, fused_mod, dev)
+    if args.full:
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_baseline(args.workload, args.cpu_seconds)
+            if path == "fused":
+                parity = parity_check(args.workload, fused_mod, dev)
 
-    # per-rank sizes of the sharded frame, gathered on rank 0
-    ranks = None
-    if sharded:
-        rast = run["info"]["rast"]
-        mine = {"rank": rank, "tile_rows": list(rast.tile_rows), "V": V,
-                "kernel_ms_per_step": round(sum(per_entry[k][0] * per_entry[k][1] for k in kernels_only), 4)}
-        plan = rast.last_plan
-        if plan is not None:
-            mine.update(send_rows=int(sum(plan.send_splits)), recv_rows=int(sum(plan.recv_splits)),
-                        owned_visible=[int(plan.v_lo), int(plan.v_hi)])
-        ranks = [None] * world
-        dist.all_gather_object(ranks, mine)
+        # per-rank sizes of the sharded frame, gathered on rank 0
+        if sharded:
+            rast = run["info"]["rast"]
+            mine = {"rank": rank, "tile_rows": list(rast.tile_rows), "V": V,
+                    "kernel_ms_per_step": round(sum(per_entry[k][0] * per_entry[k][1] for k in kernels_only), 4)}
+            plan = rast.last_plan
+            if plan is not None:
+                mine.update(send_rows=int(sum(plan.send_splits)), recv_rows=int(sum(plan.recv_splits)),
+                            owned_visible=[int(plan.v_lo), int(plan.v_hi)])
+            ranks = [None] * world
+            dist.all_gather_object(ranks, mine)
 
     if rank == 0:
         ps = run["per_step"]
@@ -660,7 +689,7 @@ def main():
                        "parallelism": "single" if not sharded else f"tile-rows x{world}, {head_mode} gradients, "
                                                                      f"{args.bands} bands"},
             "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "other_workloads": other,
-            "frame_counters": run["counters"],
+            "frame_counters": run["counters"], "full": args.full, "dump_outputs": args.dump_outputs,
         }
         if fused_mod is not None and not sharded:
             cnt = run["counters"] or {}
@@ -705,6 +734,45 @@ def main():
         except OSError:
             pass
         print(json.dumps(line), flush=True)
+
+
+DUMP_MAX_ROWS = 65536
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, image, mask, uv, holder):
+    """--dump-outputs: what the last timed step handed its caller -- the image, culling mask and uv that rasterize()
+    returned and the parameter gradients backward() left -- as out_dir/<name>.npy, float32.  The image is written
+    whole; a per-row tensor of more than DUMP_MAX_ROWS rows is sampled at fixed, seeded rows (the same rows for every
+    tensor of that length), listed in <name>_rows.npy (float64).  Workload B, the largest image, writes ~45 MB."""
+    import numpy as np
+    picked = {}
+
+    def rows(n):
+        if n not in picked:
+            gen = torch.Generator().manual_seed(n)
+            picked[n] = torch.randperm(n, generator=gen)[:DUMP_MAX_ROWS].sort().values
+        return picked[n]
+
+    per_row = {"mask": mask, "uv": uv}
+    for k in PARAM_NAMES:
+        p = getattr(holder, k)
+        if p is not None and p.grad is not None:
+            per_row[f"grad_{k}"] = p.grad
+    arrays = {"image": image.detach().float().cpu()}
+    for name, t in per_row.items():
+        t = t.detach()
+        if t.shape[0] > DUMP_MAX_ROWS:
+            idx = rows(t.shape[0])
+            arrays[f"{name}_rows"] = idx.double()
+            t = t[idx.to(t.device)]
+        arrays[name] = t.float().cpu()
+    total = sum(a.numel() * a.element_size() for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.numpy())
 
 
 def check_sharded_frame(mode, step, info, g, cam, T, grad_image, bg, fused_mod, defaults, world, rank, dev):

@@ -126,7 +126,7 @@ def test_bench_line_with_two_ranks_on_one_gpu(inject):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "2", "--workload", "B", "--spinup-steps", "2"]
+           "--warmup", "2", "--workload", "B", "--spinup-steps", "2", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -268,6 +268,56 @@ def test_bench_helpers():
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_options_and_dumped_outputs(tmp_path):
+    """bench.py's --steps is the number of timed steps (at least one); --full and --dump-outputs are off by default;
+    dump_outputs() writes float32 / float64 arrays under the size cap, per-row tensors as the same seeded sample of
+    rows every time"""
+    import importlib
+    import os
+    import sys
+    import types
+
+    import numpy as np
+    bench = importlib.import_module("bench")
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = bench.parse()
+        assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+        sys.argv = ["bench.py", "--steps", "3", "--full", "--dump-outputs", str(tmp_path)]
+        a = bench.parse()
+        assert a.full is True and a.dump_outputs == str(tmp_path)
+        sys.argv = ["bench.py", "--steps", "0"]
+        with pytest.raises(SystemExit):
+            bench.parse()
+    finally:
+        sys.argv = argv
+
+    N, V, n = 100_000, 80_000, bench.DUMP_MAX_ROWS
+    gen = torch.Generator().manual_seed(3)
+    holder = types.SimpleNamespace()
+    for k, shape in (("xyz", (N, 3)), ("rgb", (N, 3)), ("opacity", (N, 1)), ("scale", (N, 3)), ("quaternion", (N, 4)),
+                     ("sh", (N, 3, 15))):
+        p = torch.zeros(shape)
+        p.grad = torch.randn(shape, generator=gen)
+        setattr(holder, k, p)
+    image, mask, uv = torch.rand(1080, 1920, 3, generator=gen), torch.rand(N, generator=gen) < 0.2, torch.rand(V, 2)
+    for out in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(out), image, mask, uv, holder)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_MAX_BYTES
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / f"{k}.npy")) for k, v in got.items())
+    assert np.array_equal(got["image"], image.numpy())
+    rows = got["grad_sh_rows"].astype(np.int64)
+    assert rows.shape == (n,) and np.all(np.diff(rows) > 0) and np.array_equal(got["mask_rows"], got["grad_sh_rows"])
+    assert np.array_equal(got["grad_sh"], holder.sh.grad.numpy()[rows])
+    assert np.array_equal(got["mask"], mask.numpy()[rows].astype(np.float32))
+    assert np.array_equal(got["uv"], uv.numpy()[got["uv_rows"].astype(np.int64)])
+
+
 @pytest.mark.parametrize("rnd", ["r02", "r04", "r05"])
 def test_committed_traffic_and_valu_json_follow_from_the_committed_pmc_passes(tmp_path, rnd):
     """profiles/<round>/hbm_traffic_D.json and valu_insts_D.json (what bench.py reports as roofline.traffic /
