@@ -106,3 +106,99 @@ def grad_errors(g, ref, abs_sum=None):
     if abs_sum is not None:
         out["noise_normalised"] = noise_normalised_err(g, ref, abs_sum)
     return out
+
+
+# ---- the oracle's per-stage kernels (oracle/gs_oracle.cpp) chained, in either precision ------------------------------
+def _oracle():
+    from oracle import gs_oracle
+    gs_oracle.set_modes(0, 0)
+    gs_oracle.set_sh_band1_mode(0)
+    return gs_oracle
+
+
+def oracle_stages(g, cam, T, near, far, pad, dtype=torch.float32, mh=None):
+    """The per-Gaussian stage restated on the CPU with the oracle's kernels (CPU tensors g, cam.K, T).  The
+    world->camera transform is the kernels' explicit expression ((m0 x + m1 y) + m2 z) + m3, the cull compares with
+    the thresholds as `dtype` values, the SH colour is taken from the camera centre -A^-1 t formed in double.  fp32:
+    the HIP stage's bits (the colour up to the centre's last ulp); fp64: an independent derivation next to
+    tests/ref64.py.  mh given: also the oracle's sorted tile lists (fp32 only).  -> culled [N], keep, V and, per visible
+    Gaussian, uv, xyz_c, conic, opacity [V,1], rgb, plus what oracle_vjp needs."""
+    orc = _oracle()
+    T, K = T.detach().to(dtype).contiguous(), cam.K.detach().to(dtype).contiguous()
+    xyz = g.xyz.detach().to(dtype)
+    x, y, z = xyz.unbind(1)
+    xyz_c = torch.stack([T[i, 0] * x + T[i, 1] * y + T[i, 2] * z + T[i, 3] for i in range(3)], dim=1).contiguous()
+    N = xyz.shape[0]
+    uv = torch.zeros(N, 2, dtype=dtype)
+    orc.camera_projection_cuda(xyz_c, K, uv)
+    f = lambda v: torch.tensor(float(np.float32(v)), dtype=dtype)
+    culled = ((xyz_c[:, 2] < f(near)) | (xyz_c[:, 2] > f(far)) | (uv[:, 0] < f(-1.0 * pad)) |
+              (uv[:, 0] > f(cam.width + pad)) | (uv[:, 1] < f(-1.0 * pad)) | (uv[:, 1] > f(cam.height + pad)))
+    keep = ~culled
+    V = int(keep.sum())
+    uv, xc = uv[keep].contiguous(), xyz_c[keep].contiguous()
+    q, s = g.quaternion.detach()[keep].to(dtype).contiguous(), g.scale.detach()[keep].to(dtype).contiguous()
+    sigma = torch.zeros(V, 3, 3, dtype=dtype)
+    orc.compute_sigma_world_cuda(q, s, sigma)
+    J = torch.zeros(V, 2, 3, dtype=dtype)
+    orc.compute_projection_jacobian_cuda(xc, K, J)
+    conic = torch.zeros(V, 3, dtype=dtype)
+    orc.compute_conic_cuda(sigma, J, T, conic)
+    logit = g.opacity.detach()[keep].to(dtype).contiguous()
+    opacity = orc.sigmoid_det(logit) if dtype == torch.float32 else torch.sigmoid(logit)
+    A = T[:3, :3].double().numpy()
+    center = torch.from_numpy(-np.linalg.inv(A) @ T[:3, 3].double().numpy()).to(dtype)
+    Minv = torch.eye(4, dtype=dtype)
+    Minv[:3, 3] = center
+    xyz_v = xyz[keep].contiguous()
+    rgb = g.rgb.detach()[keep].to(dtype).contiguous()
+    if g.sh is not None:
+        coeffs = torch.cat((rgb.unsqueeze(2), g.sh.detach()[keep].to(dtype)), dim=2).contiguous()
+        rgb = torch.zeros(V, 3, dtype=dtype)
+        orc.precompute_rgb_from_sh_cuda(xyz_v, coeffs, Minv, rgb)
+    out = dict(culled=culled, keep=keep, V=V, uv=uv, xyz_c=xc, conic=conic, opacity=opacity, rgb=rgb, sigma=sigma, J=J,
+               q=q, s=s, Minv=Minv, T=T, K=K, xyz_v=xyz_v, N=N, n_coeff=1 if g.sh is None else g.sh.shape[2] + 1)
+    if mh is not None:
+        ntx, nty = (cam.width + 15) // 16, (cam.height + 15) // 16
+        out["sorted"], out["ranges"] = orc.get_sorted_gaussian_list(1024, uv, xc, conic, ntx, nty, mh)
+    return out
+
+
+def oracle_vjp(st, slab):
+    """dense parameter gradients (xyz, quaternion, scale, opacity, rgb[, sh]) from the render-gradient slab [V, 9]
+    (rgb 3 | opacity 1 | uv 2 | conic 3) of the visible rows of oracle_stages' st: the oracle's per-stage backward
+    kernels chained as the reference's autograd graph chains them (cuda_autograd_functions.py:19-219 + the glue of
+    rasterize.py:29-99), in st's precision"""
+    orc = _oracle()
+    dtype, V, N, n_coeff = st["uv"].dtype, st["V"], st["N"], st["n_coeff"]
+    slab = slab.to(dtype)
+    g_rgb, g_opa = slab[:, 0:3].contiguous(), slab[:, 3:4].contiguous()
+    g_uv, g_conic = slab[:, 4:6].contiguous(), slab[:, 6:9].contiguous()
+    z = lambda *shape: torch.zeros(*shape, dtype=dtype)
+    g_sigma, g_J = z(V, 3, 3), z(V, 2, 3)
+    orc.compute_conic_backward_cuda(st["sigma"], st["J"], st["T"], g_conic, g_sigma, g_J)
+    g_q, g_s = z(V, 4), z(V, 3)
+    orc.compute_sigma_world_backward_cuda(st["q"], st["s"], g_sigma, g_q, g_s)
+    gx1, gx2 = z(V, 3), z(V, 3)
+    orc.compute_projection_jacobian_backward_cuda(st["xyz_c"], st["K"], g_J, gx1)
+    orc.camera_projection_backward_cuda(st["xyz_c"], st["K"], g_uv, gx2)
+    g_xyz = (gx1 + gx2) @ st["T"][:3, :3]   # rows: R^T g
+    g_coeff = z(V, 3, n_coeff)
+    if n_coeff > 1:
+        orc.precompute_rgb_from_sh_backward_cuda(st["xyz_v"], st["Minv"], g_rgb, g_coeff)
+    else:
+        g_coeff[:, :, 0] = g_rgb   # degree 0: the colour is the rgb parameter itself
+    y = st["opacity"].reshape(-1, 1)
+    g_logit = g_opa * (1 - y) * y
+    keep = st["keep"]
+
+    def dense(v, shape):
+        out = z(*shape)
+        out[keep] = v
+        return out
+
+    out = dict(xyz=dense(g_xyz, (N, 3)), quaternion=dense(g_q, (N, 4)), scale=dense(g_s, (N, 3)),
+               opacity=dense(g_logit, (N, 1)), rgb=dense(g_coeff[:, :, 0], (N, 3)))
+    if n_coeff > 1:
+        out["sh"] = dense(g_coeff[:, :, 1:], (N, 3, n_coeff - 1))
+    return out

@@ -16,14 +16,13 @@ unsegmented k_render_bwd, the kernel the headline times):
     bit for bit and the same dense gradients up to summation order
 One case runs a tilted, translated camera with another seed (the identity camera of synthetic.make_scene exercises
 the world->camera transform and the camera centre of the SH colour trivially)."""
-import numpy as np
 import pytest
 import torch
 
 from gaussian_splatting_amd import fused, splat_cuda
 from gaussian_splatting_amd.synthetic import DEFAULTS, WORKLOADS, make_grad_image, make_scene
 
-from .helpers import rel_err, report, scaled_err
+from .helpers import oracle_vjp, rel_err, report, scaled_err
 from .test_gpu_fullsize_parity import REORDER_FACTOR, REORDER_FACTOR_ALL_TENSORS
 from .test_gpu_fused import cpu_expected_stages
 from .test_gpu_scale import PARAMS, RENDER_GRADS, check_band_backward, oracle
@@ -62,44 +61,8 @@ def oracle_frame(exp, rgb, W, H, bg, grad_image, sum_mode=0, with_abs=True):
 
 def oracle_chain(g, cam, T, exp, g_uv, g_conic, g_opa, g_rgb):
     """dense parameter gradients from the render gradients: the oracle's per-stage backward kernels chained as the
-    reference's autograd graph chains them (cuda_autograd_functions.py:19-219 + the glue of rasterize.py:29-99)"""
-    orc = oracle()
-    N = g.xyz.shape[0]
-    V = exp["V"]
-    keep = ~exp["culled"]
-    q, s = g.quaternion[keep].contiguous(), g.scale[keep].contiguous()
-    sigma = torch.zeros(V, 3, 3)
-    orc.compute_sigma_world_cuda(q, s, sigma)
-    J = torch.zeros(V, 2, 3)
-    orc.compute_projection_jacobian_cuda(exp["xyz_c"], cam.K, J)
-    g_sigma, g_J = torch.zeros(V, 3, 3), torch.zeros(V, 2, 3)
-    orc.compute_conic_backward_cuda(sigma, J, T, g_conic, g_sigma, g_J)
-    g_q, g_s = torch.zeros(V, 4), torch.zeros(V, 3)
-    orc.compute_sigma_world_backward_cuda(q, s, g_sigma, g_q, g_s)
-    gx1, gx2 = torch.zeros(V, 3), torch.zeros(V, 3)
-    orc.compute_projection_jacobian_backward_cuda(exp["xyz_c"], cam.K, g_J, gx1)
-    orc.camera_projection_backward_cuda(exp["xyz_c"], cam.K, g_uv, gx2)
-    g_xyz_v = (gx1 + gx2) @ T[:3, :3]   # rows: R^T g
-    A = T[:3, :3].double().numpy()
-    center = torch.from_numpy((-np.linalg.inv(A) @ T[:3, 3].double().numpy()).astype(np.float32))
-    Minv = torch.eye(4)
-    Minv[:3, 3] = center
-    n_coeff = 1 if g.sh is None else g.sh.shape[2] + 1
-    g_coeff = torch.zeros(V, 3, n_coeff)
-    orc.precompute_rgb_from_sh_backward_cuda(g.xyz[keep].contiguous(), Minv, g_rgb, g_coeff)
-    y = exp["opacity"].reshape(-1, 1)
-    g_logit = g_opa * (1 - y) * y
-
-    def dense(v, shape):
-        out = torch.zeros(shape)
-        out[keep] = v
-        return out
-
-    expect = dict(xyz=dense(g_xyz_v, (N, 3)), quaternion=dense(g_q, (N, 4)), scale=dense(g_s, (N, 3)),
-                  opacity=dense(g_logit, (N, 1)), rgb=dense(g_coeff[:, :, 0], (N, 3)))
-    if g.sh is not None:
-        expect["sh"] = dense(g_coeff[:, :, 1:], (N, 3, n_coeff - 1))
-    return expect
+    reference's autograd graph chains them (tests/helpers.py: oracle_vjp on cpu_expected_stages' exp)"""
+    return oracle_vjp(exp, torch.cat([g_rgb, g_opa.reshape(-1, 1), g_uv, g_conic], dim=1))
 
 
 def gpu_frame(workload, seed, T, aux):
