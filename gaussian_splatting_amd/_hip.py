@@ -43,6 +43,7 @@ EXPORTS = [
     "gs_precompute_rgb_from_sh", "gs_precompute_rgb_from_sh_backward",
     "gs_tile_workspace_ints", "gs_tile_count", "gs_tile_emit_sort", "gs_tile_emit_sort_bounded", "gs_tile_sort_flagged",
     "gs_preprocess_workspace_ints", "gs_preprocess_forward", "gs_preprocess_backward",
+    "gs_preprocess_backward_adam",
     "gs_pack_splats", "gs_render_tiles", "gs_render_tiles_packed", "gs_render_tiles_prefix", "gs_render_tiles_prefix_phased",
     "gs_render_tiles_backward",
     "gs_render_tiles_backward_packed", "gs_render_tiles_backward_slab", "gs_render_backward_prologue",

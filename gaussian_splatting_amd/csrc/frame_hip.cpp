@@ -16,6 +16,7 @@
 #include <hip/hip_runtime_api.h>
 #include <torch/extension.h>
 #include <torch/csrc/distributed/c10d/ProcessGroup.hpp>
+#include <torch/csrc/jit/python/python_ivalue.h>
 
 #include <cstdlib>
 #include <map>
@@ -365,12 +366,52 @@ void render_prefix_repair(RenderOut& r, const float* packed, const float* rgbr, 
     });
 }
 
+// ---- the opt-in fused optimizer step (train_ops.FusedRasterAdam) --------------------------------------------
+// The plan is a Python object kept alive by the graph; Preprocess::backward calls its begin() -- at backward time,
+// under the GIL, after the node has unpacked its saved tensors -- and gets what gs_preprocess_backward_adam takes:
+//   ([(param, exp_avg, exp_avg_sq, lr, step) for quaternion, scale, opacity, rgb, sh (None without SH)], beta1, beta2, eps)
+using PlanHolder = c10::intrusive_ptr<c10::ivalue::PyObjectHolder>;
+struct AdamRows {
+    Tensor p[5], m[5], v[5];
+    double lr[5] = {0, 0, 0, 0, 0};
+    int64_t step[5] = {1, 1, 1, 1, 1};
+    double beta1 = 0, beta2 = 0, eps = 0;
+};
+AdamRows adam_begin(PyObject* plan) {
+    AdamRows a;
+    std::string error;
+    {
+        py::gil_scoped_acquire gil;
+        try {
+            py::tuple t = py::reinterpret_borrow<py::object>(plan).attr("begin")();
+            py::sequence rows = t[0];
+            TORCH_CHECK(py::len(rows) == 5, "the optimizer plan must describe five tensors");
+            for (int k = 0; k < 5; k++) {
+                if (py::object(rows[k]).is_none()) continue;
+                py::tuple r = rows[k];
+                a.p[k] = r[0].cast<Tensor>();
+                a.m[k] = r[1].cast<Tensor>();
+                a.v[k] = r[2].cast<Tensor>();
+                a.lr[k] = r[3].cast<double>();
+                a.step[k] = r[4].cast<int64_t>();
+            }
+            a.beta1 = t[1].cast<double>();
+            a.beta2 = t[2].cast<double>();
+            a.eps = t[3].cast<double>();
+        } catch (py::error_already_set& e) {
+            error = e.what();   // (the Python error is released under the GIL, here)
+        }
+    }
+    TORCH_CHECK(error.empty(), error);
+    return a;
+}
+
 // ---- node 1: parameters -> uv, conic, opacity, colour (+ the frame's lists and, early, its image) --------
 struct Preprocess : public torch::autograd::Function<Preprocess> {
     static variable_list forward(AutogradContext* ctx, Tensor xyz, Tensor quaternion, Tensor scale, Tensor opacity,
                                  Tensor rgb, c10::optional<Tensor> sh_opt, Tensor camera_T_world, Tensor K, Tensor bg,
                                  int64_t W, int64_t H, double near_thresh, double far_thresh, double padding,
-                                 double mh_dist, int64_t row0, int64_t row1) {
+                                 double mh_dist, int64_t row0, int64_t row1, PlanHolder adam_plan) {
         const auto dev = xyz.device();
         const int N = (int)xyz.size(0);
         const bool has_sh = sh_opt.has_value() && sh_opt->defined();
@@ -559,6 +600,7 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
                                 far.block(4, N).view({N, 1})});
         ctx->saved_data["n_sh"] = (int64_t)n_sh;
         ctx->saved_data["V"] = V;
+        if (adam_plan) ctx->saved_data["adam_plan"] = c10::IValue(adam_plan);
         ctx->set_materialize_grads(false);
         ctx->mark_non_differentiable({packed_t, ranges_t, sorted_g, mask_t, out.image, out.fw, out.nsp, out.seg, flags_t,
                                       full_ranges_t, overflow_t, masks_t});
@@ -602,6 +644,42 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
             }
         }
         const int64_t n = N, extra = 3 * (int64_t)(n_sh - 1);
+        variable_list out(18);
+        if (ctx->saved_data.count("adam_plan")) {
+            // the fused optimizer step: quaternion, scale, opacity, rgb and sh are stepped by the kernel, in place;
+            // only xyz gets a gradient
+            AdamRows a = adam_begin(ctx->saved_data["adam_plan"].toPyObject());
+            const int n_rows = n_sh > 1 ? 5 : 4;
+            static const int64_t widths[5] = {4, 3, 1, 3, 0};
+            for (int k = 0; k < n_rows; k++) {
+                const int64_t numel = n * (k < 4 ? widths[k] : extra);
+                for (const Tensor* t : {&a.p[k], &a.m[k], &a.v[k]})
+                    TORCH_CHECK(t->defined() && t->is_cuda() && t->device() == dev && t->scalar_type() == torch::kFloat32 &&
+                                    t->is_contiguous() && t->numel() == numel,
+                                "fused optimizer step: a parameter or moment tensor has the wrong device, dtype, layout or size");
+            }
+            TORCH_CHECK(a.p[0].data_ptr() == quaternion.data_ptr() && a.p[1].data_ptr() == scale.data_ptr(),
+                        "fused optimizer step: the plan's quaternion / scale are not the frame's");
+            Tensor grad_xyz = torch::empty({n, 3}, xyz.options());
+            if (n > 0) {
+                void* stream = cur_stream();
+                auto ptr = [](const Tensor& t) { return t.defined() ? t.data_ptr() : nullptr; };
+                timed("gs_preprocess_backward_adam", stream, [&] {
+                    return gs_preprocess_backward_adam(
+                        xyz.data_ptr(), n_sh, camera_T_world.data_ptr(), K.data_ptr(), center.data_ptr(),
+                        rank.data_ptr<int32_t>(), opacity_act.data_ptr(), slab.data_ptr(), 0, (int)n, grad_xyz.data_ptr(),
+                        ptr(a.p[0]), ptr(a.m[0]), ptr(a.v[0]), a.lr[0], a.step[0], ptr(a.p[1]), ptr(a.m[1]), ptr(a.v[1]),
+                        a.lr[1], a.step[1], ptr(a.p[2]), ptr(a.m[2]), ptr(a.v[2]), a.lr[2], a.step[2], ptr(a.p[3]),
+                        ptr(a.m[3]), ptr(a.v[3]), a.lr[3], a.step[3], ptr(a.p[4]), ptr(a.m[4]), ptr(a.v[4]), a.lr[4],
+                        a.step[4], a.beta1, a.beta2, a.eps, stream);
+                });
+                // the kernel wrote through raw pointers: bump the version counters like an in-place torch op would
+                for (int k = 0; k < n_rows; k++)
+                    for (const Tensor* t : {&a.p[k], &a.m[k], &a.v[k]}) t->unsafeGetTensorImpl()->bump_version();
+            }
+            out[0] = grad_xyz;
+            return out;
+        }
         Arena ga(torch::kFloat32, dev, {3 * n, 4 * n, 3 * n, n, 3 * n, extra * n});
         if (n > 0) {
             void* stream = cur_stream();
@@ -613,7 +691,6 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
                                               ga.ptr<float>(4), n_sh > 1 ? ga.ptr<float>(5) : nullptr, stream);
             });
         }
-        variable_list out(17);
         out[0] = ga.block(0, 3 * n).view({n, 3});
         out[1] = ga.block(1, 4 * n).view({n, 4});
         out[2] = ga.block(2, 3 * n).view({n, 3});
@@ -689,10 +766,11 @@ struct Render : public torch::autograd::Function<Render> {
     }
 };
 
-std::tuple<Tensor, Tensor, Tensor> rasterize(Tensor xyz, Tensor quaternion, Tensor scale, Tensor opacity, Tensor rgb,
-                                             c10::optional<Tensor> sh, Tensor camera_T_world, Tensor K, int64_t width,
-                                             int64_t height, double near_thresh, double far_thresh, double cull_mask_padding,
-                                             double mh_dist, Tensor background_rgb, int64_t row0, int64_t row1) {
+std::tuple<Tensor, Tensor, Tensor> rasterize_impl(Tensor xyz, Tensor quaternion, Tensor scale, Tensor opacity, Tensor rgb,
+                                                  c10::optional<Tensor> sh, Tensor camera_T_world, Tensor K, int64_t width,
+                                                  int64_t height, double near_thresh, double far_thresh,
+                                                  double cull_mask_padding, double mh_dist, Tensor background_rgb,
+                                                  int64_t row0, int64_t row1, PlanHolder adam_plan) {
     const auto dev = xyz.device();
     const int64_t N = xyz.size(0);
     TORCH_CHECK(xyz.is_cuda(), "xyz is not a CUDA tensor");
@@ -718,10 +796,33 @@ std::tuple<Tensor, Tensor, Tensor> rasterize(Tensor xyz, Tensor quaternion, Tens
     c10::DeviceGuard guard(dev);
     auto o = Preprocess::apply(xyz.contiguous(), quaternion.contiguous(), scale.contiguous(), opacity.contiguous(),
                                rgb.contiguous(), sh, camera_T_world.contiguous(), K.contiguous(), background_rgb.contiguous(),
-                               width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, row0, row1);
+                               width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, row0, row1, adam_plan);
     Tensor image = Render::apply(o[0], o[1], o[2], o[3], o[4], o[5], o[6], background_rgb.contiguous(), o[8], o[9], o[10],
                                  o[11], o[12], o[13], o[14], o[15], row0, row1);
     return std::make_tuple(image, o[7], o[0]);
+}
+
+std::tuple<Tensor, Tensor, Tensor> rasterize(Tensor xyz, Tensor quaternion, Tensor scale, Tensor opacity, Tensor rgb,
+                                             c10::optional<Tensor> sh, Tensor camera_T_world, Tensor K, int64_t width,
+                                             int64_t height, double near_thresh, double far_thresh, double cull_mask_padding,
+                                             double mh_dist, Tensor background_rgb, int64_t row0, int64_t row1) {
+    return rasterize_impl(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, width, height, near_thresh, far_thresh,
+                          cull_mask_padding, mh_dist, background_rgb, row0, row1, PlanHolder());
+}
+
+// the same frame with the optimizer step of quaternion, scale, opacity, rgb and sh inside its backward
+// (train_ops.FusedRasterAdam.rasterize): whole frames; the five tensors must be contiguous (they are updated in place)
+std::tuple<Tensor, Tensor, Tensor> rasterize_adam(Tensor xyz, Tensor quaternion, Tensor scale, Tensor opacity, Tensor rgb,
+                                                  c10::optional<Tensor> sh, Tensor camera_T_world, Tensor K, int64_t width,
+                                                  int64_t height, double near_thresh, double far_thresh,
+                                                  double cull_mask_padding, double mh_dist, Tensor background_rgb,
+                                                  py::object plan) {
+    TORCH_CHECK(!plan.is_none(), "rasterize_adam needs an optimizer plan");
+    TORCH_CHECK(quaternion.is_contiguous() && scale.is_contiguous() && opacity.is_contiguous() && rgb.is_contiguous() &&
+                    (!sh.has_value() || !sh->defined() || sh->is_contiguous()),
+                "rasterize_adam: the parameters are stepped in place and must be contiguous");
+    return rasterize_impl(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, width, height, near_thresh, far_thresh,
+                          cull_mask_padding, mh_dist, background_rgb, 0, -1, c10::ivalue::ConcretePyObjectHolder::create(plan));
 }
 
 
@@ -1500,6 +1601,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("scale"), py::arg("opacity"), py::arg("rgb"), py::arg("sh"), py::arg("camera_T_world"), py::arg("K"),
           py::arg("width"), py::arg("height"), py::arg("near_thresh"), py::arg("far_thresh"), py::arg("cull_mask_padding"),
           py::arg("mh_dist"), py::arg("background_rgb"), py::arg("row0") = 0, py::arg("row1") = -1);
+    m.def("rasterize_adam", &rasterize_adam,
+          "fused frame whose backward steps quaternion, scale, opacity, rgb and sh (Adam) itself: -> (image, culling_mask, uv)",
+          py::arg("xyz"), py::arg("quaternion"), py::arg("scale"), py::arg("opacity"), py::arg("rgb"), py::arg("sh"),
+          py::arg("camera_T_world"), py::arg("K"), py::arg("width"), py::arg("height"), py::arg("near_thresh"),
+          py::arg("far_thresh"), py::arg("cull_mask_padding"), py::arg("mh_dist"), py::arg("background_rgb"), py::arg("plan"));
     m.def("sharded_rasterize", &sharded_rasterize,
           "one rank of the tile-row sharded frame, owner-sliced gradients, equal or cost-balanced bands: -> (image, culling_mask, uv)");
     m.def("last_plan", &last_plan);

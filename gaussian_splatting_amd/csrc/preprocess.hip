@@ -24,6 +24,9 @@
 // Every forward quantity is computed with the same device functions and operation order as the
 // stand-alone kernels (pg_math.h), so given the same camera-frame coordinates the results are
 // bit-identical to them and to the CPU restatement.
+#include <type_traits>
+
+#include "adam_math.h"
 #include "pg_math.h"
 #include "tile_math.h"
 
@@ -921,15 +924,42 @@ struct PreGrad {
     float* sh;          // [N,3,N_SH-1] or null
 };
 
+// ADAM (single-GPU frame, opt-in): the thread that owns a Gaussian applies the Adam step to its quaternion,
+// scale, opacity (the pre-sigmoid parameter), rgb and sh right where their gradients are in registers / LDS,
+// instead of streaming 224 B of gradients per Gaussian out for k_adam to read back.  param / exp_avg /
+// exp_avg_sq per tensor, updated in place; the step scalars per tensor (the step counts differ after an
+// opacity reset), beta1 / beta2 / eps shared.  The pointers are deliberately not __restrict__: quaternion and
+// scale are inputs of the gradient AND outputs of the step.
+struct AdamRow {
+    float *p, *m, *v;
+    float neg_step, bc2_sqrt;   // adam_scalars()
+};
+struct PreAdam {
+    AdamRow quaternion, scale, opacity, rgb, sh;
+    AdamShared s;
+    int sh_vec_ok;   // sh.p / m / v all 16-byte aligned
+};
+struct NoAdam {};
+// Whether the ADAM instantiation requests its 33 floats of parameter rows and moments BEFORE the gradient
+// arithmetic.  Degrees 0-2: yes (108 / 116 / 128 VGPRs, no scratch).  Degree 3 already needs 124 of the 128
+// VGPRs that four waves per SIMD allow; held across the arithmetic or across the SH phase the rows spill to scratch
+// (76 / 52 B per lane), so there they are requested behind the SH phase, all 26 loads at once (120 VGPRs).
+constexpr bool adam_rows_early(int n_sh) { return n_sh < 16; }
+
 // GATHER (multi-GPU, owner-sliced backward): the render-gradient row of a Gaussian is not read from a slab but summed
 // on the spot from the rows the all_to_all delivered (gather_row: the senders in ascending order, as
 // k_band_gather_sum adds them -- the same bits) -- no [owned, 9] buffer written and read back, one launch less
-template <int N_SH, bool GATHER = false>
+// ADAM: quat / scale are not dereferenced (they would alias the parameters the step writes; the rows are read
+// through PreAdam, once, before anything is written), o carries only xyz, and every Gaussian of the launch --
+// culled ones too, with gradient 0 -- is stepped, as the dense gradient + k_adam would.
+template <int N_SH, bool GATHER = false, bool ADAM = false>
 __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_preprocess_bwd(
     const float* __restrict__ xyz, const float* __restrict__ quat, const float* __restrict__ scale,
     const float* __restrict__ M, const float* __restrict__ K, const float* __restrict__ center,
     const int* __restrict__ rank, const float* __restrict__ opacity_act,
-    const float* __restrict__ g_slab, int v_base, int N, PreGrad o, GatherPlan gp = GatherPlan{}) {
+    const float* __restrict__ g_slab, int v_base, int N, PreGrad o, GatherPlan gp = GatherPlan{},
+    std::conditional_t<ADAM, PreAdam, NoAdam> ad = {}) {
+    static_assert(!(ADAM && GATHER), "the fused optimizer step serves the single-GPU frame");
     constexpr int SHW = 3 * (N_SH - 1);
     __shared__ int s_gather[GATHER ? GS_MAX_RANKS : 1][PP_BLOCK / GS_WAVE];
     float gathered[9];
@@ -945,6 +975,34 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))
     const int g = blockIdx.x * PP_BLOCK + threadIdx.x;
     const bool in_range = g < N;
     const int v = in_range ? rank[g] : -1;
+    // ADAM: the quaternion and scale rows are inputs of the gradient; their moments and the opacity / rgb rows with
+    // theirs (26 floats) are requested up front too where the registers allow it (adam_rows_early).  Plain loads: a
+    // row is 4-16 B per lane fetched dword by dword, the vector L1 merges what a bypassing load would ask L2 for
+    // three times.
+    constexpr bool ROWS_EARLY = adam_rows_early(N_SH);
+    float4 aq_p, aq_m, aq_v;
+    float as_p[3], as_m[3], as_v[3], ac_p[3], ac_m[3], ac_v[3], ao_p, ao_m, ao_v;
+    auto load_rows = [&]() {
+        if constexpr (ADAM) {
+            if (!in_range) return;
+            aq_m = reinterpret_cast<const float4*>(ad.quaternion.m)[g];
+            aq_v = reinterpret_cast<const float4*>(ad.quaternion.v)[g];
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                as_m[k] = ad.scale.m[g * 3 + k]; as_v[k] = ad.scale.v[g * 3 + k];
+                ac_p[k] = ad.rgb.p[g * 3 + k]; ac_m[k] = ad.rgb.m[g * 3 + k]; ac_v[k] = ad.rgb.v[g * 3 + k];
+            }
+            ao_p = ad.opacity.p[g]; ao_m = ad.opacity.m[g]; ao_v = ad.opacity.v[g];
+        }
+    };
+    if constexpr (ADAM) {
+        if (ROWS_EARLY ? in_range : v >= 0) {   // (read again behind the SH phase when not ROWS_EARLY)
+            aq_p = reinterpret_cast<const float4*>(ad.quaternion.p)[g];
+#pragma unroll
+            for (int k = 0; k < 3; k++) as_p[k] = ad.scale.p[g * 3 + k];
+        }
+        if constexpr (ROWS_EARLY) load_rows();
+    }
     float gx[3] = {0, 0, 0}, gq[4] = {0, 0, 0, 0}, gs[3] = {0, 0, 0}, go = 0, gc[3] = {0, 0, 0};
     float Y[N_SH];
     float gl3[3] = {0, 0, 0};   // d colour / d(sh row) factors of this Gaussian; 0 for culled rows
@@ -976,8 +1034,14 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))
         const float y = opacity_act[v];
         go = gsl[3] * (1.0f - y) * y;
         // conic -> Sigma_world, J (projection_backward.cu:385-471)
-        const float q4[4] = {quat[g * 4 + 0], quat[g * 4 + 1], quat[g * 4 + 2], quat[g * 4 + 3]};
-        const float s3[3] = {scale[g * 3 + 0], scale[g * 3 + 1], scale[g * 3 + 2]};
+        float q4[4], s3[3];
+        if constexpr (ADAM) {
+            q4[0] = aq_p.x; q4[1] = aq_p.y; q4[2] = aq_p.z; q4[3] = aq_p.w;
+            s3[0] = as_p[0]; s3[1] = as_p[1]; s3[2] = as_p[2];
+        } else {
+            q4[0] = quat[g * 4 + 0]; q4[1] = quat[g * 4 + 1]; q4[2] = quat[g * 4 + 2]; q4[3] = quat[g * 4 + 3];
+            s3[0] = scale[g * 3 + 0]; s3[1] = scale[g * 3 + 1]; s3[2] = scale[g * 3 + 2];
+        }
         float S9[9], W[9], J6[6], gS9[9], gJ6[6];
         sigma_world_of(q4, s3, S9);
         load_rotation(M, W);
@@ -1021,6 +1085,36 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))
             __syncthreads();
             const int g0 = blockIdx.x * PP_BLOCK + half * HALF;
             const int count = max(0, min(HALF, N - g0)) * SHW;
+            if constexpr (ADAM) {
+                // the write-out loop is the Adam loop: chunk i takes its gradient from s_sh and p, m, v from global
+                // memory with coalesced 16-byte accesses (streamed through once per iteration: non-temporal both
+                // ways, as k_adam), two chunks in flight per thread
+                const size_t off = (size_t)g0 * SHW;   // a multiple of 128 floats: keeps the bases' alignment
+                float *pp = ad.sh.p + off, *pm = ad.sh.m + off, *pv = ad.sh.v + off;
+                const float neg_step = ad.sh.neg_step, bc2 = ad.sh.bc2_sqrt;
+                const float4* src4 = reinterpret_cast<const float4*>(s_sh);
+                const int n4 = ad.sh_vec_ok ? (count >> 2) : 0;
+                for (int i = threadIdx.x; i < n4; i += 2 * PP_BLOCK) {
+                    const int j = i + PP_BLOCK;
+                    const bool two = j < n4;
+                    float4 p0 = nt_load4(pp + 4 * i), m0 = nt_load4(pm + 4 * i), v0 = nt_load4(pv + 4 * i);
+                    float4 p1, m1, v1;
+                    if (two) { p1 = nt_load4(pp + 4 * j); m1 = nt_load4(pm + 4 * j); v1 = nt_load4(pv + 4 * j); }
+                    adam_update4(p0, src4[i], m0, v0, ad.s, bc2, neg_step);
+                    nt_store4(pp + 4 * i, p0); nt_store4(pm + 4 * i, m0); nt_store4(pv + 4 * i, v0);
+                    if (two) {
+                        adam_update4(p1, src4[j], m1, v1, ad.s, bc2, neg_step);
+                        nt_store4(pp + 4 * j, p1); nt_store4(pm + 4 * j, m1); nt_store4(pv + 4 * j, v1);
+                    }
+                }
+                // the scalar tail, or everything when a base pointer is not 16-byte aligned
+                for (int i = 4 * n4 + threadIdx.x; i < count; i += PP_BLOCK) {
+                    float p = pp[i], m = pm[i], vv = pv[i];
+                    adam_update(p, s_sh[i], m, vv, ad.s.w1, ad.s.beta2, ad.s.w2, bc2, ad.s.eps, neg_step);
+                    pp[i] = p; pm[i] = m; pv[i] = vv;
+                }
+                continue;
+            }
             float* dst = o.sh + (size_t)g0 * SHW;   // 16-byte aligned: g0 is a multiple of 128
             // streamed out once (the optimizer reads it much later): non-temporal 16-byte stores
             typedef float vfloat4 __attribute__((ext_vector_type(4)));
@@ -1032,6 +1126,31 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))
     }
     if (!in_range) return;
     o.xyz[g * 3 + 0] = gx[0]; o.xyz[g * 3 + 1] = gx[1]; o.xyz[g * 3 + 2] = gx[2];
+    if constexpr (ADAM) {
+        const AdamShared& S = ad.s;
+        if constexpr (!ROWS_EARLY) {
+            // (the same values as at the top: nothing has written these rows in between)
+            aq_p = reinterpret_cast<const float4*>(ad.quaternion.p)[g];
+#pragma unroll
+            for (int k = 0; k < 3; k++) as_p[k] = ad.scale.p[g * 3 + k];
+            load_rows();
+        }
+        adam_update4(aq_p, make_float4(gq[0], gq[1], gq[2], gq[3]), aq_m, aq_v, S, ad.quaternion.bc2_sqrt,
+                     ad.quaternion.neg_step);
+        reinterpret_cast<float4*>(ad.quaternion.p)[g] = aq_p;
+        reinterpret_cast<float4*>(ad.quaternion.m)[g] = aq_m;
+        reinterpret_cast<float4*>(ad.quaternion.v)[g] = aq_v;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            adam_update(as_p[k], gs[k], as_m[k], as_v[k], S.w1, S.beta2, S.w2, ad.scale.bc2_sqrt, S.eps, ad.scale.neg_step);
+            ad.scale.p[g * 3 + k] = as_p[k]; ad.scale.m[g * 3 + k] = as_m[k]; ad.scale.v[g * 3 + k] = as_v[k];
+            adam_update(ac_p[k], gc[k], ac_m[k], ac_v[k], S.w1, S.beta2, S.w2, ad.rgb.bc2_sqrt, S.eps, ad.rgb.neg_step);
+            ad.rgb.p[g * 3 + k] = ac_p[k]; ad.rgb.m[g * 3 + k] = ac_m[k]; ad.rgb.v[g * 3 + k] = ac_v[k];
+        }
+        adam_update(ao_p, go, ao_m, ao_v, S.w1, S.beta2, S.w2, ad.opacity.bc2_sqrt, S.eps, ad.opacity.neg_step);
+        ad.opacity.p[g] = ao_p; ad.opacity.m[g] = ao_m; ad.opacity.v[g] = ao_v;
+        return;
+    }
     o.quaternion[g * 4 + 0] = gq[0]; o.quaternion[g * 4 + 1] = gq[1];
     o.quaternion[g * 4 + 2] = gq[2]; o.quaternion[g * 4 + 3] = gq[3];
     o.scale[g * 3 + 0] = gs[0]; o.scale[g * 3 + 1] = gs[1]; o.scale[g * 3 + 2] = gs[2];
@@ -1309,6 +1428,55 @@ int gs_preprocess_backward_gathered(const void* xyz, const void* quaternion, con
                           (const float*)K, (const float*)camera_center, rank_of_gaussian, (const float*)opacity_act, nullptr,
                           0, n, o, gp)));
     return check_launch("preprocess_backward_gathered");
+}
+
+int gs_preprocess_backward_adam(const void* xyz, int n_sh, const void* camera_T_world, const void* K,
+                                const void* camera_center, const int32_t* rank, const void* opacity_act,
+                                const void* grad_slab, int v_base, int N, void* grad_xyz,
+                                void* quaternion, void* quaternion_exp_avg, void* quaternion_exp_avg_sq,
+                                double quaternion_lr, int64_t quaternion_step,
+                                void* scale, void* scale_exp_avg, void* scale_exp_avg_sq, double scale_lr,
+                                int64_t scale_step,
+                                void* opacity, void* opacity_exp_avg, void* opacity_exp_avg_sq, double opacity_lr,
+                                int64_t opacity_step,
+                                void* rgb, void* rgb_exp_avg, void* rgb_exp_avg_sq, double rgb_lr, int64_t rgb_step,
+                                void* sh, void* sh_exp_avg, void* sh_exp_avg_sq, double sh_lr, int64_t sh_step,
+                                double beta1, double beta2, double eps, void* stream) {
+    GS_REQUIRE(n_sh == 1 || (sh != nullptr && sh_exp_avg != nullptr && sh_exp_avg_sq != nullptr),
+               "preprocess_backward_adam: sh, its exp_avg and exp_avg_sq must be given when n_sh > 1");
+    GS_REQUIRE(quaternion_step >= 1 && scale_step >= 1 && opacity_step >= 1 && rgb_step >= 1 &&
+                   (n_sh == 1 || sh_step >= 1),
+               "preprocess_backward_adam: every step count must be >= 1 (the count after this step)");
+    if (N <= 0) return GS_OK;
+    GS_REQUIRE(grad_xyz != nullptr && quaternion != nullptr && quaternion_exp_avg != nullptr &&
+                   quaternion_exp_avg_sq != nullptr && scale != nullptr && scale_exp_avg != nullptr &&
+                   scale_exp_avg_sq != nullptr && opacity != nullptr && opacity_exp_avg != nullptr &&
+                   opacity_exp_avg_sq != nullptr && rgb != nullptr && rgb_exp_avg != nullptr && rgb_exp_avg_sq != nullptr,
+               "preprocess_backward_adam: a parameter, exp_avg or exp_avg_sq pointer is NULL");
+    // the kernel reads and writes the quaternion rows and their moments as float4
+    GS_REQUIRE((((uintptr_t)quaternion | (uintptr_t)quaternion_exp_avg | (uintptr_t)quaternion_exp_avg_sq) & 15) == 0,
+               "preprocess_backward_adam: quaternion, its exp_avg and exp_avg_sq must be 16-byte aligned");
+    auto row = [&](void* p, void* m, void* v, double lr, int64_t step) {
+        AdamRow r;
+        r.p = (float*)p; r.m = (float*)m; r.v = (float*)v;
+        adam_scalars(lr, step, beta1, beta2, &r.neg_step, &r.bc2_sqrt);
+        return r;
+    };
+    PreAdam ad;
+    ad.quaternion = row(quaternion, quaternion_exp_avg, quaternion_exp_avg_sq, quaternion_lr, quaternion_step);
+    ad.scale = row(scale, scale_exp_avg, scale_exp_avg_sq, scale_lr, scale_step);
+    ad.opacity = row(opacity, opacity_exp_avg, opacity_exp_avg_sq, opacity_lr, opacity_step);
+    ad.rgb = row(rgb, rgb_exp_avg, rgb_exp_avg_sq, rgb_lr, rgb_step);
+    ad.sh = n_sh > 1 ? row(sh, sh_exp_avg, sh_exp_avg_sq, sh_lr, sh_step) : AdamRow{nullptr, nullptr, nullptr, 0.0f, 1.0f};
+    ad.s = adam_shared(beta1, beta2, eps);
+    ad.sh_vec_ok = n_sh > 1 && (((uintptr_t)sh | (uintptr_t)sh_exp_avg | (uintptr_t)sh_exp_avg_sq) & 15) == 0;
+    PreGrad o{};
+    o.xyz = (float*)grad_xyz;
+    DISPATCH_SH(n_sh, (k_preprocess_bwd<N_SH, false, true><<<div_up(N, PP_BLOCK), PP_BLOCK, 0, (hipStream_t)stream>>>(
+                          (const float*)xyz, nullptr, nullptr, (const float*)camera_T_world, (const float*)K,
+                          (const float*)camera_center, rank, (const float*)opacity_act, (const float*)grad_slab, v_base,
+                          N, o, GatherPlan{}, ad)));
+    return check_launch("preprocess_backward_adam");
 }
 
 int gs_preprocess_backward(const void* xyz, const void* quaternion, const void* scale, int n_sh,

@@ -11,6 +11,7 @@
 //
 // Both are HBM streaming kernels: 28 B moved per parameter element for Adam (p, g, m, v read; p, m, v
 // written), so a step over 2.86 M Gaussians x 59 parameters moves 4.7 GB.
+#include "adam_math.h"   // adam_update, nt_load4 / nt_store4, the host-side step scalars
 #include "gs_common.h"
 
 namespace gs {
@@ -29,30 +30,6 @@ struct AdamGroups {
     int vec_ok[GS_ADAM_MAX_GROUPS];            // all four base pointers 16-byte aligned
     int n;
 };
-
-// torch/optim/adam.py _single_tensor_adam (amsgrad=False, weight_decay=0, maximize=False), with the
-// operation order of the ATen CPU kernels:
-//   exp_avg.lerp_(grad, 1 - beta1)                         a + w (b - a)         (|w| < 0.5)
-//   exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2) self + (value t1) t2
-//   denom = (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
-//   param.addcdiv_(exp_avg, denom, value=-step_size)       self + (value t1) / t2
-__device__ inline void adam_update(float& p, float g, float& m, float& v, float w1, float beta2,
-                                   float w2, float bc2_sqrt, float eps, float neg_step) {
-    m = m + w1 * (g - m);
-    v = v * beta2 + (w2 * g) * g;
-    const float denom = __builtin_sqrtf(v) / bc2_sqrt + eps;
-    p = p + (neg_step * m) / denom;
-}
-
-typedef float vfloat4 __attribute__((ext_vector_type(4)));
-__device__ inline float4 nt_load4(const float* p) {
-    const vfloat4 v = __builtin_nontemporal_load(reinterpret_cast<const vfloat4*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ inline void nt_store4(float* p, const float4& a) {
-    vfloat4 v = {a.x, a.y, a.z, a.w};
-    __builtin_nontemporal_store(v, reinterpret_cast<vfloat4*>(p));
-}
 
 // one float4 chunk (or the scalar tail of a tensor)
 struct AdamChunk {
@@ -181,12 +158,7 @@ int gs_adam_step(int n_groups, void* const* params, const void* const* grads, vo
         G.numel[k] = numel[k];
         chunks += (numel[k] + 3) / 4;
         G.chunk_end[k] = chunks;
-        // torch/optim/adam.py: bias corrections and the step size are Python floats (fp64), the
-        // kernels then take them as fp32 scalars
-        const double bc1 = 1.0 - pow(beta1, (double)step[k]);
-        const double bc2 = 1.0 - pow(beta2, (double)step[k]);
-        G.neg_step_size[k] = (float)(-(lr[k] / bc1));
-        G.bc2_sqrt[k] = (float)sqrt(bc2);
+        adam_scalars(lr[k], step[k], beta1, beta2, &G.neg_step_size[k], &G.bc2_sqrt[k]);
         const uintptr_t bits = (uintptr_t)params[k] | (uintptr_t)grads[k] | (uintptr_t)exp_avg[k] |
                                (uintptr_t)exp_avg_sq[k];
         G.vec_ok[k] = (bits & 15) == 0;
@@ -200,10 +172,8 @@ int gs_adam_step(int n_groups, void* const* params, const void* const* grads, vo
     if (chunks == 0) return GS_OK;
     const long long want = (chunks + 255) / 256;
     const int grid = (int)(want < 8192 ? want : 8192);
-    // torch passes `1 - beta1`, `beta2`, `1 - beta2`, `eps` as Python floats (fp64) that the fp32
-    // kernels round once
-    const float w1 = (float)(1.0 - beta1), w2 = (float)(1.0 - beta2);
-    k_adam<<<grid, 256, 0, (hipStream_t)stream>>>(G, w1, (float)beta2, w2, (float)eps);
+    const AdamShared sh = adam_shared(beta1, beta2, eps);
+    k_adam<<<grid, 256, 0, (hipStream_t)stream>>>(G, sh.w1, sh.beta2, sh.w2, sh.eps);
     return check_launch("adam_step");
 }
 

@@ -406,6 +406,30 @@ def preprocess_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_ba
     return grad_xyz, grad_q, grad_scale, grad_opacity, grad_rgb, grad_sh
 
 
+def preprocess_backward_adam(xyz, camera_T_world, K, f, slab, plan):
+    """preprocess_backward with the optimizer step folded in (gs_preprocess_backward_adam): -> grad_xyz only;
+    quaternion, scale, opacity, rgb and sh are stepped in place with their moments, no gradient is written for them.
+    plan.begin() -> ([(param, exp_avg, exp_avg_sq, lr, step) x 5, sh's entry None without SH], beta1, beta2, eps):
+    called here, i.e. at backward time, after the node has unpacked its saved tensors (train_ops.FusedRasterAdam)."""
+    rows, beta1, beta2, eps = plan.begin()
+    n = f.N
+    grad_xyz = torch.empty(n, 3, dtype=torch.float32, device=xyz.device)
+    if n > 0:
+        args = []
+        for r in rows:
+            p, m, v, lr, step = r if r is not None else (None, None, None, 0.0, 1)
+            args += [_p(p), _p(m), _p(v), ctypes.c_double(lr), ctypes.c_int64(step)]
+        _hip.call("gs_preprocess_backward_adam", _p(xyz), f.n_sh, _p(camera_T_world), _p(K), _p(f.center), _p(f.rank),
+                  _p(f.opacity_act), _p(slab), 0, n, _p(grad_xyz), *args, ctypes.c_double(beta1), ctypes.c_double(beta2),
+                  ctypes.c_double(eps), _stream())
+        # the kernel wrote through raw pointers: bump the version counters like an in-place torch op would
+        for r in rows:
+            if r is not None:
+                for t in r[:3]:
+                    torch.autograd.graph.increment_version(t)
+    return grad_xyz
+
+
 # Depth segments of the backward (csrc/render.hip "depth segments"): the forward leaves, per (tile, 128-entry
 # segment of its list, pixel), the state a backward walk has at the segment boundary, and the backward runs one
 # workgroup per (tile, segment).  "auto": for frames / bands of fewer than SEGMENT_MAX_TILES tiles whose lists
@@ -568,8 +592,11 @@ def _as_slab(g_uv, g_conic, g_opa, g_rgb, V, dev):
 class _Preprocess(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, width, height, near_thresh,
-                far_thresh, cull_mask_padding, mh_dist, tile_rows, sort_prefix=0, background_rgb=None, cut_box=None):
+                far_thresh, cull_mask_padding, mh_dist, tile_rows, sort_prefix=0, background_rgb=None, cut_box=None,
+                adam_plan=None):
         # cut_box: a list; when the frame takes the depth cut its record (what _Render's two passes need) is left in it
+        # adam_plan: train_ops.FusedRasterAdam's plan -> the backward steps quaternion, scale, opacity, rgb and sh
+        # itself (preprocess_backward_adam) and returns a gradient for xyz only
         ntx = (width + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
         nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
         row0, row1 = tile_rows if tile_rows is not None else (0, nty)
@@ -603,6 +630,7 @@ class _Preprocess(torch.autograd.Function):
         V = f.V
         ctx.save_for_backward(xyz, quaternion, scale, camera_T_world, K)
         ctx.set_materialize_grads(False)   # no zero tensors for the auxiliary outputs in backward
+        ctx.adam_plan = adam_plan
         ctx.f = SimpleNamespace(N=f.N, V=V, n_sh=f.n_sh, center=f.center, rank=f.rank, opacity_act=f.opacity_act)
         uv_v, conic_v, opa_v, rgb_v = f.uv[:V], f.conic[:V], f.opacity_act[:V], f.rgb_render[:V]
         aux = (f.packed, f.xyz_cam[:V], f.culling_mask, f.ranges, f.sorted_g, f.vis_idx[:V], f.keys) + tuple(pre)
@@ -613,8 +641,10 @@ class _Preprocess(torch.autograd.Function):
     def backward(ctx, g_uv, g_conic, g_opa, g_rgb, *unused):
         xyz, quaternion, scale, camera_T_world, K = ctx.saved_tensors
         slab = _as_slab(g_uv, g_conic, g_opa, g_rgb, ctx.f.V, xyz.device)
+        if ctx.adam_plan is not None:
+            return (preprocess_backward_adam(xyz, camera_T_world, K, ctx.f, slab, ctx.adam_plan),) + (None,) * 18
         grads = preprocess_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab)
-        return grads + (None,) * 12
+        return grads + (None,) * 13
 
 
 class _Render(torch.autograd.Function):
@@ -781,12 +811,18 @@ def supported(gaussians, camera_T_world, camera, use_sh_precompute):
 
 def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
               use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None, slab_sync=None,
-              frame_hook=None):
+              frame_hook=None, adam_plan=None):
     """tile_rows=(row0, row1) restricts binning and rendering to those tile rows; slab_sync(flat) is
     called on the flat [9 V] render-gradient slab in the backward (grad_sync is the generic
     per-tensor form used by the reference-shaped path): the hooks gaussian_splatting_amd.sharded
-    uses; all default to the single-GPU behaviour.  frame_hook(dict) receives the frame's tile ranges."""
+    uses; all default to the single-GPU behaviour.  frame_hook(dict) receives the frame's tile ranges.
+    adam_plan: only train_ops.FusedRasterAdam.rasterize passes it (the per-Gaussian backward then steps
+    quaternion, scale, opacity, rgb and sh itself): whole single-GPU frames without hooks, SH-precompute colour."""
     hooks = return_aux or grad_sync or slab_sync or frame_hook
+    if adam_plan is not None:
+        _require(not hooks and tile_rows is None, "the fused optimizer step serves whole single-GPU frames without hooks")
+        _require(supported(gaussians, camera_T_world, camera, use_sh_precompute),
+                 "the fused optimizer step needs fp32 device tensors and the SH-precompute colour mode")
     if (gaussians.sh is not None and not use_sh_precompute and not hooks and gaussians.xyz.is_cuda
             and gaussians.xyz.dtype == torch.float32):
         # per-pixel SH evaluation (N_SH in {4, 9, 16} render kernels) on the fused frame's stages: single-GPU frames;
@@ -806,6 +842,10 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
         nat.set_segments(0 if SEGMENTS == "auto" else (1 if SEGMENTS else -1))
         nat.set_depth_cut(0 if DEPTH_CUT == "auto" else (1 if DEPTH_CUT else -1), int(DEPTH_CUT_MIN_MEAN_LIST))
         row0, row1 = tile_rows if tile_rows is not None else (0, -1)
+        if adam_plan is not None:
+            return nat.rasterize_adam(g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
+                                      int(camera.width), int(camera.height), near_thresh, far_thresh, cull_mask_padding,
+                                      mh_dist, background_rgb, adam_plan)
         return nat.rasterize(g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
                              int(camera.width), int(camera.height), near_thresh, far_thresh, cull_mask_padding, mh_dist,
                              background_rgb, row0, row1)
@@ -816,7 +856,7 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
         g.xyz.contiguous(), g.quaternion.contiguous(), g.scale.contiguous(), g.opacity.contiguous(),
         g.rgb.contiguous(), sh, camera_T_world.contiguous(), camera.K.contiguous(), int(camera.width),
         int(camera.height), near_thresh, far_thresh, cull_mask_padding, mh_dist, tile_rows, sort_prefix,
-        background_rgb.contiguous(), cut_box)
+        background_rgb.contiguous(), cut_box, adam_plan)
     uv, conic, opacity, rgb, packed, xyz_cam, culling_mask, ranges, sorted_g, vis_idx, keys = out[:11]
     if frame_hook is not None:   # multi-GPU cost-balanced bands: the band's tile ranges
         frame_hook(dict(ranges=ranges, ntx=(int(camera.width) + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX))

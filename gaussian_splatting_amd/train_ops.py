@@ -5,6 +5,11 @@
                               constructor, param_groups and state layout ("step", "exp_avg",
                               "exp_avg_sq"), so OptimizerManager's parameter surgery works on it
                               unchanged; step() is ONE HIP launch over all parameter tensors
+    FusedRasterAdam           Adam whose rasterize() returns a frame that steps quaternion, scale, opacity,
+                              rgb and sh INSIDE its backward (the per-Gaussian backward kernel applies the
+                              update where the gradients are in registers: they are never written out and
+                              read back); step() then steps xyz.  Opt-in; falls back to fused.rasterize +
+                              Adam.step whenever a condition of the fused step does not hold
     accumulate_grad_stats     trainer.py:378-385 (densification statistics) in one launch, without
                               the boolean-mask index_put and its host sync
 
@@ -81,6 +86,153 @@ class Adam(torch.optim.Adam):
             torch.autograd.graph.increment_version(m)
             torch.autograd.graph.increment_version(v)
         return loss
+
+
+_FUSED_NAMES = ("quaternion", "scale", "opacity", "rgb", "sh")   # stepped in the backward; xyz stays with step()
+_GROUP_ORDER = ("xyz", "quaternion", "scale", "opacity", "rgb", "sh")   # densify.GROUP_ORDER (optimizer_manager.py:15-42)
+
+
+class _FusedPlan:
+    """What one frame's backward needs to step the five tensors: handed to fused.rasterize, asked by the
+    per-Gaussian backward node (Python or native) at backward time."""
+
+    def __init__(self, opt, items):
+        self.opt = opt
+        self.items = items   # [(name, parameter, param group)] in _FUSED_NAMES order, without sh when there is none
+
+    def begin(self):
+        """-> ([(param, exp_avg, exp_avg_sq, lr, step) x 5 (sh: None without SH)], beta1, beta2, eps), with the
+        hyper-parameters as the groups hold them NOW and every state["step"] advanced by one"""
+        opt = self.opt
+        shared = None
+        for name, p, group in self.items:
+            if not (opt._group_ok(group) and len(group["params"]) == 1 and group["params"][0] is p):
+                raise RuntimeError(f"FusedRasterAdam: the param group of '{name}' changed between rasterize() and backward()")
+            key = (tuple(group["betas"]), group["eps"])
+            shared = key if shared is None else shared
+            if key != shared:
+                raise RuntimeError("FusedRasterAdam: betas / eps of the groups differ at backward()")
+        rows = []
+        for name, p, group in self.items:
+            state = opt.state[p]
+            if len(state) == 0:   # torch/optim/adam.py _init_group
+                state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            state["step"] += 1
+            rows.append((p, state["exp_avg"], state["exp_avg_sq"], float(group["lr"]), int(state["step"])))
+            opt._stepped_in_backward[id(p)] = (name, p)
+        rows += [None] * (len(_FUSED_NAMES) - len(rows))
+        (beta1, beta2), eps = shared
+        return rows, float(beta1), float(beta2), float(eps)
+
+
+class FusedRasterAdam(Adam):
+    """train_ops.Adam (same constructor, param_groups and state layout) with the optimizer step of five of the six
+    parameter tensors folded into the frame's backward:
+
+        opt = FusedRasterAdam(param_groups)      # one group per tensor: xyz, quaternion, scale, opacity, rgb[, sh]
+        image, culling_mask, uv = opt.rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh,
+                                                cull_mask_padding, mh_dist, use_sh_precompute, background_rgb)
+        loss.backward()     # quaternion / scale / opacity / rgb / sh are stepped inside the backward
+        opt.step()          # steps what the backward did not: xyz (and everything on a fallback frame)
+
+    rasterize() has fused.rasterize's (image, culling_mask, uv) contract; uv.retain_grad() / uv.grad and
+    gaussians.xyz.grad work as they do there.  A parameter stepped in the backward comes out with .grad None, its
+    state["step"] advanced by one; lr / betas / eps are read from its group at backward time.  step() skips it as
+    Adam.step skips any parameter without a gradient -- and raises RuntimeError if it nevertheless has a .grad
+    (another consumer in the graph, e.g. a regulariser on scale): stepping it again would apply two steps.
+
+    The parameters are looked up per call: group i of param_groups in the reference's order (densify.GROUP_ORDER)
+    must hold exactly the tensor of `gaussians`, so a DensityController may swap them between iterations.
+
+    The fused step is taken only when all of this holds -- otherwise rasterize() IS fused.rasterize and step() IS
+    Adam.step, with today's results: fp32 contiguous device leaf tensors that require grad, grad mode on,
+    use_sh_precompute or no SH, no amsgrad / weight decay / maximize / capturable / differentiable in the five
+    groups, which all share betas and eps.
+
+    Limits: the single-GPU frame only (no tile_rows, hooks or `sharded`).  The step modifies quaternion and scale,
+    which the frame saved for its backward: a second backward over a retained graph fails autograd's in-place
+    check.  Every backward is a step: accumulating gradients over several frames before one step() is not what
+    this mode does (use Adam for that)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._stepped_in_backward = {}
+        self.last_fallback_reason = None   # why the latest rasterize() did not take the fused step (None: it did)
+
+    @staticmethod
+    def _group_ok(group):
+        return not (group["amsgrad"] or group["weight_decay"] != 0 or group["maximize"]
+                    or group.get("capturable", False) or group.get("differentiable", False))
+
+    def fused_decision(self, gaussians, use_sh_precompute=True):
+        """-> (plan, None) when the frame's backward can take the fused step, else (None, why not).  Looks at the
+        param groups first and then at tensor metadata only: nothing here touches the device."""
+        g = gaussians
+        if not torch.is_grad_enabled():
+            return None, "grad mode is off"
+        if g.sh is not None and not use_sh_precompute:
+            return None, "per-pixel SH colour (use_sh_precompute=False)"
+        names = [k for k in _FUSED_NAMES if getattr(g, k) is not None]
+        if names[:4] != list(_FUSED_NAMES[:4]):
+            return None, "a parameter tensor is missing"
+        shared = None
+        for name in names:
+            i = _GROUP_ORDER.index(name)
+            if i >= len(self.param_groups):
+                return None, f"no param group for '{name}'"
+            group = self.param_groups[i]
+            if not (len(group["params"]) == 1 and group["params"][0] is getattr(g, name)):
+                return None, f"param group {i} does not hold exactly the '{name}' tensor of the Gaussians"
+            for opt_name in ("amsgrad", "weight_decay", "maximize", "capturable", "differentiable"):
+                if group.get(opt_name, False):
+                    return None, f"{opt_name} in the group of '{name}'"
+            key = (tuple(group["betas"]), group["eps"])
+            shared = key if shared is None else shared
+            if key != shared:
+                return None, "the groups do not share betas and eps"
+        if not (g.xyz.is_cuda and g.xyz.dtype == torch.float32 and g.xyz.shape[0] > 0):
+            return None, "not fp32 device tensors"
+        items = []
+        for name in names:
+            p = getattr(g, name)
+            if not (p.is_cuda and p.device == g.xyz.device and p.dtype == torch.float32 and p.is_contiguous()
+                    and p.shape[0] == g.xyz.shape[0]):
+                return None, f"'{name}' is not a contiguous fp32 tensor on the device of xyz"
+            if not (p.requires_grad and p.is_leaf):
+                return None, f"'{name}' is not a leaf that requires grad"
+            state = self.state.get(p)
+            if state:
+                for k in ("exp_avg", "exp_avg_sq"):
+                    t = state.get(k)
+                    if not (torch.is_tensor(t) and t.is_cuda and t.device == p.device and t.dtype == torch.float32
+                            and t.is_contiguous() and t.shape == p.shape):
+                        return None, f"the optimizer state of '{name}' is not in the kernel's layout"
+                if "step" not in state:
+                    return None, f"the optimizer state of '{name}' has no step count"
+            items.append((name, p, self.param_groups[_GROUP_ORDER.index(name)]))
+        return _FusedPlan(self, items), None
+
+    def fused_plan(self, gaussians, use_sh_precompute=True):
+        plan, self.last_fallback_reason = self.fused_decision(gaussians, use_sh_precompute)
+        return plan
+
+    def rasterize(self, gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+                  use_sh_precompute, background_rgb):
+        from . import fused
+
+        plan = self.fused_plan(gaussians, use_sh_precompute)
+        return fused.rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+                               use_sh_precompute, background_rgb, adam_plan=plan)
+
+    def step(self, closure=None):
+        stepped, self._stepped_in_backward = self._stepped_in_backward, {}
+        for name, p in stepped.values():
+            if p.grad is not None:
+                raise RuntimeError(f"FusedRasterAdam: '{name}' was stepped inside the backward but has a .grad at step() "
+                                   "(another consumer of it in the graph?): stepping it again would apply two steps")
+        return super().step(closure)
 
 
 def accumulate_grad_stats(uv_grad, culling_mask, xyz_grad, camera, uv_grad_accum, xyz_grad_accum, grad_accum_count):

@@ -252,6 +252,34 @@ int gs_preprocess_backward(const void* xyz, const void* quaternion, const void* 
                            void* grad_scale, void* grad_opacity_logit, void* grad_rgb_param,
                            void* grad_sh, void* stream);
 
+/* gs_preprocess_backward with the optimizer step folded in (ABI 9; single-GPU form, no reference counterpart):
+ * the gradients are computed exactly as above, grad_xyz[N,3] is written as above, and for quaternion[N,4],
+ * scale[N,3], opacity[N,1] (the pre-sigmoid parameter, not opacity_act), rgb[N,3] and (n_sh > 1) sh[N,3,n_sh-1]
+ * NO gradient is written: the kernel applies gs_adam_step's update to the parameter and its exp_avg / exp_avg_sq
+ * IN PLACE, for every one of the N Gaussians (culled ones with gradient 0: the moments decay and the parameter
+ * moves, as a dense zero gradient through gs_adam_step would make them).  The result is bit-identical to
+ * gs_preprocess_backward followed by gs_adam_step over the five tensors (one shared definition of the arithmetic,
+ * -ffp-contract=off).  xyz is only read: its gradient is needed by the densification statistics anyway, the
+ * caller steps it with gs_adam_step.
+ * quaternion and scale are inputs of the gradient and outputs of the step: they are passed once.
+ * Per tensor: <t>_lr and <t>_step (the 1-based step count AFTER this step, >= 1) as lr[k] / step[k] of gs_adam_step;
+ * beta1, beta2, eps are shared by the five tensors.  All pointers fp32 device memory; quaternion and its moments
+ * 16-byte aligned; sh and its moments may be unaligned (scalar accesses then) and are NULL / ignored when
+ * n_sh == 1.  v_base and slices [i0, i1) as in gs_preprocess_backward (every per-Gaussian pointer advanced to row
+ * i0).  There is no gathered (multi-GPU) form. */
+int gs_preprocess_backward_adam(const void* xyz, int n_sh, const void* camera_T_world, const void* K,
+                                const void* camera_center, const int32_t* rank, const void* opacity_act,
+                                const void* grad_slab, int v_base, int N, void* grad_xyz,
+                                void* quaternion, void* quaternion_exp_avg, void* quaternion_exp_avg_sq,
+                                double quaternion_lr, int64_t quaternion_step,
+                                void* scale, void* scale_exp_avg, void* scale_exp_avg_sq, double scale_lr,
+                                int64_t scale_step,
+                                void* opacity, void* opacity_exp_avg, void* opacity_exp_avg_sq, double opacity_lr,
+                                int64_t opacity_step,
+                                void* rgb, void* rgb_exp_avg, void* rgb_exp_avg_sq, double rgb_lr, int64_t rgb_step,
+                                void* sh, void* sh_exp_avg, void* sh_exp_avg_sq, double sh_lr, int64_t sh_step,
+                                double beta1, double beta2, double eps, void* stream);
+
 /* ---- tile renderer ---------------------------------------------------------------------------- */
 /* Packs what the render kernels read per splat into one 48-byte (fp32) record per visible Gaussian:
  *   packed[V][12] = (u, v, r2, opacity | a, b, c, det | 1/det, SH_0*col0, SH_0*col1, SH_0*col2)

@@ -1,5 +1,8 @@
 """Where does one training iteration go?  Host time to enqueue and GPU time (sync after each stage) of
-rasterize / loss+backward / Adam / statistics at a given Gaussian count.  usage: python scripts/iter_profile.py [N]"""
+rasterize / loss+backward / Adam / statistics at a given Gaussian count.
+usage: python scripts/iter_profile.py [N] [--fused-adam]
+--fused-adam: the same iteration with train_ops.FusedRasterAdam (five of the six tensors are stepped inside the
+backward, "adam" is then the step of xyz alone)"""
 import os
 import sys
 import time
@@ -11,16 +14,18 @@ import bench  # noqa: E402
 from gaussian_splatting_amd import fused  # noqa: E402
 from gaussian_splatting_amd.densify import DensifyConfig, DensityController  # noqa: E402
 from gaussian_splatting_amd.synthetic import DEFAULTS, make_scene  # noqa: E402
-from gaussian_splatting_amd.train_ops import Adam, ssim_l1_loss  # noqa: E402
+from gaussian_splatting_amd.train_ops import Adam, FusedRasterAdam, ssim_l1_loss  # noqa: E402
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 700_000
+FUSED_ADAM = "--fused-adam" in sys.argv
+argv = [a for a in sys.argv[1:] if a != "--fused-adam"]
+N = int(argv[0]) if argv else 700_000
 dev = torch.device("cuda", 0)
 W, H = 1297, 840
 g, cam, T = make_scene(N, W, H, 3, seed=5, device=dev)
 names = ("xyz", "quaternion", "scale", "opacity", "rgb", "sh")
 for k in names:
     getattr(g, k).requires_grad_(True)
-opt = Adam([{"params": getattr(g, k), "lr": 1e-3} for k in names])
+opt = (FusedRasterAdam if FUSED_ADAM else Adam)([{"params": getattr(g, k), "lr": 1e-3} for k in names])
 ctrl = DensityController(g, opt, DensifyConfig())
 poses = bench.camera_poses(24, 4321, dev, moving=True)
 target = torch.rand(H, W, 3, device=dev)
@@ -42,7 +47,7 @@ def iteration(i, sync):
     opt.zero_grad(set_to_none=True)
     bg = torch.full((3,), float(i % 255) / 255.0, device=dev)
     t = mark("zero_grad+bg", t, sync)
-    img, culled, uv = fused.rasterize(g, poses[i % 24], cam, use_sh_precompute=True, background_rgb=bg, **DEFAULTS)
+    img, culled, uv = (opt.rasterize if FUSED_ADAM else fused.rasterize)(g, poses[i % 24], cam, use_sh_precompute=True, background_rgb=bg, **DEFAULTS)
     uv.retain_grad()
     t = mark("rasterize", t, sync)
     loss = ssim_l1_loss(img, target, 0.2)
@@ -68,5 +73,5 @@ host = {k: v[0] * 10 for k, v in stages.items()}
 stages.clear()
 for i in range(100):
     iteration(i, True)
-print(f"N={N}: {free:.3f} ms/iteration free-running; host enqueue ms: " + ", ".join(f"{k} {v:.3f}" for k, v in host.items()))
+print(f"N={N}{' (fused optimizer step)' if FUSED_ADAM else ''}: {free:.3f} ms/iteration free-running; host enqueue ms: " + ", ".join(f"{k} {v:.3f}" for k, v in host.items()))
 print("with a sync after every stage (host + GPU) ms: " + ", ".join(f"{k} {v[1] * 10:.3f}" for k, v in stages.items()))
