@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/gsplat_hip.h"
+#include "frame_policy.h"
 
 namespace {
 
@@ -39,21 +40,22 @@ void* cur_stream() { return (void*)c10::hip::getCurrentHIPStream().stream(); }
 
 constexpr int SLAB_WIDTH = 9;   // rgb 3 | opacity 1 | uv 2 | conic 3
 
-// ---- per-process state: capacity guesses, pinned read buffers, counters ---------------------------------
+// ---- per-process state: one record per frame shape, pinned read buffers, counters -------------------------------
+using namespace frame_policy;
+static_assert(PREFIX_RENDER == GS_PREFIX_RENDER && PREFIX_REPAIR == GS_PREFIX_REPAIR, "frame_policy.h vs gsplat_hip.h");
 struct HintKey {
     int dev, N, T, row0, row1;
-    int mode = 0;   // 1: the frame's lists are depth-cut (their instance count is another quantity)
     bool operator<(const HintKey& o) const {
-        return std::tie(dev, N, T, row0, row1, mode) < std::tie(o.dev, o.N, o.T, o.row0, o.row1, o.mode);
+        return std::tie(dev, N, T, row0, row1) < std::tie(o.dev, o.N, o.T, o.row0, o.row1);
     }
 };
+// frame_policy.h's record of a shape + the pinned int32[1] the repair kernel of its cut frames writes (undefined until
+// the shape's first cut frame)
+struct ShapeRecord : ShapeState {
+    Tensor cut_flagged;
+};
 std::mutex g_mutex;
-std::map<HintKey, int64_t> g_capacity;
-// depth cut (include/gsplat_hip.h "depth-bucketed binning"): capacity of the overflow buffers (the frame's complete
-// instance count) and the complete instance count of the latest frame of a shape (what "auto" decides on)
-std::map<HintKey, int64_t> g_overflow_capacity, g_complete_count;
-std::map<HintKey, int64_t> g_visible_count;   // V of the shape's latest frame (the cut's partition scales with V, not N)
-std::map<HintKey, int64_t> g_longest_list;   // longest tile list of the shape's last complete-list frame (a guess for the next)
+std::map<HintKey, ShapeRecord> g_shapes;
 struct PinnedRing {
     std::vector<Tensor> bufs;
     std::vector<hipEvent_t> events;
@@ -66,10 +68,7 @@ struct Counters {
 } g_counters;
 std::vector<Tensor> g_flag_log;
 Tensor g_last_flags;   // tile_flags of the latest prefix-mode render (tests / tools)
-bool g_sort_prefix = true, g_early_render = true;
-// depth segments of the backward (include/gsplat_hip.h: gs_render_segment_workspace_bytes): 0 = auto (frames /
-// bands of fewer than 1500 tiles whose lists average >= 192 entries: a multi-GPU rank's band), 1 = always, -1 = never
-int g_segments = 0;
+Policy g_policy;
 bool g_band_compact = true;   // multi-GPU: band-compact per-Gaussian stage (OwnerPreprocess)
 // band-compact frames: the fused frontend (gs_band_frontend, ABI 8) and the gathering per-Gaussian backward; false =
 // the three-call pipeline of rounds 3-5 (gs_band_project, gs_halo_plan_masked, gs_preprocess_forward_list;
@@ -77,10 +76,6 @@ bool g_band_compact = true;   // multi-GPU: band-compact per-Gaussian stage (Own
 bool g_band_fused = true;
 // the render backward reads the touch masks its forward built (512 bytes per tile) instead of rebuilding them
 bool g_touch_masks = true;
-// depth cut: 0 = auto (whole frames in the LDS-histogram regime whose lists averaged g_cut_min_mean_list entries or
-// more in an earlier frame of the same shape), 1 = always (where supported), -1 = never
-int g_depth_cut = 0;
-int64_t g_cut_min_mean_list = 1280;   // workload C (1477 per tile): 1.227 -> 1.193 ms with the cut (profiles/r04)
 // the histogram gs_preprocess_forward_cut fills and returns to zero: one per (device, stream), zeroed once
 int32_t* depth_hist_of(const torch::Device& dev, void* stream) {
     static std::map<std::pair<int, void*>, Tensor> hists;
@@ -90,87 +85,6 @@ int32_t* depth_hist_of(const torch::Device& dev, void* stream) {
     if (it == hists.end())
         it = hists.emplace(key, torch::zeros({GS_CUT_HIST_BINS}, torch::TensorOptions().dtype(torch::kInt32).device(dev))).first;
     return it->second.data_ptr<int32_t>();
-}
-// "auto" also backs off when the cut does not pay: a frame in which more than an eighth of the tiles had to be
-// repaired from their complete lists (faint scenes, e.g. right after an opacity reset: every pixel composites deep)
-// emitted most lists twice.  The render's repair kernel leaves the flagged-tile count of every cut frame in a pinned
-// word; it is looked at -- never waited for -- when a later frame of the shape decides, and switches the cut off
-// for the next CUT_COOLDOWN frames of that shape (then it is tried again).
-constexpr int CUT_COOLDOWN = 32;
-struct CutFeedback {
-    Tensor flagged;   // pinned int32[1]
-    int cooldown = 0;
-};
-std::map<HintKey, CutFeedback> g_cut_feedback;
-int32_t* cut_feedback_word(const HintKey& shape) {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    CutFeedback& fb = g_cut_feedback[shape];
-    if (!fb.flagged.defined())
-        fb.flagged = torch::zeros({1}, torch::TensorOptions().dtype(torch::kInt32).pinned_memory(true));
-    return fb.flagged.data_ptr<int32_t>();
-}
-// "auto" is decided ONCE per frame shape, from the exact instance count of the first frame of that shape (which is
-// never speculative), and kept: a speculative frame only knows a capacity (S * 1.25 + 4096), so near the
-// 192-entries-per-tile threshold the first frame and later frames of the same scene would pick different backward
-// kernels and their gradients would differ in the last bits from frame to frame (round-3 advisor finding).
-std::map<HintKey, bool> g_segment_choice;
-bool want_segments(int64_t n_instances, int64_t n_tiles) {
-    if (g_segments == 0) return n_tiles > 0 && n_tiles < 1500 && n_instances >= 192 * n_tiles;
-    return g_segments > 0 && n_tiles > 0;
-}
-bool want_depth_cut(const HintKey& shape, int N, int ntx, int row0, int row1, bool whole, int sort_prefix) {
-    if (g_depth_cut < 0 || !whole || !sort_prefix) return false;
-    if (!gs_cut_supported(ntx, row0, row1, N)) return false;
-    if (g_depth_cut > 0) return true;
-    std::lock_guard<std::mutex> lock(g_mutex);
-    auto it = g_complete_count.find(shape);
-    const int64_t n_tiles = (int64_t)(row1 - row0) * ntx;
-    if (it == g_complete_count.end() || it->second < g_cut_min_mean_list * n_tiles) return false;
-    // gs_cut_supported gates on N, the capacity; what the cut's partition and count passes walk is the VISIBLE set: a
-    // heavily culled view of a large scene can pass the gate on N and not pay (round-4 advisor finding)
-    auto iv = g_visible_count.find(shape);
-    if (iv != g_visible_count.end() && !gs_cut_supported(ntx, row0, row1, (int)std::min<int64_t>(iv->second, N))) return false;
-    // "auto" cut and "auto" segments exclude each other per shape: a cut frame takes the unsegmented backward, so a
-    // small whole frame that qualifies for both (fewer than 1500 tiles, long lists) would otherwise change backward
-    // kernels -- and the last bits of its gradients -- whenever the cut policy switches (first frame of a shape,
-    // every backoff).  Such shapes keep the segments (round-4 advisor finding).
-    // What counts is what the backward of this shape will really take: the choice segments_for() STORED from the
-    // shape's first exact count when there is one (a shape whose lists grew past the cut's threshold later -- a
-    // densifying scene -- keeps its stored "no segments" and may take the cut), want_segments() on the latest
-    // complete count only before that.  Segments FORCED on (g_segments > 0) are an explicit request for the
-    // segmented backward, which a cut frame cannot honour: the auto cut then stays off (round-5 advisor finding).
-    if (g_segments > 0) return false;
-    if (g_segments == 0) {
-        auto sc = g_segment_choice.find(shape);
-        if (sc != g_segment_choice.end() ? sc->second : want_segments(it->second, n_tiles)) return false;
-    }
-    auto fb = g_cut_feedback.find(shape);
-    if (fb != g_cut_feedback.end() && fb->second.flagged.defined()) {
-        volatile int32_t* w = fb->second.flagged.data_ptr<int32_t>();
-        // During a backoff no cut frame is enqueued, so the word is not looked at; it is cleared when the backoff
-        // ends -- CUT_COOLDOWN uncut frames after the last cut frame was enqueued, whose repair kernel has long
-        // written its count by then -- never while a cut frame may still be in flight (a count landing after a
-        // host-side reset used to start a second backoff; round-4 advisor finding).
-        if (fb->second.cooldown > 0) {
-            if (--fb->second.cooldown == 0) *w = 0;
-            return false;
-        }
-        if ((int64_t)*w * 8 > n_tiles) {
-            fb->second.cooldown = CUT_COOLDOWN;
-            g_counters.cut_backoffs++;
-            return false;
-        }
-    }
-    return true;
-}
-bool segments_for(const HintKey& key, int64_t n_instances, bool exact_count, int64_t n_tiles) {
-    if (g_segments != 0) return want_segments(n_instances, n_tiles);
-    std::lock_guard<std::mutex> lock(g_mutex);
-    auto it = g_segment_choice.find(key);
-    if (it != g_segment_choice.end()) return it->second;
-    const bool on = want_segments(n_instances, n_tiles);
-    if (exact_count) g_segment_choice[key] = on;
-    return on;
 }
 
 // optional per-entry-point timing (bench.py): events on the launch stream around every C-ABI call, so the
@@ -234,6 +148,60 @@ std::pair<int32_t*, hipEvent_t> pinned_slot(int dev) {
     return {ring.bufs[ring.next].data_ptr<int32_t>(), ring.events[ring.next]};
 }
 
+// ---- the two critical sections of a frame --------------------------------------------------------------------
+// At its start a frame decides on the depth cut, takes a copy of its shape's record -- every guess of the frame comes
+// from that copy -- and the pinned slot of its host read.  may_cut: a whole single-GPU frame.
+struct FrameStart {
+    ShapeState st;
+    bool cut = false;
+    int32_t* cut_word = nullptr;   // cut frames: where the render's repair kernel leaves its flagged-tile count
+    int32_t* host = nullptr;
+    hipEvent_t ready = nullptr;
+};
+FrameStart begin_frame(const HintKey& shape, int ntx, bool may_cut, int sort_prefix) {
+    FrameStart s;
+    std::lock_guard<std::mutex> lock(g_mutex);
+    ShapeRecord& rec = g_shapes[shape];
+    if (may_cut) {
+        volatile int32_t* w = rec.cut_flagged.defined() ? rec.cut_flagged.data_ptr<int32_t>() : nullptr;
+        const CutDecision d =
+            want_depth_cut(rec, g_policy, shape.N, (int64_t)(shape.row1 - shape.row0) * ntx, true, sort_prefix, w ? *w : 0,
+                           [&](int n) { return gs_cut_supported(ntx, shape.row0, shape.row1, n) != 0; });
+        if (d.clear_word) *w = 0;
+        g_counters.cut_backoffs += d.backoff;
+        if ((s.cut = d.cut)) {
+            if (!w) rec.cut_flagged = torch::zeros({1}, torch::TensorOptions().dtype(torch::kInt32).pinned_memory(true));
+            s.cut_word = rec.cut_flagged.data_ptr<int32_t>();
+        }
+    }
+    s.st = rec;
+    std::tie(s.host, s.ready) = pinned_slot(shape.dev);
+    return s;
+}
+// After its host read a frame counts itself and leaves what it learned in the (live) record.  V >= 0: the frame also
+// reports the complete and the visible count the "auto" cut decides on (single-GPU frames).  -> does the exact render
+// of this frame (o.act == Act::Render, complete lists) take the depth-segmented backward
+bool finish_frame(const HintKey& shape, const FrameKind& k, const FramePlan& f, const FrameOutcome& o, const FrameCounts& c,
+                  int64_t n_tiles, int64_t V = -1) {
+    std::lock_guard<std::mutex> lock(g_mutex);
+    g_counters.frames++;
+    g_counters.speculative += f.speculative;
+    g_counters.cut_frames += k.cut;
+    g_counters.s_min = g_counters.s_min < 0 ? c.S_complete : std::min(g_counters.s_min, c.S_complete);
+    g_counters.s_max = std::max(g_counters.s_max, c.S_complete);
+    g_counters.misses += o.miss;
+    g_counters.long_list_misses += o.unsorted_long;
+    g_counters.late_repairs += o.act == Act::LateRepair;
+    g_counters.render_only += o.render_only;
+    ShapeRecord& rec = g_shapes[shape];
+    learn(rec, k, c);
+    if (V >= 0) {
+        rec.complete_count = c.S_complete;
+        rec.visible_count = V;
+    }
+    return o.act == Act::Render && !k.cut && segments_for(rec, g_policy, c.S, true, n_tiles);
+}
+
 // one allocation cut into 1-D blocks, each starting 16-byte aligned
 struct Arena {
     Tensor buf;
@@ -250,6 +218,21 @@ struct Arena {
     Tensor block(size_t i, int64_t n) { return buf.narrow(0, offsets[i], n); }
 };
 
+// the gradients of one per-Gaussian backward over n Gaussians: xyz | quaternion | scale | opacity | rgb | sh in one
+// allocation, handed to autograd as views (the first six inputs of both first nodes)
+struct ParamGrads {
+    int64_t n, n_sh;
+    Arena a;
+    ParamGrads(c10::Device dev, int64_t n, int n_sh)
+        : n(n), n_sh(n_sh), a(torch::kFloat32, dev, {3 * n, 4 * n, 3 * n, n, 3 * n, 3 * (int64_t)(n_sh - 1) * n}) {}
+    float* ptr(size_t i) { return i == 5 && n_sh <= 1 ? nullptr : a.ptr<float>(i); }
+    void views(variable_list& out) {
+        static const int64_t widths[5] = {3, 4, 3, 1, 3};
+        for (int k = 0; k < 5; k++) out[k] = a.block(k, widths[k] * n).view({n, widths[k]});
+        if (n_sh > 1) out[5] = a.block(5, 3 * (n_sh - 1) * n).view({n, 3, n_sh - 1});
+    }
+};
+
 void require_f32_cuda(const Tensor& t, const char* name, c10::Device dev, std::initializer_list<int64_t> shape) {
     TORCH_CHECK(t.is_cuda() && t.device() == dev, name, " is not a CUDA tensor on ", dev);
     TORCH_CHECK(t.scalar_type() == torch::kFloat32, name, " is not a float tensor");
@@ -257,6 +240,32 @@ void require_f32_cuda(const Tensor& t, const char* name, c10::Device dev, std::i
     int64_t d = 0;
     for (int64_t s : shape) same = same && t.size(d++) == s;
     TORCH_CHECK(same, name, " has the wrong shape ", t.sizes());
+}
+// what every frame entry point demands of its tensors before their pointers go to the C ABI; -> an sh tensor is given
+bool check_frame_inputs(const Tensor& xyz, const Tensor& quaternion, const Tensor& scale, const Tensor& opacity,
+                        const Tensor& rgb, const c10::optional<Tensor>& sh, const Tensor& camera_T_world, const Tensor& K,
+                        const Tensor& background_rgb, int64_t width, int64_t height) {
+    const auto dev = xyz.device();
+    const int64_t N = xyz.size(0);
+    TORCH_CHECK(xyz.is_cuda(), "xyz is not a CUDA tensor");
+    require_f32_cuda(xyz, "xyz", dev, {N, 3});
+    require_f32_cuda(quaternion, "quaternion", dev, {N, 4});
+    require_f32_cuda(scale, "scale", dev, {N, 3});
+    require_f32_cuda(opacity, "opacity", dev, {N, 1});
+    require_f32_cuda(rgb, "rgb", dev, {N, 3});
+    require_f32_cuda(camera_T_world, "camera_T_world", dev, {4, 4});
+    require_f32_cuda(K, "K", dev, {3, 3});
+    require_f32_cuda(background_rgb, "background_rgb", dev, {3});
+    const bool has_sh = sh.has_value() && sh->defined();
+    if (has_sh) {
+        TORCH_CHECK(sh->is_cuda() && sh->device() == dev, "sh is not a CUDA tensor on ", dev);
+        TORCH_CHECK(sh->scalar_type() == torch::kFloat32, "sh is not a float tensor");
+        TORCH_CHECK(sh->dim() == 3 && sh->size(0) == N && sh->size(1) == 3 &&
+                        (sh->size(2) == 3 || sh->size(2) == 8 || sh->size(2) == 15),
+                    "sh has the wrong shape ", sh->sizes());
+    }
+    TORCH_CHECK(width > 0 && height > 0, "image must be non-empty");
+    return has_sh;
 }
 
 struct RenderOut {
@@ -276,9 +285,24 @@ struct CutRef {
     int32_t* host_flagged;
 };
 
+// The prefix render of a frame, in phases, on the buffers in r.  GS_PREFIX_REPAIR alone: the repair phase of a frame
+// whose render was enqueued without it (the guess "no list exceeds the prefix" turned out wrong): full sort + second
+// render of the flagged tiles
+void render_prefix(RenderOut& r, const float* packed, const float* rgbr, const int32_t* ranges, Tensor& sorted, Tensor& keys,
+                   const Tensor& bg, int W, int H, int row0, int row1, int phases, void* stream) {
+    timed("gs_render_tiles_prefix", stream, [&] {
+        return gs_render_tiles_prefix_phased_m(packed, rgbr, ranges, sorted.data_ptr<int32_t>(),
+                                               (const uint64_t*)keys.data_ptr<int64_t>(), sorted.size(0), bg.data_ptr(), W, H, row0,
+                                               row1, r.prefix_flags.data_ptr<int32_t>(), r.nsp.data_ptr<int32_t>(),
+                                               r.fw.data_ptr(), r.image.data_ptr(), r.tile_cost,
+                                               r.seg.numel() > 0 ? r.seg.data_ptr() : nullptr, phases,
+                                               r.masks.defined() ? (uint64_t*)r.masks.data_ptr<int64_t>() : nullptr, stream);
+    });
+}
+
 RenderOut render_forward(const float* packed, const float* rgbr, const int32_t* ranges, Tensor& sorted, Tensor& keys,
                          const Tensor& bg, int W, int H, int row0, int row1, bool whole, int sort_prefix, void* stream,
-                         const HintKey& key, bool exact_count, int64_t image_rows = 0, const CutRef* cut = nullptr,
+                         bool segments, int64_t image_rows = 0, const CutRef* cut = nullptr,
                          int prefix_phases = GS_PREFIX_RENDER | GS_PREFIX_REPAIR) {
     const int64_t P = (int64_t)W * H;
     // image_rows > H (multi-GPU, equal bands): the image block holds world_size full bands so that the band
@@ -296,8 +320,16 @@ RenderOut render_forward(const float* packed, const float* rgbr, const int32_t* 
     r.image = r.buf.narrow(0, 0, 3 * PI).view({-1, W, 3});
     r.fw = r.buf.narrow(0, 3 * PI, P).view({H, W});
     r.nsp = r.buf.narrow(0, 3 * PI + P, P).view(torch::kInt32).view({H, W});
-    int32_t* tile_cost = reinterpret_cast<int32_t*>(r.buf.data_ptr<float>()) + 3 * PI + 2 * P;
-    r.tile_cost = tile_cost;
+    int32_t* tile_cost = r.tile_cost = reinterpret_cast<int32_t*>(r.buf.data_ptr<float>()) + 3 * PI + 2 * P;
+    // the prefix / cut render leaves touch masks for the backward; its tile flags go to the log of tests and tools
+    auto touch_masks = [&] {
+        if (g_touch_masks) r.masks = torch::empty({T * 64}, opt.dtype(torch::kInt64));
+    };
+    auto log_flags = [&](const Tensor& flags) {
+        std::lock_guard<std::mutex> lock(g_mutex);
+        if (g_flag_log.size() < 512) g_flag_log.push_back(flags);
+        g_last_flags = flags;
+    };
     if (cut != nullptr) {
         // depth-cut lists: kept prefixes, then (on the device, only if a tile was flagged) the complete lists of the
         // flagged tiles from the overflow buffers
@@ -307,7 +339,7 @@ RenderOut render_forward(const float* packed, const float* rgbr, const int32_t* 
         const int64_t ocap = std::max<int64_t>(cut->overflow_capacity, 1);
         r.overflow_sorted = torch::empty({ocap}, opt.dtype(torch::kInt32));
         Tensor okeys = torch::empty({ocap}, opt.dtype(torch::kInt64));
-        if (g_touch_masks) r.masks = torch::empty({T * 64}, opt.dtype(torch::kInt64));
+        touch_masks();
         uint64_t* masks_p = r.masks.defined() ? (uint64_t*)r.masks.data_ptr<int64_t>() : nullptr;
         timed("gs_render_tiles_prefix", stream, [&] {
             return gs_render_tiles_cut_m(packed, rgbr, ranges, sorted.data_ptr<int32_t>(), sorted.size(0), cut->full_ranges,
@@ -317,30 +349,17 @@ RenderOut render_forward(const float* packed, const float* rgbr, const int32_t* 
                                          r.cut_flags.data_ptr<int32_t>(), r.nsp.data_ptr<int32_t>(), r.fw.data_ptr(),
                                          r.image.data_ptr(), tile_cost, cut->host_flagged, masks_p, stream);
         });
-        std::lock_guard<std::mutex> lock(g_mutex);
-        if (g_flag_log.size() < 512) g_flag_log.push_back(r.cut_flags);
-        g_last_flags = r.cut_flags;
+        log_flags(r.cut_flags);
         return r;
     }
-    const bool segments = segments_for(key, sorted.size(0), exact_count, (int64_t)(row1 - row0) * ntx);
     r.seg = torch::empty({segments ? (int64_t)(gs_render_segment_workspace_bytes(W, H, row0, row1) / 4) : 0}, opt);
-    void* seg_p = segments ? r.seg.data_ptr() : nullptr;
     if (sort_prefix && sorted.size(0) > sort_prefix) {
-        Tensor flags = torch::empty({(int64_t)ntx * nty}, opt.dtype(torch::kInt32));
-        if (g_touch_masks) r.masks = torch::empty({T * 64}, opt.dtype(torch::kInt64));
-        uint64_t* masks_p = r.masks.defined() ? (uint64_t*)r.masks.data_ptr<int64_t>() : nullptr;
-        timed("gs_render_tiles_prefix", stream, [&] {
-            return gs_render_tiles_prefix_phased_m(packed, rgbr, ranges, sorted.data_ptr<int32_t>(),
-                                                   (const uint64_t*)keys.data_ptr<int64_t>(), sorted.size(0), bg.data_ptr(), W, H,
-                                                   row0, row1, flags.data_ptr<int32_t>(), r.nsp.data_ptr<int32_t>(),
-                                                   r.fw.data_ptr(), r.image.data_ptr(), tile_cost, seg_p, prefix_phases, masks_p,
-                                                   stream);
-        });
-        r.prefix_flags = flags;
-        std::lock_guard<std::mutex> lock(g_mutex);
-        if (g_flag_log.size() < 512) g_flag_log.push_back(flags);
-        g_last_flags = flags;
+        r.prefix_flags = torch::empty({(int64_t)ntx * nty}, opt.dtype(torch::kInt32));
+        touch_masks();
+        render_prefix(r, packed, rgbr, ranges, sorted, keys, bg, W, H, row0, row1, prefix_phases, stream);
+        log_flags(r.prefix_flags);
     } else {
+        void* seg_p = segments ? r.seg.data_ptr() : nullptr;
         // no costs measured: all tiles equal (any launch order is as good as another)
         TORCH_CHECK(hipMemsetAsync(tile_cost, 0, sizeof(int32_t) * (size_t)T, (hipStream_t)stream) == hipSuccess,
                     "hipMemsetAsync failed");
@@ -350,20 +369,6 @@ RenderOut render_forward(const float* packed, const float* rgbr, const int32_t* 
         });
     }
     return r;
-}
-
-// the repair phase of a prefix-sorted frame whose render was enqueued without it (the guess "no list exceeds the
-// prefix" turned out wrong): full sort + second render of the flagged tiles, on the buffers of that render
-void render_prefix_repair(RenderOut& r, const float* packed, const float* rgbr, const int32_t* ranges, Tensor& sorted,
-                          Tensor& keys, const Tensor& bg, int W, int H, int row0, int row1, void* stream) {
-    timed("gs_render_tiles_prefix", stream, [&] {
-        return gs_render_tiles_prefix_phased_m(packed, rgbr, ranges, sorted.data_ptr<int32_t>(),
-                                               (const uint64_t*)keys.data_ptr<int64_t>(), sorted.size(0), bg.data_ptr(), W, H, row0,
-                                               row1, r.prefix_flags.data_ptr<int32_t>(), r.nsp.data_ptr<int32_t>(),
-                                               r.fw.data_ptr(), r.image.data_ptr(), r.tile_cost,
-                                               r.seg.numel() > 0 ? r.seg.data_ptr() : nullptr, GS_PREFIX_REPAIR,
-                                               r.masks.defined() ? (uint64_t*)r.masks.data_ptr<int64_t>() : nullptr, stream);
-    });
 }
 
 // ---- the opt-in fused optimizer step (train_ops.FusedRasterAdam) --------------------------------------------
@@ -407,6 +412,11 @@ AdamRows adam_begin(PyObject* plan) {
 }
 
 // ---- node 1: parameters -> uv, conic, opacity, colour (+ the frame's lists and, early, its image) --------
+// its outputs: the four differentiable per-splat tensors, then what node 2 and the caller take over
+enum PreOutput {
+    PRE_UV, PRE_CONIC, PRE_OPACITY, PRE_RGB, PRE_PACKED, PRE_RANGES, PRE_SORTED, PRE_MASK, PRE_IMAGE, PRE_FW, PRE_NSP,
+    PRE_SEG, PRE_CUT_FLAGS, PRE_FULL_RANGES, PRE_OVERFLOW, PRE_MASKS, PRE_OUTPUTS
+};
 struct Preprocess : public torch::autograd::Function<Preprocess> {
     static variable_list forward(AutogradContext* ctx, Tensor xyz, Tensor quaternion, Tensor scale, Tensor opacity,
                                  Tensor rgb, c10::optional<Tensor> sh_opt, Tensor camera_T_world, Tensor K, Tensor bg,
@@ -419,11 +429,13 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
         const int n_sh = has_sh ? (int)sh.size(2) + 1 : 1;
         const int ntx = ((int)W + 15) / 16, nty = ((int)H + 15) / 16, T = ntx * nty;
         const bool whole = row0 == 0 && row1 == nty;
-        const int sort_prefix = g_sort_prefix ? GS_SORT_PREFIX : 0;
+        const int sort_prefix = g_policy.sort_prefix ? GS_SORT_PREFIX : 0;
         void* stream = cur_stream();
 
-        const HintKey shape{(int)dev.index(), N, T, (int)row0, (int)row1, 0};
-        const bool cut = want_depth_cut(shape, N, ntx, (int)row0, (int)row1, whole, sort_prefix);
+        const HintKey shape{(int)dev.index(), N, T, (int)row0, (int)row1};
+        const FrameStart start = begin_frame(shape, ntx, whole, sort_prefix);
+        const bool cut = start.cut;
+        int32_t* const host = start.host;
         const int stride = cut ? gs_cut_sample_stride(N) : 1;
         const int64_t n_ws = (int64_t)gs_preprocess_workspace_ints(N), n_tc = (int64_t)gs_tile_workspace_ints(T);
         const int64_t n_cut = cut ? (int64_t)gs_cut_workspace_ints(N, T) : 0;
@@ -454,19 +466,8 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
                                              nullptr /* rgb_render: the colour is in the packed record */, packed,
                                              cut ? bin_rec : nullptr, cut ? cut_ws : nullptr, depth_hist, stride, stream);
         });
-        HintKey key = shape;
-        key.mode = cut ? 1 : 0;
-        int64_t guess = -1, guess_overflow = -1;
-        int32_t* host;
-        hipEvent_t ready;
-        {
-            std::lock_guard<std::mutex> lock(g_mutex);
-            auto it = g_capacity.find(key);
-            if (it != g_capacity.end()) guess = it->second;
-            auto io = g_overflow_capacity.find(key);
-            if (io != g_overflow_capacity.end()) guess_overflow = io->second;
-            std::tie(host, ready) = pinned_slot((int)dev.index());
-        }
+        const FrameKind kind{cut, sort_prefix, !cut && sort_prefix != 0, true};
+        const FramePlan plan = plan_frame(start.st, g_policy, kind);
         timed("gs_tile_count", stream, [&] {
             if (cut)
                 return gs_tile_count_cut(bin_rec, N, count, ntx, nty, (float)mh_dist, (int)row0, (int)row1, tile_counts, cut_ws,
@@ -475,11 +476,11 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
                                  tile_counts, ranges_buf, host, stream);
         });
         // (the scan kernel of the count wrote the frame's counts into the pinned slot: no copy in the stream)
-        hip_ok(hipEventRecord(ready, (hipStream_t)stream));
+        hip_ok(hipEventRecord(start.ready, (hipStream_t)stream));
 
         auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
         Tensor sorted, keys;
-        auto emit_sort = [&](int64_t capacity, int64_t longest = -1) {
+        auto emit_sort = [&](int64_t capacity, int64_t longest) {
             sorted = torch::empty({capacity}, i32);
             keys = torch::empty({capacity}, i32.dtype(torch::kInt64));
             if (capacity > 0)
@@ -494,118 +495,67 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
                                                      sorted.data_ptr<int32_t>(), sort_prefix, longest, stream);
                 });
         };
-
-        // the frame's only device->host read: (S, V) -- with the depth cut (S' kept, V, S complete) --, to size the
-        // outputs.  With capacities guessed from earlier frames of this shape, emit + sort + render are enqueued before
-        // the host waits.
-        const bool speculative = guess >= 0 && (!cut || guess_overflow >= 0);
-        CutRef cref{bin_rec, tile_counts, cut_ws, full_ranges, N, (float)mh_dist, 0, cut ? cut_feedback_word(shape) : nullptr};
+        CutRef cref{bin_rec, tile_counts, cut_ws, full_ranges, N, (float)mh_dist, plan.overflow_capacity, start.cut_word};
+        auto render = [&](Tensor& lists, Tensor& list_keys, bool segments, int phases) {
+            return render_forward(packed, rgbr, ranges_buf, lists, list_keys, bg, (int)W, (int)H, (int)row0, (int)row1, whole,
+                                  sort_prefix, stream, segments, 0, cut ? &cref : nullptr, phases);
+        };
         RenderOut out;
-        bool rendered = false;
-        int64_t capacity = 0;
-        // Complete-list frames also guess the LONGEST list (from the shape's last frame): none beyond 4096 entries ->
-        // the sort's walk-grid kernel for those is not enqueued, none beyond the prefix -> neither is the render's
-        // repair phase (a sparse frame -- workload B -- otherwise pays ~5 us each for three kernels that find nothing
-        // to do).  The count pass's scan reports the true value with the frame's counts; a guess that was too small
-        // is made good below: the repair enqueued late, or emit + sort + render repeated.
-        int64_t longest_guess = -1;
-        int phases = GS_PREFIX_RENDER | GS_PREFIX_REPAIR;
-        if (speculative) {
-            capacity = guess;
-            cref.overflow_capacity = guess_overflow;
-            if (!cut && sort_prefix) {
-                std::lock_guard<std::mutex> lock(g_mutex);
-                auto il = g_longest_list.find(key);
-                if (il != g_longest_list.end()) longest_guess = il->second;
-            }
-            emit_sort(capacity, longest_guess);
-            if (g_early_render && sort_prefix && (cut || capacity > sort_prefix)) {
-                if (longest_guess >= 0 && longest_guess <= sort_prefix) phases = GS_PREFIX_RENDER;
-                out = render_forward(packed, rgbr, ranges_buf, sorted, keys, bg, (int)W, (int)H, (int)row0, (int)row1, whole,
-                                     sort_prefix, stream, shape, false, 0, cut ? &cref : nullptr, phases);
-                rendered = true;
-            }
+        const int64_t n_tiles = (int64_t)(row1 - row0) * ntx;
+        if (plan.speculative) emit_sort(plan.capacity, plan.longest_guess);
+        if (plan.early_render) {
+            ShapeState st = start.st;   // (a capacity is no exact count: nothing is stored)
+            out = render(sorted, keys, !cut && segments_for(st, g_policy, plan.capacity, false, n_tiles), plan.phases);
         }
-        hip_ok(hipEventSynchronize(ready));
-        const int64_t S = host[0], V = host[1], S_complete = cut ? host[2] : host[0];
-        const int64_t longest = cut ? -1 : host[2];
-        // (a list beyond 4096 entries whose sort kernel was not enqueued: the lists are not what the render needs)
-        const bool unsorted_long = speculative && longest_guess >= 0 && longest_guess <= 4096 && longest > 4096;
-        const bool miss = speculative && (S > capacity || (cut && S_complete > cref.overflow_capacity) || unsorted_long);
-        {
-            std::lock_guard<std::mutex> lock(g_mutex);
-            g_counters.frames++;
-            g_counters.speculative += speculative;
-            g_counters.cut_frames += cut;
-            g_counters.s_min = g_counters.s_min < 0 ? S_complete : std::min(g_counters.s_min, S_complete);
-            g_counters.s_max = std::max(g_counters.s_max, S_complete);
-            g_counters.misses += miss;
-            g_counters.long_list_misses += unsorted_long;
-            int64_t& hint = g_capacity[key];
-            hint = std::max(hint, S + S / 4 + 4096);
-            if (cut) {
-                int64_t& ho = g_overflow_capacity[key];
-                ho = std::max(ho, S_complete + S_complete / 4 + 4096);
-            }
-            g_complete_count[shape] = S_complete;
-            g_visible_count[shape] = V;
-            if (!cut && sort_prefix) g_longest_list[key] = longest;
-        }
-        if (!speculative || miss) {
-            cref.overflow_capacity = S_complete;
-            emit_sort(S, longest);
-            rendered = false;
+        // the frame's only device->host read: (S, V, longest list) -- with the depth cut (S' kept, V, S complete) --, to
+        // size the outputs
+        hip_ok(hipEventSynchronize(start.ready));
+        const int64_t V = host[1];
+        const FrameCounts counts{host[0], cut ? host[2] : host[0], cut ? -1 : host[2]};
+        const int64_t S = counts.S;
+        const FrameOutcome res = classify_frame(plan, kind, counts);
+        const bool segments = finish_frame(shape, kind, plan, res, counts, n_tiles, V);
+        if (res.re_emit) {
+            cref.overflow_capacity = counts.S_complete;
+            emit_sort(S, counts.longest);
         }
         Tensor sorted_g = sorted.narrow(0, 0, S), keys_g = keys.narrow(0, 0, S);
-        if (!rendered) {
-            phases = (!cut && sort_prefix && longest >= 0 && longest <= sort_prefix) ? GS_PREFIX_RENDER
-                                                                                    : (GS_PREFIX_RENDER | GS_PREFIX_REPAIR);
-            out = render_forward(packed, rgbr, ranges_buf, sorted_g, keys_g, bg, (int)W, (int)H, (int)row0, (int)row1, whole,
-                                 sort_prefix, stream, shape, true, 0, cut ? &cref : nullptr, phases);
-        } else if (!cut && phases == GS_PREFIX_RENDER && longest > sort_prefix && out.prefix_flags.defined()) {
-            // the early render went without its repair phase and a list IS longer than the prefix: repair now
-            render_prefix_repair(out, packed, rgbr, ranges_buf, sorted, keys, bg, (int)W, (int)H, (int)row0, (int)row1, stream);
-            phases = GS_PREFIX_RENDER | GS_PREFIX_REPAIR;
-            std::lock_guard<std::mutex> lock(g_mutex);
-            g_counters.late_repairs++;
-        }
-        if (phases == GS_PREFIX_RENDER && out.prefix_flags.defined()) {
-            std::lock_guard<std::mutex> lock(g_mutex);
-            g_counters.render_only++;
-        }
+        if (res.act == Act::Render)
+            out = render(sorted_g, keys_g, segments, res.phases);
+        else if (res.act == Act::LateRepair)
+            render_prefix(out, packed, rgbr, ranges_buf, sorted, keys, bg, (int)W, (int)H, (int)row0, (int)row1, GS_PREFIX_REPAIR,
+                          stream);
 
-        Tensor uv_t, conic_t;
-        if (cut) {
-            Tensor rec = far.block(7, 8 * nn).view({N, 8}).narrow(0, 0, V);
-            uv_t = rec.narrow(1, 0, 2);
-            conic_t = rec.narrow(1, 2, 3);
-        } else {
-            uv_t = far.block(1, 2 * nn).view({N, 2}).narrow(0, 0, V);
-            conic_t = far.block(3, 3 * nn).view({N, 3}).narrow(0, 0, V);
-        }
-        Tensor opa_t = far.block(4, N).view({N, 1}).narrow(0, 0, V);
-        Tensor packed_t = far.block(6, 12 * (int64_t)N).view({N, 12});
+        Tensor rec = cut ? far.block(7, 8 * nn).view({N, 8}).narrow(0, 0, V) : Tensor();
+        variable_list o(PRE_OUTPUTS);
+        o[PRE_UV] = cut ? rec.narrow(1, 0, 2) : far.block(1, 2 * nn).view({N, 2}).narrow(0, 0, V);
+        o[PRE_CONIC] = cut ? rec.narrow(1, 2, 3) : far.block(3, 3 * nn).view({N, 3}).narrow(0, 0, V);
+        o[PRE_OPACITY] = far.block(4, N).view({N, 1}).narrow(0, 0, V);
         // the colour output of this node only carries the autograd edge of the render gradients' colour columns (the
         // kernels read the colour from the packed record, nobody reads this tensor's values): a stride-0 placeholder
-        Tensor rgbr_t = zero_scalar(dev).expand({V, 3});
-        Tensor ranges_t = iar.block(5, T + 1);
-        Tensor mask_t = iar.block(6, (N + 3) / 4).view(torch::kBool).narrow(0, 0, N);
+        o[PRE_RGB] = zero_scalar(dev).expand({V, 3});
+        o[PRE_PACKED] = far.block(6, 12 * nn).view({N, 12});
+        o[PRE_RANGES] = iar.block(5, T + 1);
+        o[PRE_SORTED] = sorted_g;
+        o[PRE_MASK] = iar.block(6, (N + 3) / 4).view(torch::kBool).narrow(0, 0, N);
+        o[PRE_IMAGE] = out.image;
+        o[PRE_FW] = out.fw;
+        o[PRE_NSP] = out.nsp;
+        o[PRE_SEG] = out.seg;
         // depth-cut frames: what the backward needs to read a repaired tile's complete list (empty otherwise)
-        Tensor flags_t = cut ? out.cut_flags : torch::empty({0}, i32);
-        Tensor full_ranges_t = cut ? iar.block(8, T + 1) : torch::empty({0}, i32);
-        Tensor overflow_t = cut ? out.overflow_sorted : torch::empty({0}, i32);
+        o[PRE_CUT_FLAGS] = cut ? out.cut_flags : torch::empty({0}, i32);
+        o[PRE_FULL_RANGES] = cut ? iar.block(8, T + 1) : torch::empty({0}, i32);
+        o[PRE_OVERFLOW] = cut ? out.overflow_sorted : torch::empty({0}, i32);
         // the touch masks the forward left for the backward (empty: the backward builds its own)
-        Tensor masks_t = out.masks.defined() ? out.masks : torch::empty({0}, i32.dtype(torch::kInt64));
+        o[PRE_MASKS] = out.masks.defined() ? out.masks : torch::empty({0}, i32.dtype(torch::kInt64));
         ctx->save_for_backward({xyz, quaternion, scale, camera_T_world, K, far.block(0, 3), iar.block(2, N),
                                 far.block(4, N).view({N, 1})});
         ctx->saved_data["n_sh"] = (int64_t)n_sh;
         ctx->saved_data["V"] = V;
         if (adam_plan) ctx->saved_data["adam_plan"] = c10::IValue(adam_plan);
         ctx->set_materialize_grads(false);
-        ctx->mark_non_differentiable({packed_t, ranges_t, sorted_g, mask_t, out.image, out.fw, out.nsp, out.seg, flags_t,
-                                      full_ranges_t, overflow_t, masks_t});
-        return {uv_t, conic_t, opa_t, rgbr_t, packed_t, ranges_t, sorted_g, mask_t, out.image, out.fw, out.nsp, out.seg,
-                flags_t, full_ranges_t, overflow_t, masks_t};
+        ctx->mark_non_differentiable(variable_list(o.begin() + PRE_PACKED, o.end()));
+        return o;
     }
 
     static variable_list backward(AutogradContext* ctx, variable_list g) {
@@ -680,23 +630,17 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
             out[0] = grad_xyz;
             return out;
         }
-        Arena ga(torch::kFloat32, dev, {3 * n, 4 * n, 3 * n, n, 3 * n, extra * n});
+        ParamGrads ga(dev, n, n_sh);
         if (n > 0) {
             void* stream = cur_stream();
             timed("gs_preprocess_backward", stream, [&] {
                 return gs_preprocess_backward(xyz.data_ptr(), quaternion.data_ptr(), scale.data_ptr(), n_sh,
                                               camera_T_world.data_ptr(), K.data_ptr(), center.data_ptr(),
                                               rank.data_ptr<int32_t>(), opacity_act.data_ptr(), slab.data_ptr(), 0, (int)n,
-                                              ga.ptr<float>(0), ga.ptr<float>(1), ga.ptr<float>(2), ga.ptr<float>(3),
-                                              ga.ptr<float>(4), n_sh > 1 ? ga.ptr<float>(5) : nullptr, stream);
+                                              ga.ptr(0), ga.ptr(1), ga.ptr(2), ga.ptr(3), ga.ptr(4), ga.ptr(5), stream);
             });
         }
-        out[0] = ga.block(0, 3 * n).view({n, 3});
-        out[1] = ga.block(1, 4 * n).view({n, 4});
-        out[2] = ga.block(2, 3 * n).view({n, 3});
-        out[3] = ga.block(3, n).view({n, 1});
-        out[4] = ga.block(4, 3 * n).view({n, 3});
-        if (n_sh > 1) out[5] = ga.block(5, extra * n).view({n, 3, (int64_t)n_sh - 1});
+        ga.views(out);
         return out;
     }
 };
@@ -771,25 +715,8 @@ std::tuple<Tensor, Tensor, Tensor> rasterize_impl(Tensor xyz, Tensor quaternion,
                                                   int64_t height, double near_thresh, double far_thresh,
                                                   double cull_mask_padding, double mh_dist, Tensor background_rgb,
                                                   int64_t row0, int64_t row1, PlanHolder adam_plan) {
+    check_frame_inputs(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, background_rgb, width, height);
     const auto dev = xyz.device();
-    const int64_t N = xyz.size(0);
-    TORCH_CHECK(xyz.is_cuda(), "xyz is not a CUDA tensor");
-    require_f32_cuda(xyz, "xyz", dev, {N, 3});
-    require_f32_cuda(quaternion, "quaternion", dev, {N, 4});
-    require_f32_cuda(scale, "scale", dev, {N, 3});
-    require_f32_cuda(opacity, "opacity", dev, {N, 1});
-    require_f32_cuda(rgb, "rgb", dev, {N, 3});
-    require_f32_cuda(camera_T_world, "camera_T_world", dev, {4, 4});
-    require_f32_cuda(K, "K", dev, {3, 3});
-    require_f32_cuda(background_rgb, "background_rgb", dev, {3});
-    if (sh.has_value() && sh->defined()) {
-        TORCH_CHECK(sh->is_cuda() && sh->device() == dev, "sh is not a CUDA tensor on ", dev);
-        TORCH_CHECK(sh->scalar_type() == torch::kFloat32, "sh is not a float tensor");
-        TORCH_CHECK(sh->dim() == 3 && sh->size(0) == N && sh->size(1) == 3 &&
-                        (sh->size(2) == 3 || sh->size(2) == 8 || sh->size(2) == 15),
-                    "sh has the wrong shape ", sh->sizes());
-    }
-    TORCH_CHECK(width > 0 && height > 0, "image must be non-empty");
     const int64_t nty = (height + 15) / 16;
     if (row1 < 0) row1 = nty;
     TORCH_CHECK(0 <= row0 && row0 <= row1 && row1 <= nty, "bad tile row range");
@@ -797,9 +724,10 @@ std::tuple<Tensor, Tensor, Tensor> rasterize_impl(Tensor xyz, Tensor quaternion,
     auto o = Preprocess::apply(xyz.contiguous(), quaternion.contiguous(), scale.contiguous(), opacity.contiguous(),
                                rgb.contiguous(), sh, camera_T_world.contiguous(), K.contiguous(), background_rgb.contiguous(),
                                width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, row0, row1, adam_plan);
-    Tensor image = Render::apply(o[0], o[1], o[2], o[3], o[4], o[5], o[6], background_rgb.contiguous(), o[8], o[9], o[10],
-                                 o[11], o[12], o[13], o[14], o[15], row0, row1);
-    return std::make_tuple(image, o[7], o[0]);
+    Tensor image = Render::apply(o[PRE_UV], o[PRE_CONIC], o[PRE_OPACITY], o[PRE_RGB], o[PRE_PACKED], o[PRE_RANGES],
+                                 o[PRE_SORTED], background_rgb.contiguous(), o[PRE_IMAGE], o[PRE_FW], o[PRE_NSP], o[PRE_SEG],
+                                 o[PRE_CUT_FLAGS], o[PRE_FULL_RANGES], o[PRE_OVERFLOW], o[PRE_MASKS], row0, row1);
+    return std::make_tuple(image, o[PRE_MASK], o[PRE_UV]);
 }
 
 std::tuple<Tensor, Tensor, Tensor> rasterize(Tensor xyz, Tensor quaternion, Tensor scale, Tensor opacity, Tensor rgb,
@@ -859,7 +787,13 @@ struct ShardSpec {
         }
     }
 };
-struct FrameRec {
+// the numbers of a frame's exchange plan (what last_plan() reports of the latest sharded frame)
+struct PlanNumbers {
+    int64_t v_lo = 0, v_hi = 0, V = 0, S = 0, L = 0;
+    std::vector<int64_t> send_splits, recv_splits;
+    bool compact = false;
+};
+struct FrameRec : PlanNumbers {
     ShardSpec spec;
     Tensor xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, bg;   // the replicated values
     int N = 0, n_sh = 1, W = 0, H = 0, row0 = 0, row1 = 0, i0 = 0, i1 = 0;
@@ -867,9 +801,7 @@ struct FrameRec {
     Tensor ibuf, fbuf, hbuf;   // arenas (kept alive: everything below points into them)
     Tensor packed, rgbr, ranges, sorted_g, center, rank_t, opa_act, halo_mask, halo_send, halo_ws;
     RenderOut out;
-    int64_t V = 0, L = 0, S = 0, v_lo = 0, v_hi = 0;
-    bool compact = false, fused = false;   // fused: compact through gs_band_frontend (its workspace layout in halo_ws)
-    std::vector<int64_t> send_splits, recv_splits;
+    bool fused = false;   // compact through gs_band_frontend (its workspace layout in halo_ws)
     Tensor owned_rows, rendered_uv_grad;
     // band-compact frames: the received rows and their per-sender offsets, handed from the render node's backward to
     // the per-Gaussian backward, which sums them on the spot (gs_preprocess_backward_gathered) unless somebody needs
@@ -897,13 +829,10 @@ struct RowCosts {
 };
 std::map<int, RowCosts> g_row_costs;   // per device (one slot per process let a second device's frame overwrite the first's)
 
-struct PlanInfo {
-    int64_t v_lo = 0, v_hi = 0, V = 0, S = 0, L = 0;
-    std::vector<int64_t> send_splits, recv_splits;
+struct PlanInfo : PlanNumbers {
     // tests (debug_keep_band_lists): the band's tile ranges and sorted list of the latest sharded frame, and the send
     // list that maps a band-compact row back to its visible index
     Tensor ranges, sorted_g, send_list;
-    bool compact = false;
 } g_last_plan;
 bool g_keep_band_lists = false;
 
@@ -925,7 +854,7 @@ struct OwnerPreprocess : public torch::autograd::Function<OwnerPreprocess> {
         const int n_sh = fr.n_sh, W = fr.W, H = fr.H;
         const int ntx = (W + 15) / 16, nty = (H + 15) / 16, T = ntx * nty;
         const int row0 = fr.row0, row1 = fr.row1;
-        const int sort_prefix = g_sort_prefix ? GS_SORT_PREFIX : 0;
+        const int sort_prefix = g_policy.sort_prefix ? GS_SORT_PREFIX : 0;
         const int plan_ints = 4 + 2 * G;
         // band-compact per-Gaussian stage (csrc/preprocess.hip): the full evaluation only for the Gaussians that can
         // reach the band, arrays compacted to those rows (row index l); everything downstream then works on rows l
@@ -955,12 +884,10 @@ struct OwnerPreprocess : public torch::autograd::Function<OwnerPreprocess> {
         const int32_t *items_n = count, *subset = nullptr, *subset_n = nullptr;
         // the frame's host read: (S, V, -) from the tile scan and the plan record behind it.  Band-compact path: both
         // kernels write straight into the pinned slot (no copy kernel in the stream); otherwise one copy of the record
-        int32_t* host;
-        hipEvent_t ready;
-        {
-            std::lock_guard<std::mutex> lock(g_mutex);
-            std::tie(host, ready) = pinned_slot((int)dev.index());
-        }
+        // (a band shares the record of the single-GPU frame of its shape; it never takes the depth cut)
+        const HintKey key{(int)dev.index(), N, T, row0, row1};
+        const FrameStart start = begin_frame(key, ntx, false, sort_prefix);
+        int32_t* const host = start.host;
         const int rec_at = compact ? 3 : 2;   // where the plan record starts in the host buffer
         if (fused) {
             // the fused band frontend: cull + band masks, scan, compaction of the API arrays and of the band's rows,
@@ -974,9 +901,6 @@ struct OwnerPreprocess : public torch::autograd::Function<OwnerPreprocess> {
                                         center, mask, rank, uv, opa, h + N, h, uv_l, xyz_cam, conic, packed, record,
                                         host + rec_at, stream);
             });
-            bin_uv = uv_l;
-            items_n = record;   // record[0] = rows of the send list = rows of the compact arrays
-            rgbr = packed;      // (the one-coefficient render reads the colour from the record)
         } else if (compact) {
             timed("gs_band_project", stream, [&] {
                 return gs_band_project(fr.xyz.data_ptr(), fr.scale.data_ptr(), fr.opacity.data_ptr(), fr.camera_T_world.data_ptr(),
@@ -994,9 +918,6 @@ struct OwnerPreprocess : public torch::autograd::Function<OwnerPreprocess> {
                                                   fr.camera_T_world.data_ptr(), fr.K.data_ptr(), center, h + N, record, N, vis_idx,
                                                   uv, opa, uv_l, xyz_cam, conic, packed, stream);
             });
-            bin_uv = uv_l;
-            items_n = record;   // record[0] = rows of the send list = rows of the compact arrays
-            rgbr = packed;      // (the one-coefficient render reads the colour from the record)
         } else {
             timed("gs_preprocess_forward", stream, [&] {
                 return gs_preprocess_forward(fr.xyz.data_ptr(), fr.quaternion.data_ptr(), fr.scale.data_ptr(), fr.opacity.data_ptr(),
@@ -1013,13 +934,18 @@ struct OwnerPreprocess : public torch::autograd::Function<OwnerPreprocess> {
             subset = G > 1 ? h + N : nullptr;
             subset_n = G > 1 ? record : nullptr;
         }
+        if (compact) {
+            bin_uv = uv_l;
+            items_n = record;   // record[0] = rows of the send list = rows of the compact arrays
+            rgbr = packed;      // (the one-coefficient render reads the colour from the record)
+        }
         timed("gs_tile_count", stream, [&] {
             return gs_tile_count(bin_uv, bin_conic, N, items_n, subset, subset_n, ntx, nty, (float)fr.mh_dist, row0, row1,
                                  tile_counts, ranges_buf, compact ? host : nullptr, stream);
         });
         auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
         Tensor sorted, keys;
-        auto emit_sort = [&](int64_t capacity, int64_t longest = -1) {
+        auto emit_sort = [&](int64_t capacity, int64_t longest) {
             sorted = torch::empty({capacity}, i32);
             keys = torch::empty({capacity}, i32.dtype(torch::kInt64));
             if (capacity > 0)
@@ -1030,68 +956,40 @@ struct OwnerPreprocess : public torch::autograd::Function<OwnerPreprocess> {
                                                      sorted.data_ptr<int32_t>(), sort_prefix, longest, stream);
                 });
         };
-        const HintKey key{(int)dev.index(), N, T, row0, row1};
-        // compact frames also guess the band's LONGEST list from the shape's last frame (the tile scan reports it with
-        // the counts): none beyond 4096 entries -> the sort's walk-grid kernel for those is not enqueued (~5 us that
-        // find nothing to do); a guess that was too small repeats emit + sort + render, as a capacity miss does
-        int64_t guess = -1, longest_guess = -1;
-        {
-            std::lock_guard<std::mutex> lock(g_mutex);
-            auto it = g_capacity.find(key);
-            if (it != g_capacity.end()) guess = it->second;
-            auto il = g_longest_list.find(key);
-            if (compact && sort_prefix && il != g_longest_list.end()) longest_guess = il->second;
-        }
+        // (compact frames also guess the band's LONGEST list: the tile scan reports it with the counts.  No late repair:
+        // a guess that was too small repeats emit + sort + render, as a capacity miss does)
+        const FrameKind kind{false, sort_prefix, compact && sort_prefix != 0, false};
+        const FramePlan plan = plan_frame(start.st, g_policy, kind);
         if (!compact)
             hip_ok(hipMemcpyAsync(host, ranges_buf + T, (2 + plan_ints) * sizeof(int32_t), hipMemcpyDeviceToHost,
                                   (hipStream_t)stream));
-        hip_ok(hipEventRecord(ready, (hipStream_t)stream));
-        const bool speculative = guess >= 0;
+        hip_ok(hipEventRecord(start.ready, (hipStream_t)stream));
         // a band.  With the real exchange the other bands' rows are overwritten by the all-gather and nothing reads
         // the other rows' splat counts / weights: no zero fill (5 us per frame); a stand-in exchange (tests, the
         // one-GPU measurement of a rank's frame) returns the band image with zeros outside it
         const bool whole = sp.a2a_hook.is_none();
         const int64_t image_rows =
             !sp.a2a_hook.is_none() ? 0 : (sp.equal_bands ? sp.padded_height : 16 * (int64_t)nty + sp.chunk_rows);
-        bool rendered = false;
-        int64_t capacity = 0;
-        if (speculative) {
-            capacity = guess;
-            emit_sort(capacity, longest_guess);
-            if (g_early_render && sort_prefix && capacity > sort_prefix) {
-                fr.out = render_forward(packed, rgbr, ranges_buf, sorted, keys, fr.bg, W, H, row0, row1, whole, sort_prefix, stream,
-                                        key, false, image_rows);
-                rendered = true;
-            }
+        const int64_t n_tiles = (int64_t)(row1 - row0) * ntx;
+        auto render = [&](Tensor& lists, Tensor& list_keys, bool segments) {
+            return render_forward(packed, rgbr, ranges_buf, lists, list_keys, fr.bg, W, H, row0, row1, whole, sort_prefix, stream,
+                                  segments, image_rows);
+        };
+        if (plan.speculative) emit_sort(plan.capacity, plan.longest_guess);
+        if (plan.early_render) {
+            ShapeState st = start.st;   // (a capacity is no exact count: nothing is stored)
+            fr.out = render(sorted, keys, segments_for(st, g_policy, plan.capacity, false, n_tiles));
         }
-        hip_ok(hipEventSynchronize(ready));
+        hip_ok(hipEventSynchronize(start.ready));
         // the plan's host half: rows to send, V, v_lo, v_hi, send[G], recv[G]
         const int32_t* rec = host + rec_at;
         const int64_t S = host[0], V = rec[1], L = compact ? rec[0] : rec[1];
-        const int64_t longest = compact ? host[2] : -1;   // (k_scan_tiles' host mirror: S, V, longest list)
-        // (a list beyond 4096 entries whose sort kernel was not enqueued: the lists are not what the render needs)
-        const bool unsorted_long = speculative && longest_guess >= 0 && longest_guess <= 4096 && longest > 4096;
-        const bool miss = speculative && (S > capacity || unsorted_long);
-        {
-            std::lock_guard<std::mutex> lock(g_mutex);
-            g_counters.frames++;
-            g_counters.speculative += speculative;
-            g_counters.s_min = g_counters.s_min < 0 ? S : std::min(g_counters.s_min, S);
-            g_counters.s_max = std::max(g_counters.s_max, S);
-            g_counters.misses += miss;
-            g_counters.long_list_misses += unsorted_long;
-            int64_t& hint = g_capacity[key];
-            hint = std::max(hint, S + S / 4 + 4096);
-            if (compact && sort_prefix) g_longest_list[key] = longest;
-        }
-        if (!speculative || miss) {
-            emit_sort(S, longest);
-            rendered = false;
-        }
+        const FrameCounts counts{S, S, compact ? host[2] : -1};   // (k_scan_tiles' host mirror: S, V, longest list)
+        const FrameOutcome res = classify_frame(plan, kind, counts);
+        const bool segments = finish_frame(key, kind, plan, res, counts, n_tiles);
+        if (res.re_emit) emit_sort(S, counts.longest);
         Tensor sorted_g = sorted.narrow(0, 0, S), keys_g = keys.narrow(0, 0, S);
-        if (!rendered)
-            fr.out = render_forward(packed, rgbr, ranges_buf, sorted_g, keys_g, fr.bg, W, H, row0, row1, whole, sort_prefix, stream,
-                                    key, true, image_rows);
+        if (res.act == Act::Render) fr.out = render(sorted_g, keys_g, segments);
         fr.v_lo = rec[2];
         fr.v_hi = rec[3];
         fr.send_splits.assign(rec + 4, rec + 4 + G);
@@ -1115,14 +1013,7 @@ struct OwnerPreprocess : public torch::autograd::Function<OwnerPreprocess> {
         fr.bwd_mode = gs_get_backward_mode();
         {
             std::lock_guard<std::mutex> lock(g_mutex);
-            g_last_plan.v_lo = fr.v_lo;
-            g_last_plan.v_hi = fr.v_hi;
-            g_last_plan.V = V;
-            g_last_plan.S = S;
-            g_last_plan.send_splits = fr.send_splits;
-            g_last_plan.recv_splits = fr.recv_splits;
-            g_last_plan.L = L;
-            g_last_plan.compact = compact;
+            static_cast<PlanNumbers&>(g_last_plan) = fr;
             if (g_keep_band_lists) {
                 int64_t n_send = 0;
                 for (int64_t c : fr.send_splits) n_send += c;
@@ -1159,38 +1050,33 @@ struct OwnerPreprocess : public torch::autograd::Function<OwnerPreprocess> {
         fr.recv_rows = Tensor();
         bool gathered = fr.gather_pending;
         fr.gather_pending = false;
-        {
-            // a loss term put directly on uv needs the owned rows as a tensor after all
-            const Tensor& gu = g[0];
-            const Tensor& rendered0 = fr.rendered_uv_grad;
-            const bool extra_uv = gu.defined() && fr.v_hi > fr.v_lo && gu.stride(0) != 0 &&
-                                  !(rendered0.defined() && gu.unsafeGetTensorImpl() == rendered0.unsafeGetTensorImpl());
-            if (gathered && extra_uv) {
-                const int64_t n_own = fr.v_hi - fr.v_lo;
-                owned = torch::empty({std::max<int64_t>(n_own, 1), SLAB_WIDTH}, recv.options()).narrow(0, 0, n_own);
-                void* stream = cur_stream();
-                timed("gs_halo_gather_sum", stream, [&] {
-                    return gs_band_gather_sum(fr.halo_ws.data_ptr<int32_t>(), fr.N, sp.G, sp.rank, sp.owner_blocks.data(),
-                                              fr.rank_t.data_ptr<int32_t>(), (int)fr.v_lo, recv.data_ptr(),
-                                              fr.recv_offsets.data(), owned.data_ptr(), stream);
-                });
-                gathered = false;
-            }
-        }
         // a loss term put directly on uv arrives on top of what node 2 handed over (the owned rows' uv columns,
-        // or a stride-0 placeholder): add the rest for the owned rows
+        // or a stride-0 placeholder)
         const Tensor& g_uv = g[0];
         Tensor rendered = fr.rendered_uv_grad;
         fr.rendered_uv_grad = Tensor();
-        if (g_uv.defined() && fr.v_hi > fr.v_lo && g_uv.stride(0) != 0 &&
-            !(rendered.defined() && g_uv.unsafeGetTensorImpl() == rendered.unsafeGetTensorImpl())) {
+        const bool extra_uv = g_uv.defined() && fr.v_hi > fr.v_lo && g_uv.stride(0) != 0 &&
+                              !(rendered.defined() && g_uv.unsafeGetTensorImpl() == rendered.unsafeGetTensorImpl());
+        if (gathered && extra_uv) {
+            // ... and needs the owned rows as a tensor after all
+            const int64_t n_own = fr.v_hi - fr.v_lo;
+            owned = torch::empty({std::max<int64_t>(n_own, 1), SLAB_WIDTH}, recv.options()).narrow(0, 0, n_own);
+            void* stream = cur_stream();
+            timed("gs_halo_gather_sum", stream, [&] {
+                return gs_band_gather_sum(fr.halo_ws.data_ptr<int32_t>(), fr.N, sp.G, sp.rank, sp.owner_blocks.data(),
+                                          fr.rank_t.data_ptr<int32_t>(), (int)fr.v_lo, recv.data_ptr(),
+                                          fr.recv_offsets.data(), owned.data_ptr(), stream);
+            });
+            gathered = false;
+        }
+        if (extra_uv) {   // add the rest for the owned rows
             Tensor extra = g_uv.narrow(0, fr.v_lo, fr.v_hi - fr.v_lo);
             if (rendered.defined() && rendered.stride(0) != 0) extra = extra - rendered.narrow(0, fr.v_lo, fr.v_hi - fr.v_lo);
             owned = owned.clone();
             owned.narrow(1, 4, 2).add_(extra);
         }
-        const int64_t n = fr.i1 - fr.i0, extra_w = 3 * (int64_t)(n_sh - 1);
-        Arena ga(torch::kFloat32, dev, {3 * n, 4 * n, 3 * n, n, 3 * n, extra_w * n});
+        const int64_t n = fr.i1 - fr.i0;
+        ParamGrads ga(dev, n, n_sh);
         if (n > 0) {
             void* stream = cur_stream();
             const int64_t i0 = fr.i0;
@@ -1201,22 +1087,16 @@ struct OwnerPreprocess : public torch::autograd::Function<OwnerPreprocess> {
                         fr.scale.data_ptr<float>() + 3 * i0, n_sh, fr.camera_T_world.data_ptr(), fr.K.data_ptr(),
                         fr.center.data_ptr(), fr.rank_t.data_ptr<int32_t>() + i0, fr.opa_act.data_ptr(),
                         fr.halo_ws.data_ptr<int32_t>(), fr.N, sp.G, sp.rank, sp.owner_blocks.data(), recv.data_ptr(),
-                        fr.recv_offsets.data(), (int)n, ga.ptr<float>(0), ga.ptr<float>(1), ga.ptr<float>(2),
-                        ga.ptr<float>(3), ga.ptr<float>(4), n_sh > 1 ? ga.ptr<float>(5) : nullptr, stream);
+                        fr.recv_offsets.data(), (int)n, ga.ptr(0), ga.ptr(1), ga.ptr(2), ga.ptr(3), ga.ptr(4), ga.ptr(5),
+                        stream);
                 return gs_preprocess_backward(fr.xyz.data_ptr<float>() + 3 * i0, fr.quaternion.data_ptr<float>() + 4 * i0,
                                               fr.scale.data_ptr<float>() + 3 * i0, n_sh, fr.camera_T_world.data_ptr(),
                                               fr.K.data_ptr(), fr.center.data_ptr(), fr.rank_t.data_ptr<int32_t>() + i0,
-                                              fr.opa_act.data_ptr(), owned.data_ptr(), (int)fr.v_lo, (int)n, ga.ptr<float>(0),
-                                              ga.ptr<float>(1), ga.ptr<float>(2), ga.ptr<float>(3), ga.ptr<float>(4),
-                                              n_sh > 1 ? ga.ptr<float>(5) : nullptr, stream);
+                                              fr.opa_act.data_ptr(), owned.data_ptr(), (int)fr.v_lo, (int)n, ga.ptr(0),
+                                              ga.ptr(1), ga.ptr(2), ga.ptr(3), ga.ptr(4), ga.ptr(5), stream);
             });
         }
-        out[0] = ga.block(0, 3 * n).view({n, 3});
-        out[1] = ga.block(1, 4 * n).view({n, 4});
-        out[2] = ga.block(2, 3 * n).view({n, 3});
-        out[3] = ga.block(3, n).view({n, 1});
-        out[4] = ga.block(4, 3 * n).view({n, 3});
-        if (n_sh > 1) out[5] = ga.block(5, extra_w * n).view({n, 3, (int64_t)n_sh - 1});
+        ga.views(out);
         return out;
     }
 };
@@ -1358,28 +1238,12 @@ std::tuple<Tensor, Tensor, Tensor> sharded_rasterize(
     int64_t width, int64_t height, double near_thresh, double far_thresh, double cull_mask_padding, double mh_dist,
     Tensor background_rgb, int64_t world_size, int64_t rank, std::vector<int64_t> bounds, std::vector<int64_t> owner_blocks,
     py::object process_group, py::object all_to_all_hook, bool cost_bands) {
+    const bool has_sh = check_frame_inputs(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, background_rgb, width, height);
     const auto dev = xyz.device();
     const int64_t N = xyz.size(0);
-    TORCH_CHECK(xyz.is_cuda(), "xyz is not a CUDA tensor");
-    require_f32_cuda(xyz, "xyz", dev, {N, 3});
-    require_f32_cuda(quaternion, "quaternion", dev, {N, 4});
-    require_f32_cuda(scale, "scale", dev, {N, 3});
-    require_f32_cuda(opacity, "opacity", dev, {N, 1});
-    require_f32_cuda(rgb, "rgb", dev, {N, 3});
-    require_f32_cuda(camera_T_world, "camera_T_world", dev, {4, 4});
-    require_f32_cuda(K, "K", dev, {3, 3});
-    require_f32_cuda(background_rgb, "background_rgb", dev, {3});
-    const bool has_sh = sh.has_value() && sh->defined();
-    if (has_sh) {
-        TORCH_CHECK(sh->is_cuda() && sh->device() == dev && sh->scalar_type() == torch::kFloat32, "sh is not a float CUDA tensor");
-        TORCH_CHECK(sh->dim() == 3 && sh->size(0) == N && sh->size(1) == 3 &&
-                        (sh->size(2) == 3 || sh->size(2) == 8 || sh->size(2) == 15),
-                    "sh has the wrong shape ", sh->sizes());
-    }
     const int G = (int)world_size, me = (int)rank;
     TORCH_CHECK(G >= 1 && G <= GS_MAX_RANKS && me >= 0 && me < G, "bad world size / rank");
     TORCH_CHECK((int)bounds.size() == G + 1 && (int)owner_blocks.size() == G + 1, "bounds / owner_blocks need world_size + 1 entries");
-    TORCH_CHECK(width > 0 && height > 0, "image must be non-empty");
     const int64_t nty = (height + 15) / 16;
     auto fr = std::make_shared<FrameRec>();
     ShardSpec& sp = fr->spec;
@@ -1569,28 +1433,30 @@ py::object take_row_costs() {
 // render repeated with the exact sizes)
 void debug_scale_capacity_hints(double factor) {
     std::lock_guard<std::mutex> lock(g_mutex);
-    for (auto& kv : g_capacity) kv.second = (int64_t)(kv.second * factor);
-    for (auto& kv : g_overflow_capacity) kv.second = (int64_t)(kv.second * factor);
+    for (auto& kv : g_shapes)
+        for (auto* c : {&kv.second.capacity[0], &kv.second.capacity[1], &kv.second.overflow_capacity})
+            if (*c) *c = (int64_t)(**c * factor);
 }
 
 // (tests) overwrite the longest-list guesses of every shape seen so far
 void debug_set_longest_list_hints(int64_t value) {
     std::lock_guard<std::mutex> lock(g_mutex);
-    for (auto& kv : g_longest_list) kv.second = value;
+    for (auto& kv : g_shapes)
+        if (kv.second.longest_list) kv.second.longest_list = value;
 }
 
-void set_segments(int mode) { g_segments = mode; }
+void set_segments(int mode) { g_policy.segments = mode; }
 void set_depth_cut(int mode, int64_t min_mean_list) {
-    g_depth_cut = mode;
-    if (min_mean_list > 0) g_cut_min_mean_list = min_mean_list;
+    g_policy.depth_cut = mode;
+    if (min_mean_list > 0) g_policy.cut_min_mean_list = min_mean_list;
 }
 void set_band_compact(bool on) { g_band_compact = on; }
 void set_band_fused(bool on) { g_band_fused = on; }
 void set_touch_masks(bool on) { g_touch_masks = on; }
 
 void set_modes(bool sort_prefix, bool early_render) {
-    g_sort_prefix = sort_prefix;
-    g_early_render = early_render;
+    g_policy.sort_prefix = sort_prefix;
+    g_policy.early_render = early_render;
 }
 
 }  // namespace

@@ -481,6 +481,59 @@ def test_native_frame_guesses_the_longest_list(case, N):
         assert c["long_list_misses"] >= 3, c   # guesses 100, 2000, 100 of a frame with a list beyond 4096
 
 
+def test_native_frame_kinds_share_one_record_per_shape():
+    """The native orchestration keeps ONE record of guesses per frame shape (csrc/frame_policy.h: ShapeState): row-
+    restricted frames, whole complete-list frames and whole depth-cut frames of a scene in alternation.  The second
+    frame of every (shape, mode) must run on guessed capacities and none may miss -- a cut frame's capacity is its KEPT
+    count, far below the complete count the uncut frame of the same shape needs, so the two must not overwrite each
+    other -- and every result stays that of the Python orchestration, which guesses nothing."""
+    nat = fused.native()
+    if nat is None:
+        pytest.skip("native frame module not built")
+    N, W, H = 90_000, 256, 192   # the "medium" scene of test_native_frame_guesses_the_longest_list
+    g, cam, T = make_scene(N, W, H, 0, seed=9, device=DEV)
+    g.opacity.fill_(-5.0)
+    bg = torch.full((3,), 0.25, device=DEV)
+    gi = make_grad_image(W, H, seed=3, device=DEV)
+    for k in PARAMS:
+        if getattr(g, k) is not None:
+            getattr(g, k).requires_grad_(True)
+
+    def frame(native, cut, rows):
+        prev = fused.NATIVE, fused.DEPTH_CUT
+        fused.NATIVE, fused.DEPTH_CUT = native, cut
+        try:
+            for k in PARAMS:
+                if getattr(g, k) is not None:
+                    getattr(g, k).grad = None
+            img, mask, uv = fused.rasterize(g, T, cam, 0.3, 500.0, 100, 3.0, True, bg, tile_rows=rows)
+            img.backward(gi)
+            return img.detach().clone(), {k: getattr(g, k).grad.clone() for k in PARAMS if getattr(g, k) is not None}
+        finally:
+            fused.NATIVE, fused.DEPTH_CUT = prev
+
+    refs = {rows: frame(False, False, rows) for rows in ((3, 9), None)}
+    fused.reset_counters()
+    seen, log = set(), []
+    for cut, rows in ((False, (3, 9)), (False, (3, 9)), (True, None), (False, None), (True, None), (False, None)):
+        before = fused.counters()
+        img, grads = frame(True, cut, rows)
+        c = fused.counters()
+        d = {k: c[k] - before[k] for k in ("frames", "speculative_frames", "capacity_misses", "depth_cut_frames")}
+        log.append(d)
+        assert d["frames"] == 1 and d["depth_cut_frames"] == int(cut), (cut, rows, d)
+        if (cut, rows) in seen:
+            assert d["speculative_frames"] == 1, (cut, rows, d)
+        seen.add((cut, rows))
+        assert torch.equal(img, refs[rows][0]), (cut, rows)
+        for k in grads:
+            assert scaled_err(grads[k], refs[rows][1][k]) < 1e-5, (cut, rows, k)
+    c = fused.counters()
+    report("native_frame_shared_records", S_min=c["S_min"], S_max=c["S_max"],
+           speculative=[d["speculative_frames"] for d in log], misses=[d["capacity_misses"] for d in log])
+    assert c["frames"] == 6 and c["capacity_misses"] == 0 and c["depth_cut_frames"] == 2, c
+
+
 def test_fused_rasterize_rejects_bad_inputs():
     """the fused path hands raw pointers to the C ABI: wrong dtype / device / shape must raise like the
     reference's TORCH_CHECKs (src/checks.cuh:5-14) instead of reading garbage"""
