@@ -43,7 +43,7 @@ EXPORTS = [
     "gs_precompute_rgb_from_sh", "gs_precompute_rgb_from_sh_backward",
     "gs_tile_workspace_ints", "gs_tile_count", "gs_tile_emit_sort", "gs_tile_emit_sort_bounded", "gs_tile_sort_flagged",
     "gs_preprocess_workspace_ints", "gs_preprocess_forward", "gs_preprocess_backward",
-    "gs_preprocess_backward_adam",
+    "gs_preprocess_backward_adam", "gs_pose_workspace_floats", "gs_pose_backward",
     "gs_pack_splats", "gs_render_tiles", "gs_render_tiles_packed", "gs_render_tiles_prefix", "gs_render_tiles_prefix_phased",
     "gs_render_tiles_backward",
     "gs_render_tiles_backward_packed", "gs_render_tiles_backward_slab", "gs_render_backward_prologue",
@@ -81,6 +81,7 @@ def lib():
         _lib = ctypes.CDLL(LIB_PATH)
         _lib.gs_last_error.restype = ctypes.c_char_p
         _lib.gs_preprocess_workspace_ints.restype = ctypes.c_size_t
+        _lib.gs_pose_workspace_floats.restype = ctypes.c_size_t
         _lib.gs_tile_workspace_ints.restype = ctypes.c_size_t
         _lib.gs_halo_workspace_ints.restype = ctypes.c_size_t
         _lib.gs_band_frontend_workspace_ints.restype = ctypes.c_size_t

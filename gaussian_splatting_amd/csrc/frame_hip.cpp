@@ -68,6 +68,14 @@ struct Counters {
 } g_counters;
 std::vector<Tensor> g_flag_log;
 Tensor g_last_flags;   // tile_flags of the latest prefix-mode render (tests / tools)
+// tests / tools (fused.keep_last_slab): a reference to the [V, 9] slab of the latest per-Gaussian backward
+bool g_keep_slab = false;
+Tensor g_last_slab;
+// (also bound for the Python orchestration: with this module loaded there is ONE slot, whichever path ran last)
+void note_slab(Tensor slab) {
+    std::lock_guard<std::mutex> lock(g_mutex);
+    if (g_keep_slab) g_last_slab = std::move(slab);
+}
 Policy g_policy;
 bool g_band_compact = true;   // multi-GPU: band-compact per-Gaussian stage (OwnerPreprocess)
 // band-compact frames: the fused frontend (gs_band_frontend, ABI 8) and the gathering per-Gaussian backward; false =
@@ -553,6 +561,8 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
         ctx->saved_data["n_sh"] = (int64_t)n_sh;
         ctx->saved_data["V"] = V;
         if (adam_plan) ctx->saved_data["adam_plan"] = c10::IValue(adam_plan);
+        // (recorded here: the node's edge indices skip an absent sh, its backward cannot ask by argument position)
+        ctx->saved_data["pose_grad"] = camera_T_world.requires_grad();
         ctx->set_materialize_grads(false);
         ctx->mark_non_differentiable(variable_list(o.begin() + PRE_PACKED, o.end()));
         return o;
@@ -595,6 +605,21 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
         }
         const int64_t n = N, extra = 3 * (int64_t)(n_sh - 1);
         variable_list out(18);
+        if (g_keep_slab) note_slab(slab.narrow(0, 0, V));
+        // camera_T_world's gradient (gs_pose_backward), before the fused optimizer step, which overwrites the quaternion
+        // and scale the pose terms read
+        if (ctx->saved_data["pose_grad"].toBool()) {
+            void* stream = cur_stream();
+            // (two allocations: the gradient outlives the backward, the workspace must not live as long)
+            Tensor grad_pose = torch::empty({4, 4}, xyz.options());
+            Tensor ws = torch::empty({(int64_t)gs_pose_workspace_floats(N)}, xyz.options());
+            timed("gs_pose_backward", stream, [&] {
+                return gs_pose_backward(xyz.data_ptr(), quaternion.data_ptr(), scale.data_ptr(), camera_T_world.data_ptr(),
+                                        K.data_ptr(), rank.data_ptr<int32_t>(), slab.data_ptr(), 0, N,
+                                        ws.data_ptr(), grad_pose.data_ptr(), stream);
+            });
+            out[6] = grad_pose;
+        }
         if (ctx->saved_data.count("adam_plan")) {
             // the fused optimizer step: quaternion, scale, opacity, rgb and sh are stepped by the kernel, in place;
             // only xyz gets a gradient
@@ -1360,6 +1385,19 @@ void reset_counters() {
     g_flag_log.clear();
 }
 
+// every call drops what was kept
+void keep_last_slab(bool on) {
+    std::lock_guard<std::mutex> lock(g_mutex);
+    g_keep_slab = on;
+    g_last_slab = Tensor();
+}
+c10::optional<Tensor> last_slab() {
+    std::lock_guard<std::mutex> lock(g_mutex);
+    c10::optional<Tensor> out;
+    if (g_last_slab.defined()) out = g_last_slab;
+    return out;
+}
+
 c10::optional<Tensor> last_tile_flags(bool clear) {
     std::lock_guard<std::mutex> lock(g_mutex);
     c10::optional<Tensor> out;
@@ -1493,6 +1531,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("set_touch_masks", &set_touch_masks, py::arg("on"));
     if (const char* e = std::getenv("GSPLAT_TOUCH_MASKS")) g_touch_masks = std::atoi(e) != 0;   // (A/B runs of bench.py)
     m.def("last_tile_flags", &last_tile_flags, py::arg("clear") = false);
+    m.def("keep_last_slab", &keep_last_slab, py::arg("on"));
+    m.def("last_slab", &last_slab);
+    m.def("note_slab", &note_slab, py::arg("slab"));
     m.def("enable_timing", &enable_timing, py::arg("on"), py::arg("only") = std::string());
     m.def("reserve_events", &reserve_events);
     m.def("collect_timing", &collect_timing);

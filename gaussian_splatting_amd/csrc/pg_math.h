@@ -62,16 +62,11 @@ __device__ inline void conic_of(const T* J6, const T* W, const T* S9, T* conic3)
 }
 
 
-// projection_backward.cu:385-471
+// The gradient of (J W)^T [3,2] in the conic's backward: S (JW)^T G + S^T (JW)^T G
+// (projection_backward.cu:430-455).  One definition for conic_bwd_of and conic_bwd_pose_of.
 template <typename T>
-__device__ inline void conic_bwd_of(const T* J6, const T* W, const T* S9, const T* gc3, T* gS9,
-                                    T* gJ6) {
-    T JW[6], JWt[6], G2[4], A[6], SJ[6], L[6], St[9], StJ[6], Rr[6], gJWt[6], gJt[6];
-    matmul<T, 2, 3, 3>(J6, W, JW);
-    transp<T, 2, 3>(JW, JWt);
-    G2[0] = gc3[0]; G2[1] = gc3[1]; G2[2] = gc3[1]; G2[3] = gc3[2];
-    matmul<T, 3, 2, 2>(JWt, G2, A);
-    matmul<T, 3, 2, 3>(A, JW, gS9);
+__device__ inline void conic_bwd_gJWt_of(const T* JWt, const T* G2, const T* S9, T* gJWt) {
+    T SJ[6], L[6], St[9], StJ[6], Rr[6];
     matmul<T, 3, 3, 2>(S9, JWt, SJ);
     matmul<T, 3, 2, 2>(SJ, G2, L);   // G2 is symmetric: its transpose is itself
     transp<T, 3, 3>(S9, St);
@@ -79,8 +74,57 @@ __device__ inline void conic_bwd_of(const T* J6, const T* W, const T* S9, const 
     matmul<T, 3, 2, 2>(StJ, G2, Rr);
 #pragma unroll
     for (int k = 0; k < 6; k++) gJWt[k] = L[k] + Rr[k];
+}
+
+// projection_backward.cu:385-471
+template <typename T>
+__device__ inline void conic_bwd_of(const T* J6, const T* W, const T* S9, const T* gc3, T* gS9,
+                                    T* gJ6) {
+    T JW[6], JWt[6], G2[4], A[6], gJWt[6], gJt[6];
+    matmul<T, 2, 3, 3>(J6, W, JW);
+    transp<T, 2, 3>(JW, JWt);
+    G2[0] = gc3[0]; G2[1] = gc3[1]; G2[2] = gc3[1]; G2[3] = gc3[2];
+    matmul<T, 3, 2, 2>(JWt, G2, A);
+    matmul<T, 3, 2, 3>(A, JW, gS9);
+    conic_bwd_gJWt_of(JWt, G2, S9, gJWt);
     matmul<T, 3, 3, 2>(W, gJWt, gJt);
     transp<T, 3, 2>(gJt, gJ6);
+}
+
+// The conic's backward towards the camera pose: gJ6 as conic_bwd_of gives it, and gW9 [3,3], the gradient of the
+// rotation block W through the product J W itself: J^T (gJWt)^T = 2 J^T G (J W) S for a symmetric S.  (The
+// reference's ComputeConic returns no gradient for camera_T_world; this is the term it leaves out.)
+template <typename T>
+__device__ inline void conic_bwd_pose_of(const T* J6, const T* W, const T* S9, const T* gc3, T* gJ6,
+                                         T* gW9) {
+    T JW[6], JWt[6], G2[4], gJWt[6], gJt[6], Jt[6], gJW[6];
+    matmul<T, 2, 3, 3>(J6, W, JW);
+    transp<T, 2, 3>(JW, JWt);
+    G2[0] = gc3[0]; G2[1] = gc3[1]; G2[2] = gc3[1]; G2[3] = gc3[2];
+    conic_bwd_gJWt_of(JWt, G2, S9, gJWt);
+    matmul<T, 3, 3, 2>(W, gJWt, gJt);
+    transp<T, 3, 2>(gJt, gJ6);
+    transp<T, 2, 3>(J6, Jt);
+    transp<T, 3, 2>(gJWt, gJW);
+    matmul<T, 3, 2, 3>(Jt, gJW, gW9);
+}
+
+// J and uv -> camera-frame xyz (projection_backward.cu:93-120 and :9-36; the uv part is nothing when z <= 0, Q10).
+// c: the camera-frame position, gJ6: the gradient of the projection Jacobian, g_uv: the gradient of uv (read only
+// when z > 0).
+template <typename T>
+__device__ inline void cam_grad_of(const T* c, T fx, T fy, const T* gJ6, const T* g_uv, T* gcam) {
+    const T z = c[2], z2 = c[2] * c[2], z3 = c[2] * c[2] * c[2];
+    gcam[0] = gJ6[2] * -fx / z2;
+    gcam[1] = gJ6[5] * -fy / z2;
+    gcam[2] = gJ6[0] * -fx / z2 + gJ6[4] * -fy / z2 + gJ6[2] * 2 * c[0] * fx / z3 +
+              gJ6[5] * 2 * c[1] * fy / z3;
+    if (z > T(0)) {
+        const T gu = g_uv[0], gv = g_uv[1];
+        gcam[0] += gu * (fx / z);
+        gcam[1] += gv * (fy / z);
+        gcam[2] += gu * (-fx * c[0] / z2) + gv * (-fy * c[1] / z2);
+    }
 }
 
 

@@ -1158,6 +1158,95 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))
     o.rgb[g * 3 + 0] = gc[0]; o.rgb[g * 3 + 1] = gc[1]; o.rgb[g * 3 + 2] = gc[2];
 }
 
+// ---- the gradient of camera_T_world (gs_pose_backward) ----
+// The rotation block A and the translation t of camera_T_world as twelve free numbers: per visible Gaussian, with
+// c = A p + t, the conic reaches A directly through J A (conic_bwd_pose_of's gW9 = 2 J^T G (J A) Sigma) and A, t
+// through c: g_cam p^T and g_cam, g_cam being k_preprocess_bwd's gcam[] (cam_grad_of restates those expressions; that
+// kernel keeps its own text because its register allocation must not move).  The SH view
+// direction carries no gradient (as for xyz), so the slab's colour and opacity columns are not read.
+// A kernel of its own: k_preprocess_bwd has no registers left for twelve accumulators, and only frames whose pose
+// requires a gradient pay for this one (80 B read per visible Gaussian).
+// The twelve sums are reduced without atomics, in an order that depends on (N, grid) only: per thread over its
+// grid-stride Gaussians, across the wave with cross-lane moves, across the workgroup's waves through LDS, one row of
+// twelve per workgroup to the workspace; k_pose_sum, a second launch of one workgroup, adds the rows in fp64.
+constexpr int POSE_MAX_BLOCKS = 2048;   // 8 workgroups per CU of a 256-CU device: beyond that a thread takes several Gaussians
+constexpr int POSE_SUM_BLOCK = 1024;
+
+inline int pose_blocks(int N) {
+    const int nb = N > 0 ? div_up(N, PP_BLOCK) : 0;
+    return nb < POSE_MAX_BLOCKS ? nb : POSE_MAX_BLOCKS;
+}
+
+__global__ __launch_bounds__(PP_BLOCK) void k_pose_bwd(
+    const float* __restrict__ xyz, const float* __restrict__ quat, const float* __restrict__ scale,
+    const float* __restrict__ M, const float* __restrict__ K, const int* __restrict__ rank,
+    const float* __restrict__ g_slab, int v_base, int N, float* __restrict__ rows) {
+    __shared__ float s_part[PP_BLOCK / GS_WAVE][12];
+    float acc[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) acc[k] = 0.0f;
+    float W[9];
+    load_rotation(M, W);
+    const float fx = K[0], fy = K[4];
+    for (int g = blockIdx.x * PP_BLOCK + threadIdx.x; g < N; g += gridDim.x * PP_BLOCK) {
+        const int v = rank[g];
+        if (v < 0) continue;
+        const float* gsl = g_slab + (size_t)(v - v_base) * 9;
+        const float p[3] = {xyz[g * 3 + 0], xyz[g * 3 + 1], xyz[g * 3 + 2]};
+        const float q4[4] = {quat[g * 4 + 0], quat[g * 4 + 1], quat[g * 4 + 2], quat[g * 4 + 3]};
+        const float s3[3] = {scale[g * 3 + 0], scale[g * 3 + 1], scale[g * 3 + 2]};
+        float c[3], S9[9], J6[6], gJ6[6], gW9[9], gcam[3];
+        to_camera(M, p[0], p[1], p[2], c);
+        sigma_world_of(q4, s3, S9);
+        const float z = c[2], z2 = c[2] * c[2];
+        J6[0] = fx / z; J6[1] = 0; J6[2] = -fx * c[0] / z2;
+        J6[3] = 0; J6[4] = fy / z; J6[5] = -fy * c[1] / z2;
+        const float gc3[3] = {gsl[6], gsl[7], gsl[8]};
+        conic_bwd_pose_of(J6, W, S9, gc3, gJ6, gW9);
+        cam_grad_of(c, fx, fy, gJ6, gsl + 4, gcam);
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+#pragma unroll
+            for (int j = 0; j < 3; j++) acc[4 * i + j] += gW9[3 * i + j] + gcam[i] * p[j];
+            acc[4 * i + 3] += gcam[i];
+        }
+    }
+    // wave: a butterfly of cross-lane moves, every lane ends with the wave's sum
+#pragma unroll
+    for (int k = 0; k < 12; k++)
+#pragma unroll
+        for (int d = 1; d < GS_WAVE; d <<= 1) acc[k] += __shfl_xor(acc[k], d);
+    if ((threadIdx.x & (GS_WAVE - 1)) == 0)
+#pragma unroll
+        for (int k = 0; k < 12; k++) s_part[threadIdx.x / GS_WAVE][k] = acc[k];
+    __syncthreads();
+    static_assert(PP_BLOCK / GS_WAVE == 4, "the workgroup sum below names its four waves");
+    if (threadIdx.x < 12)
+        rows[blockIdx.x * 12 + threadIdx.x] = (s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) +
+                                              (s_part[2][threadIdx.x] + s_part[3][threadIdx.x]);
+}
+
+// out[16] = camera_T_world's gradient, row-major: the n_rows workspace rows added in fp64 in a fixed order (lane
+// r of 64 takes rows r, r + 64, ...; the 64 partial sums are then added in ascending order), the last row 0.
+__global__ __launch_bounds__(POSE_SUM_BLOCK) void k_pose_sum(const float* __restrict__ rows, int n_rows,
+                                                             float* __restrict__ out) {
+    __shared__ double s_sum[POSE_SUM_BLOCK / 16][12];
+    const int k = threadIdx.x & 15, r0 = threadIdx.x >> 4;
+    if (k < 12) {
+        double sum = 0.0;
+        for (int r = r0; r < n_rows; r += POSE_SUM_BLOCK / 16) sum += (double)rows[(size_t)r * 12 + k];
+        s_sum[r0][k] = sum;
+    }
+    __syncthreads();
+    if (threadIdx.x < 12) {
+        double sum = 0.0;
+        for (int r = 0; r < POSE_SUM_BLOCK / 16; r++) sum += s_sum[r][threadIdx.x];
+        out[threadIdx.x] = (float)sum;
+    } else if (threadIdx.x < 16) {
+        out[threadIdx.x] = 0.0f;
+    }
+}
+
 }  // namespace gs
 
 using namespace gs;
@@ -1501,6 +1590,26 @@ int gs_preprocess_backward(const void* xyz, const void* quaternion, const void* 
                           (const float*)camera_center, rank, (const float*)opacity_act,
                           (const float*)grad_slab, v_base, N, o)));
     return check_launch("preprocess_backward");
+}
+
+size_t gs_pose_workspace_floats(int N) { return (size_t)pose_blocks(N) * 12 + 4; }
+
+int gs_pose_backward(const void* xyz, const void* quaternion, const void* scale, const void* camera_T_world,
+                     const void* K, const int32_t* rank, const void* grad_slab, int v_base, int N, void* workspace,
+                     void* grad_camera_T_world, void* stream) {
+    GS_REQUIRE(grad_camera_T_world != nullptr, "pose_backward: grad_camera_T_world is NULL");
+    GS_REQUIRE(N <= 0 || (workspace != nullptr && xyz != nullptr && quaternion != nullptr && scale != nullptr &&
+                          rank != nullptr && grad_slab != nullptr && camera_T_world != nullptr && K != nullptr),
+               "pose_backward: an input or the workspace is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    const int nb = pose_blocks(N);
+    if (nb > 0)
+        k_pose_bwd<<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)quaternion, (const float*)scale,
+                                           (const float*)camera_T_world, (const float*)K, rank, (const float*)grad_slab,
+                                           v_base, N, (float*)workspace);
+    // (N == 0: no rows, the sum writes the zeros)
+    k_pose_sum<<<1, POSE_SUM_BLOCK, 0, s>>>((const float*)workspace, nb, (float*)grad_camera_T_world);
+    return check_launch("pose_backward");
 }
 
 }  // extern "C"

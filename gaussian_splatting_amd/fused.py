@@ -103,6 +103,41 @@ def last_flags(clear=False):
     return out
 
 
+# fused.keep_last_slab: ONE slot for the [V, 9] slab of the latest per-Gaussian backward, whichever orchestration ran
+# it -- inside the native module when that is loaded (its backward runs without the interpreter), else _last_slab
+_keep_slab = False
+_last_slab = None
+_slab_slot = None   # the native module holding the slot, fixed by keep_last_slab(True)
+
+
+def keep_last_slab(on):
+    """Tests and tools: while on, both orchestrations keep a reference (no copy) to the render-gradient slab of their
+    latest per-Gaussian backward.  The render backward's summation order differs from run to run, so a gradient
+    derived from the slab (camera_T_world's) can only be checked against the slab it was computed from.  Every call
+    drops what was kept."""
+    global _keep_slab, _last_slab, _slab_slot
+    _keep_slab, _last_slab = bool(on), None
+    if _native_mod is not None:
+        _native_mod.keep_last_slab(False)
+    _slab_slot = native() if on else None
+    if _slab_slot is not None:
+        _slab_slot.keep_last_slab(True)
+
+
+def last_slab():
+    """the [V, 9] slab (rgb 3 | opacity 1 | uv 2 | conic 3) of the latest per-Gaussian backward since
+    keep_last_slab(True), whichever orchestration ran it; None if there was none"""
+    return _slab_slot.last_slab() if _slab_slot is not None else _last_slab
+
+
+def _note_slab(slab, V):
+    global _last_slab
+    if _slab_slot is not None:
+        _slab_slot.note_slab(slab[:V])
+    else:
+        _last_slab = slab[:V]
+
+
 _capacity_hint = {}   # (device, N, tiles, band) -> instance capacity guessed from the previous frame
 _pinned = {}
 
@@ -406,6 +441,19 @@ def preprocess_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_ba
     return grad_xyz, grad_q, grad_scale, grad_opacity, grad_rgb, grad_sh
 
 
+def pose_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_base=0):
+    """The gradient of camera_T_world [4, 4] from the render-gradient slab of frame record f (gs_pose_backward): the
+    rotation block and the translation as twelve free numbers, the last row 0.  Reads the quaternion and scale the
+    forward saw: with the fused optimizer step it goes BEFORE preprocess_backward_adam on the same stream."""
+    n = f.N
+    # (two allocations: the gradient outlives the backward, the workspace must not live as long)
+    grad = torch.empty(4, 4, dtype=torch.float32, device=xyz.device)
+    ws = torch.empty(_hip.lib().gs_pose_workspace_floats(n), dtype=torch.float32, device=xyz.device)
+    _hip.call("gs_pose_backward", _p(xyz), _p(quaternion), _p(scale), _p(camera_T_world), _p(K), _p(f.rank), _p(slab),
+              int(v_base), n, _p(ws), _p(grad), _stream())
+    return grad
+
+
 def preprocess_backward_adam(xyz, camera_T_world, K, f, slab, plan):
     """preprocess_backward with the optimizer step folded in (gs_preprocess_backward_adam): -> grad_xyz only;
     quaternion, scale, opacity, rgb and sh are stepped in place with their moments, no gradient is written for them.
@@ -593,10 +641,12 @@ class _Preprocess(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, width, height, near_thresh,
                 far_thresh, cull_mask_padding, mh_dist, tile_rows, sort_prefix=0, background_rgb=None, cut_box=None,
-                adam_plan=None):
+                adam_plan=None, pose_grad=False):
         # cut_box: a list; when the frame takes the depth cut its record (what _Render's two passes need) is left in it
         # adam_plan: train_ops.FusedRasterAdam's plan -> the backward steps quaternion, scale, opacity, rgb and sh
         # itself (preprocess_backward_adam) and returns a gradient for xyz only
+        # pose_grad: the frame gives camera_T_world its gradient when it requires one (pose_backward); False keeps
+        # the pose a constant (multi-GPU frames: the sum would need an all-reduce; per-pixel SH: its rays depend on it)
         ntx = (width + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
         nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
         row0, row1 = tile_rows if tile_rows is not None else (0, nty)
@@ -631,6 +681,7 @@ class _Preprocess(torch.autograd.Function):
         ctx.save_for_backward(xyz, quaternion, scale, camera_T_world, K)
         ctx.set_materialize_grads(False)   # no zero tensors for the auxiliary outputs in backward
         ctx.adam_plan = adam_plan
+        ctx.pose_grad = pose_grad
         ctx.f = SimpleNamespace(N=f.N, V=V, n_sh=f.n_sh, center=f.center, rank=f.rank, opacity_act=f.opacity_act)
         uv_v, conic_v, opa_v, rgb_v = f.uv[:V], f.conic[:V], f.opacity_act[:V], f.rgb_render[:V]
         aux = (f.packed, f.xyz_cam[:V], f.culling_mask, f.ranges, f.sorted_g, f.vis_idx[:V], f.keys) + tuple(pre)
@@ -641,10 +692,17 @@ class _Preprocess(torch.autograd.Function):
     def backward(ctx, g_uv, g_conic, g_opa, g_rgb, *unused):
         xyz, quaternion, scale, camera_T_world, K = ctx.saved_tensors
         slab = _as_slab(g_uv, g_conic, g_opa, g_rgb, ctx.f.V, xyz.device)
+        if _keep_slab:
+            _note_slab(slab, ctx.f.V)
+        # (before the fused optimizer step, which overwrites the quaternion and scale the pose terms read)
+        g_pose = None
+        if ctx.pose_grad and ctx.needs_input_grad[6]:
+            g_pose = pose_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab)
         if ctx.adam_plan is not None:
-            return (preprocess_backward_adam(xyz, camera_T_world, K, ctx.f, slab, ctx.adam_plan),) + (None,) * 18
-        grads = preprocess_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab)
-        return grads + (None,) * 13
+            grads = (preprocess_backward_adam(xyz, camera_T_world, K, ctx.f, slab, ctx.adam_plan),) + (None,) * 5
+        else:
+            grads = preprocess_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab)
+        return grads + (g_pose,) + (None,) * 13
 
 
 class _Render(torch.autograd.Function):
@@ -856,7 +914,7 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
         g.xyz.contiguous(), g.quaternion.contiguous(), g.scale.contiguous(), g.opacity.contiguous(),
         g.rgb.contiguous(), sh, camera_T_world.contiguous(), camera.K.contiguous(), int(camera.width),
         int(camera.height), near_thresh, far_thresh, cull_mask_padding, mh_dist, tile_rows, sort_prefix,
-        background_rgb.contiguous(), cut_box, adam_plan)
+        background_rgb.contiguous(), cut_box, adam_plan, not (grad_sync or slab_sync))
     uv, conic, opacity, rgb, packed, xyz_cam, culling_mask, ranges, sorted_g, vis_idx, keys = out[:11]
     if frame_hook is not None:   # multi-GPU cost-balanced bands: the band's tile ranges
         frame_hook(dict(ranges=ranges, ntx=(int(camera.width) + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX))

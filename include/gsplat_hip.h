@@ -280,6 +280,25 @@ int gs_preprocess_backward_adam(const void* xyz, int n_sh, const void* camera_T_
                                 void* sh, void* sh_exp_avg, void* sh_exp_avg_sq, double sh_lr, int64_t sh_step,
                                 double beta1, double beta2, double eps, void* stream);
 
+/* The gradient of camera_T_world from the same render-gradient slab (ABI 10; the reference's pipeline gets the part of
+ * it that flows through the positions from autograd, rasterize.py:29, and none through ComputeConic).  The rotation
+ * block A and the translation t are twelve free numbers (no orthonormality assumed).  Per visible Gaussian, with
+ * c = A p + t, G = [[g_c0, g_c1], [g_c1, g_c2]] and g_cam the camera-frame position gradient gs_preprocess_backward
+ * forms:  dL/dA += 2 J^T G (J A) Sigma + g_cam p^T,  dL/dt += g_cam.  The SH view direction carries no gradient
+ * (as for xyz), so the slab's colour and opacity columns are not read.
+ *   inputs    xyz, quaternion, scale, camera_T_world, K, rank, grad_slab as gs_preprocess_backward takes them;
+ *             workspace float[gs_pose_workspace_floats(N)].  A caller that wants the sum over the Gaussians
+ *             [i0, i1) only passes xyz, quaternion, scale and rank advanced to row i0, N = i1 - i0 and, if its slab
+ *             starts at another visible index than 0, that index as v_base.
+ *   output    grad_camera_T_world[4,4] row-major, written (not accumulated), last row 0; all zeros for N == 0 or
+ *             when no Gaussian is visible
+ * Two launches, no atomics: the sums are added in an order that depends on N only, so equal inputs give equal
+ * bits.  Must be enqueued BEFORE gs_preprocess_backward_adam, which overwrites the quaternion and scale it reads. */
+size_t gs_pose_workspace_floats(int N);
+int gs_pose_backward(const void* xyz, const void* quaternion, const void* scale, const void* camera_T_world,
+                     const void* K, const int32_t* rank, const void* grad_slab, int v_base, int N, void* workspace,
+                     void* grad_camera_T_world, void* stream);
+
 /* ---- tile renderer ---------------------------------------------------------------------------- */
 /* Packs what the render kernels read per splat into one 48-byte (fp32) record per visible Gaussian:
  *   packed[V][12] = (u, v, r2, opacity | a, b, c, det | 1/det, SH_0*col0, SH_0*col1, SH_0*col2)
