@@ -23,14 +23,18 @@
 // ordered; the forward reads no further, raises tile_flags[t] if a pixel is still unsaturated there,
 // and k_render_fwd_flagged renders such tiles again after their full sort -- results are exact.
 //
-// Backward starts at the tile's largest num_splats_per_pixel instead of the end of the list and skips the
-// reduction for waves none of whose lanes the splat reaches.  The fused renderer's kernel (fp32, one colour
-// coefficient: SLOTS) sums the nine per-splat values over the wave with a transposing DPP / permlane-swap
-// reduction into a wave-private LDS slot (plain store, no LDS atomics), the flush adds the four waves' slots
-// and issues the global atomics nine lanes per 36-byte row of the [V, 9] slab; the other instantiations
-// (per-pixel SH, fp64) keep DPP row sums + LDS float atomics and one global atomic per value per
-// (splat, tile) -- the reference issues eight (one per warp), unconditionally.  The fused backward starts its
-// tiles longest-first from durations the forward measured (k_bwd_prologue: tile_order_body).
+// Backward: two kernels.  Both start at the tile's largest num_splats_per_pixel instead of the end of the list and
+// skip the reduction for waves none of whose lanes the splat reaches.
+//   k_render_bwd<float, N_SH>, every fp32 backward (the fused renderer's is <float, 1>): sums nine per-splat values
+//   over the wave with a transposing DPP / permlane-swap reduction into a wave-private LDS slot (plain store, no LDS
+//   atomics); the flush adds the four waves' slots and issues the global atomics nine lanes per 36-byte row (of the
+//   [V, 9] slab, or of the separate gradient arrays).  With per-pixel SH (N_SH > 1) the colour-coefficient gradients
+//   leave the slots: a matrix-core contraction over the wave's 64 pixels per batch of 16 contributing splats (SHMM).
+//   It alone carries the fused frame's depth segments, depth-cut overflow lists, handed-over touch masks and the
+//   longest-first tile order (durations the forward measured; k_bwd_prologue: tile_order_body).
+//   k_render_bwd_ref<N_SH>, fp64 (gradcheck and the fp64 parity tests): one shared LDS row of 3 N_SH + 6 sums per
+//   staged splat, shuffle wave sums + one LDS atomic per value per visit, one global atomic per value per
+//   (splat, tile) -- the reference issues eight (one per warp), unconditionally.
 //
 // Numerics.  The fp32 forward is bit-identical to the CPU restatement: same operation order and
 // operand precisions as render.cu (including its double-literal promotions), the IEEE quotient (formed
@@ -126,9 +130,6 @@ __device__ unsigned long long g_timeline[2 * GS_TIMELINE_CAP * GS_TIMELINE_W];
 #define GS_HALF_CHUNK(i)
 #endif
 
-#ifndef GS_BWD_GROUP
-#define GS_BWD_GROUP 16   // lanes summed with DPP before the LDS atomic (measured: 16 -> 0.90 ms, 64 -> 1.03, 8 -> 1.52)
-#endif
 #ifndef GS_BWD_CHUNK
 // splats staged per step by the fused renderer's backward.  64: 12.5 KB of LDS and 71 VGPRs = 7 waves per
 // SIMD (128: 25 KB and 78 VGPRs = 6; 0.514 -> 0.505 ms at D, 0.155 -> 0.149 at B; with amdgpu_waves_per_eu(8)
@@ -1083,42 +1084,8 @@ template <bool CK> static void repair_attr_once() {
 // ---------------------------------------------------------------------------------------------------
 // wave reductions
 // ---------------------------------------------------------------------------------------------------
-// Sum over the 64 lanes, result valid in lane 63.  Four in-row DPP shifts (Hillis-Steele inside
-// each 16-lane row), then row_bcast:15 / row_bcast:31 carry the row sums across.
-#define GS_DPP(x, ctrl, row_mask, bound)                                                           \
-    __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (x)), (ctrl),  \
-                                                          (row_mask), 0xf, (bound)))
-__device__ inline float wave_sum(float v) {
-    v += GS_DPP(v, 0x111, 0xf, true);    // row_shr:1
-    v += GS_DPP(v, 0x112, 0xf, true);    // row_shr:2
-    v += GS_DPP(v, 0x114, 0xf, true);    // row_shr:4
-    v += GS_DPP(v, 0x118, 0xf, true);    // row_shr:8  -> lane 15 of each row = row sum
-    v += GS_DPP(v, 0x142, 0xa, false);   // row_bcast:15 into rows 1 and 3
-    v += GS_DPP(v, 0x143, 0xc, false);   // row_bcast:31 into rows 2 and 3 -> lane 63 = total
-    return v;
-}
-__device__ inline double wave_sum(double v);
-// Sum within each 16-lane row only: lanes 15, 31, 47, 63 hold the four row sums.  The backward
-// lets those four lanes issue the LDS atomic (the LDS pipe is otherwise idle there), which saves the
-// two cross-row DPP steps per value.
-__device__ inline float row_sum(float v) {
-    v += GS_DPP(v, 0x111, 0xf, true);
-    v += GS_DPP(v, 0x112, 0xf, true);
-    v += GS_DPP(v, 0x114, 0xf, true);
-#if GS_BWD_GROUP >= 16
-    v += GS_DPP(v, 0x118, 0xf, true);
-#endif
-#if GS_BWD_GROUP >= 32
-    v += GS_DPP(v, 0x142, 0xa, false);   // row_bcast:15 into rows 1 and 3: lanes 31, 63 hold half sums
-#endif
-    return v;
-}
-__device__ inline double row_sum(double v) { return wave_sum(v); }
-template <typename T> __device__ inline bool row_leader(int lane) {
-    return sizeof(T) == 4 ? (lane & (GS_BWD_GROUP - 1)) == (GS_BWD_GROUP - 1) : lane == 63;
-}
-
-__device__ inline double wave_sum(double v) {   // gradcheck-only path: plain shuffles
+// Sum over the 64 lanes, result valid in lane 63 (the fp64 reference backward: plain shuffles).
+__device__ inline double wave_sum(double v) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const double o = __shfl_up(v, d);
@@ -1127,9 +1094,6 @@ __device__ inline double wave_sum(double v) {   // gradcheck-only path: plain sh
     return v;
 }
 
-template <typename T> __device__ inline void lds_add(T* p, T v) {
-    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 template <typename T> __device__ inline void global_add(T* p, T v) { unsafeAtomicAdd(p, v); }
 
 
@@ -1223,7 +1187,7 @@ __device__ __forceinline__ void reduce9_to_slot(const float* val, bool stores, f
 // ---------------------------------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------------------------------
-// At most 7 waves per SIMD (no minimum: the per-pixel-SH and fp64 instantiations sit far below).  Squeezed into the 64
+// The fp32 kernel.  At most 7 waves per SIMD (no minimum: the per-pixel-SH instantiations sit far below).  Squeezed into the 64
 // registers of 8 waves, k_render_bwd<float, 1> reloads a coefficient of the exponential in every visit; with the 72
 // of 7 it stays resident (104 -> 103 vector instructions per visit, 0.4506 -> 0.4466 ms at D alternating on one box),
 // and the kernel never held 8 waves anyway (5-7).
@@ -1242,41 +1206,38 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
     const T* __restrict__ src_opacity, const T* __restrict__ src_conic, const SegState seg,
     const int* __restrict__ cut_flags, const int* __restrict__ full_ranges, const int* __restrict__ overflow_sorted,
     const unsigned long long* __restrict__ touch_masks) {
-    constexpr bool fast = sizeof(T) == 4;
+    static_assert(sizeof(T) == 4, "the fp32 slot kernel; fp64 goes to k_render_bwd_ref");
     constexpr int CW = ColW<N_SH>::value;
     constexpr int C = 3 * N_SH;
-    constexpr int NV = C + 6;   // rgb coeffs, opacity, u, v, conic x3
     constexpr int REF_CH = ref_chunk<T>(N_SH);
-    // SLOTS: the fp32 kernels.  Every wave owns a slot of nine sums per staged splat and writes it once
-    // (plain store after a full-wave reduction), the flush adds the slots of the waves that wrote -- no LDS
-    // atomics, no zero fill.  The fp64 instantiations (gradcheck) keep one shared accumulator row per splat.
-    // SHMM: fp32 with per-pixel SH (render_backward.cu:422-488).  The gradient of coefficient (ch, s) of a
+    // Every wave owns a slot of nine sums per staged splat and writes it once (plain store after a full-wave
+    // reduction), the flush adds the slots of the waves that wrote -- no LDS atomics, no zero fill.
+    // SHMM: per-pixel SH (render_backward.cu:422-488).  The gradient of coefficient (ch, s) of a
     // splat is sum over pixels of Y_s(p) gi_ch(p) * aw(p): a contraction over the wave's 64 pixels whose left
     // factor does not depend on the splat -- a GEMM [16 x 64] x [64 x 16 splats] per channel, done with
     // v_mfma_f32_16x16x4_f32 (exact fp32) on batches of 16 contributing splats instead of 3 * N_SH cross-lane
     // reductions per visit.  The slots then carry only the six geometric sums.
-    constexpr bool SLOTS = fast;
-    constexpr bool SHMM = fast && N_SH > 1;
+    constexpr bool SHMM = N_SH > 1;
     constexpr int SV = 9;   // width of a slot: colour 3 (unused with SHMM) | w, w du, w dv | conic terms 3
-    constexpr int RCHUNK = SLOTS ? GS_BWD_CHUNK : Chunk<T, N_SH>::value;
+    constexpr int RCHUNK = GS_BWD_CHUNK;
     constexpr int NWORD = RCHUNK / 64 > 0 ? RCHUNK / 64 : 1;
     constexpr int MB = 16;        // splats per MFMA batch (the N of 16x16x4)
     constexpr int BROW = 64 + 4;  // floats per row of the batch's aw matrix [slot][pixel] (16-byte aligned rows)
     __shared__ alignas(16) T s_geom[RCHUNK * GS_PACKED_WIDTH];
     __shared__ alignas(16) T s_col[N_SH > 1 ? RCHUNK * CW : 4];
     __shared__ int s_idx[RCHUNK];
-    __shared__ T s_acc[SLOTS ? 4 * RCHUNK * SV : RCHUNK * NV];   // SLOTS: [wave][splat][9]
+    __shared__ T s_acc[4 * RCHUNK * SV];                         // [wave][splat][9]
     __shared__ alignas(16) float s_B[SHMM ? 4 * MB * BROW : 4];  // SHMM: [wave][slot][pixel] aw of the open batch
     __shared__ int s_bidx[SHMM ? 4 * MB : 1];                     // SHMM: [wave][slot] Gaussian index of the splat
     __shared__ alignas(16) float s_gi[SHMM ? 4 * 3 * 64 : 4];    // SHMM: [wave][ch][pixel] grad_image
     __shared__ int s_max[4];
     __shared__ unsigned long long s_mask[4][NWORD];
-    __shared__ unsigned long long s_hit[SLOTS ? 4 : 1][NWORD];   // SLOTS: slots written by each wave
+    __shared__ unsigned long long s_hit[4][NWORD];               // slots written by each wave
 
     // depth segments (fused renderer, seg.rec != nullptr): work item = (tile, segment), block index =
     // segment * grid + block of the tile; segment 0 -- every pixel active, the most work -- starts first
     int seg_id = 0, blk = blockIdx.x;
-    const bool seg_on = SLOTS && seg.rec != nullptr;
+    const bool seg_on = seg.rec != nullptr;
     if (seg_on) {
         const int g0 = render_grid(nt);
         seg_id = blockIdx.x / g0;
@@ -1310,12 +1271,10 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
             const size_t p = (size_t)px.v * W + px.u;
             nsp = nsp_in[p];
             weight = fw_in[p];
-            if constexpr (SLOTS) {
-                if (seg_on) {
-                    kend = seg.kend[p - seg.pix0];
-                    oma_last = seg.oma_last[p - seg.pix0];
-                    bgw = seg.bgw[p - seg.pix0];
-                }
+            if (seg_on) {
+                kend = seg.kend[p - seg.pix0];
+                oma_last = seg.oma_last[p - seg.pix0];
+                bgw = seg.bgw[p - seg.pix0];
             }
             gi[0] = grad_image[p * 3 + 0];
             gi[1] = grad_image[p * 3 + 1];
@@ -1434,37 +1393,35 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
     // the workgroup's part of the list: [seg_lo, seg_hi) (the whole used part without segments)
     int seg_lo = 0, seg_hi = n_used;
     int reach_end = nsp;   // the lane looks at list entries k < reach_end (render_backward.cu:131)
-    if constexpr (SLOTS) {
-        if (seg_on) {
-            seg_lo = seg_id * SEG_LEN;
-            if (seg_lo >= n_used) return;
-            if (seg_id < SEG_MAX - 1) seg_hi = min(n_used, seg_lo + SEG_LEN);
-            if (kend <= seg_lo) {
-                reach_end = 0;   // the pixel's walk ended in front of this segment
-            } else if (kend > seg_hi) {
-                // the pixel's walk comes from behind: resume it with the state it has at the boundary
-                const Vec4<float>* rec = seg.rec + (size_t)(tile - seg.tile0) * SEG_MAX * RB + tid;
-                const int e_p = min((kend - 1) / SEG_LEN, SEG_MAX - 1);        // segment of its last contributor
-                const int e_tile = min((n_used - 1) / SEG_LEN, SEG_MAX - 1);   // wave-uniform bound
-                const int k_m = kend - 1;
-                const bool first_divides = (exact ? k_m : k_m % REF_CH) < nsp - 1;   // Q1 at the first contributor
-                // weight after the walk's first step, with the last contributor's own factor taken out again
-                // (it is inside P of its segment)
-                T wb = (first_divides ? weight * fast_rcp(oma_last) : weight) * oma_last;
-                T d0 = 0, d1 = 0, d2 = 0;
-                for (int s2 = e_tile; s2 > seg_id; s2--) {   // deepest first, as the walk accumulates
-                    if (s2 <= e_p) {
-                        const Vec4<float> r4 = rec[s2 * RB];
-                        wb = wb * fast_rcp(r4.x);   // the walk's weight at the near boundary of segment s2
-                        d0 += wb * r4.y; d1 += wb * r4.z; d2 += wb * r4.w;
-                    }
+    if (seg_on) {
+        seg_lo = seg_id * SEG_LEN;
+        if (seg_lo >= n_used) return;
+        if (seg_id < SEG_MAX - 1) seg_hi = min(n_used, seg_lo + SEG_LEN);
+        if (kend <= seg_lo) {
+            reach_end = 0;   // the pixel's walk ended in front of this segment
+        } else if (kend > seg_hi) {
+            // the pixel's walk comes from behind: resume it with the state it has at the boundary
+            const Vec4<float>* rec = seg.rec + (size_t)(tile - seg.tile0) * SEG_MAX * RB + tid;
+            const int e_p = min((kend - 1) / SEG_LEN, SEG_MAX - 1);        // segment of its last contributor
+            const int e_tile = min((n_used - 1) / SEG_LEN, SEG_MAX - 1);   // wave-uniform bound
+            const int k_m = kend - 1;
+            const bool first_divides = (exact ? k_m : k_m % REF_CH) < nsp - 1;   // Q1 at the first contributor
+            // weight after the walk's first step, with the last contributor's own factor taken out again
+            // (it is inside P of its segment)
+            T wb = (first_divides ? weight * fast_rcp(oma_last) : weight) * oma_last;
+            T d0 = 0, d1 = 0, d2 = 0;
+            for (int s2 = e_tile; s2 > seg_id; s2--) {   // deepest first, as the walk accumulates
+                if (s2 <= e_p) {
+                    const Vec4<float> r4 = rec[s2 * RB];
+                    wb = wb * fast_rcp(r4.x);   // the walk's weight at the near boundary of segment s2
+                    d0 += wb * r4.y; d1 += wb * r4.z; d2 += wb * r4.w;
                 }
-                weight = wb;
-                color_accum[0] = bg0 * bgw + d0;
-                color_accum[1] = bg1 * bgw + d1;
-                color_accum[2] = bg2 * bgw + d2;
-                bg_init = true;
             }
+            weight = wb;
+            color_accum[0] = bg0 * bgw + d0;
+            color_accum[1] = bg1 * bgw + d1;
+            color_accum[2] = bg2 * bgw + d2;
+            bg_init = true;
         }
     }
     const int first_chunk = seg_lo / RCHUNK;
@@ -1480,11 +1437,9 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
         const int cnt = min(RCHUNK, seg_hi - base);
         GS_STAT(1, 1);
         __syncthreads();   // previous chunk fully flushed
-        stage_chunk<T, N_SH, SLOTS ? 1 : 0>(packed, rgb, sorted, s0 + base, cnt, tid, s_geom, s_col, s_idx, src_opacity, src_conic);
-        if constexpr (!SLOTS)
-            for (int k = tid; k < cnt * NV; k += RB) s_acc[k] = 0;
+        stage_chunk<T, N_SH, 1>(packed, rgb, sorted, s0 + base, cnt, tid, s_geom, s_col, s_idx, src_opacity, src_conic);
         GS_PHASE(0);
-        if constexpr (SLOTS && RCHUNK == 64) {
+        if constexpr (RCHUNK == 64) {
             if (touch_masks != nullptr && chunk < GS_MASK_WORDS) {
                 // the forward's own masks of this word (GS_MASK_WORDS); entries beyond the used part are not staged here
                 if (tid < 4) {
@@ -1506,7 +1461,7 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
         for (int word = (cnt - 1) >> 6; word >= 0; word--) {
           unsigned long long m = s_mask[wave][word];
           m = wave_uniform(m);
-          unsigned long long hit = 0;   // SLOTS: the splats of this word whose slot the wave wrote
+          unsigned long long hit = 0;   // the splats of this word whose slot the wave wrote
           while (m) {
             const int bit = 63 - __builtin_clzll(m);
             m &= ~(1ull << bit);
@@ -1520,130 +1475,42 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
             GS_STAT(9, 1);                          // visits with a reaching lane
             GS_STAT(6, __popcll(ballot(reach)));
             GS_STAT_FLAG(st_in);
-            if constexpr (SLOTS) {
-                // ---- fp32, one colour coefficient per channel: the fused renderer's kernel -------------
-                // Per lane: aw = alpha * weight (colour gradient = aw * Y0 grad_image[ch]),
-                // w = norm_prob * grad_alpha (the opacity gradient term), and with t = k w,
-                // k = -0.5 opacity / det a per-splat constant applied in the flush:
-                //   grad_u = -2 (c du - b dv) t, grad_v = -2 (a dv - b du) t     (render_backward.cu:216-219)
-                //   grad_conic = (dv^2 - c mh, b mh - du dv, du^2 - a mh) t      (:221-229, cf = mh / det)
-                // The uv pair only needs the sums of w du and w dv (the flush forms the combinations);
-                // the conic terms are formed per pixel as the reference does -- their cancellation is
-                // benign there and would not be after the sum.  All nine are 0 for a lane that does not
-                // contribute, so the reduction needs no zero-filled value array.
-                const T* rec = s_geom + i * GS_PACKED_WIDTH;
-                const Vec4<T> g0 = *reinterpret_cast<const Vec4<T>*>(rec);       // u v r2 opacity
-                // the whole 48-byte record at once (one LDS round trip per visit instead of three dependent
-                // ones; LDS bandwidth is no longer what bounds this kernel): 0.70 -> 0.69 ms
-                const Vec4<T> g1 = *reinterpret_cast<const Vec4<T>*>(rec + 4);   // a b c det
-                const Vec4<T> g2 = *reinterpret_cast<const Vec4<T>*>(rec + 8);   // 1/det, colour
-                asm volatile("" ::"v"(g1.x), "v"(g1.y), "v"(g1.z), "v"(g1.w), "v"(g2.x), "v"(g2.y), "v"(g2.z), "v"(g2.w));
-                const T du = pu - g0.x, dv = pv - g0.y;
-                const T du2 = du * du, dv2 = dv * dv;
-                // aw, w and mh are formed by the lanes that pass the alpha test only; the others are cut out of the
-                // nine sums by `contrib` below -- no zero-filled registers in front of (and, for the ones the
-                // exponential reuses, again inside) the branches: they were 11 of the visit's ~120 vector instructions
-                T aw = unset<T>(), w = unset<T>(), mh = unset<T>(), duv = unset<T>();
-                bool contrib = false;
-                if (reach && !(du2 + dv2 > g0.z)) {   // inside the cutoff radius
-                    GS_STAT_SET(st_in);
-                    // render_backward.cu:153-165 (multiplies by 1/det; the forward divides)
-                    duv = du * dv;
-                    mh = (g1.z * du * du - g1.w * du * dv + g1.x * dv * dv) * g2.x;   // g1.w = b + b (stage_chunk)
-                    // norm_prob = 0 unless mh > 0 (render_backward.cu:158-165) -- and then alpha = 0 fails the 1/255 test:
-                    // `mh > 0` joins the test's lane mask (a scalar and), behind it norm_prob IS the exponential
-                    const T norm_prob = exp_neg_half(mh);
-                    T alpha = g0.w * norm_prob;
-                    if (alpha > Thr<T>::sat_gt()) alpha = Thr<T>::alpha_cap();   // min(0.9999, .)
-                    if ((mh > T(0)) & (alpha >= Thr<T>::alpha_min())) {
-                        contrib = true;
-                        if (!bg_init) {   // render_backward.cu:172-181
-                            const T bw = background_weight<T>(alpha, weight);
-                            if (bw > Thr<T>::bgw_gt()) {
-                                color_accum[0] += bg0 * bw;
-                                color_accum[1] += bg1 * bw;
-                                color_accum[2] += bg2 * bw;
-                            }
-                            bg_init = true;
-                        }
-                        // values only from here on (no threshold depends on them): contraction allowed
-                        {
-#pragma clang fp contract(fast)
-                            const T r1ma = fast_rcp(T(1) - alpha);
-                            if (kq < nsp - 1) weight = weight * r1ma;   // Q1 (chunk-local index) unless exact
-                            aw = alpha * weight;
-                            // grad_alpha (render_backward.cu:196-203); the record's colour is Y0 * coefficient
-                            T c0 = g2.y, c1 = g2.z, c2 = g2.w;
-                            if constexpr (SHMM) {   // colour at this pixel's view direction
-                                T col[3];
-                                sh_to_rgb_contracted<T, N_SH>(s_col + i * CW, Y, col);
-                                c0 = col[0]; c1 = col[1]; c2 = col[2];
-                            }
-                            const T ga = (c0 * weight - color_accum[0] * r1ma) * gi[0] +
-                                         (c1 * weight - color_accum[1] * r1ma) * gi[1] +
-                                         (c2 * weight - color_accum[2] * r1ma) * gi[2];
-                            color_accum[0] += c0 * aw;
-                            color_accum[1] += c1 * aw;
-                            color_accum[2] += c2 * aw;
-                            w = norm_prob * ga;
-                        }
-                    }
-                }
-                // a lane contributes iff it passed the alpha test; aw > 0 there (alpha >= 1/255, weight > 0)
-                const T awz = contrib ? aw : T(0);
-                const unsigned long long cmask = ballot(awz != T(0));
-                GS_STAT(3, ballot(st_in) != 0);
-                GS_STAT(4, cmask != 0);
-                GS_STAT(5, __popcll(cmask));
-                GS_HALF_VISIT(ballot(st_in));
-                if (cmask == 0) continue;   // every reaching lane skipped the splat
-                T val[9];
-                const T wz = contrib ? w : T(0);
-                const T awy = awz * Y[0];   // (the compiler re-formed Y0 * gi[ch] at every visit to save registers)
-                val[0] = awy * gi[0]; val[1] = awy * gi[1]; val[2] = awy * gi[2];
-                val[3] = wz; val[4] = wz * du; val[5] = wz * dv;
-                // (mh and duv of a lane that stayed outside are whatever an earlier visit left: 0 * x = 0 for every x)
-                {
-#pragma clang fp contract(fast)
-                    val[6] = mul_zero_wins((dv2 - g1.z * mh), wz);
-                    val[7] = mul_zero_wins((g1.y * mh - duv), wz);
-                    val[8] = mul_zero_wins((du2 - g1.x * mh), wz);
-                }
-                int slot_i = i * SV;   // (kept scalar: the compiler otherwise folds it into a 64-bit vector multiply-add)
-                asm volatile("" : "+s"(slot_i));
-                reduce9_to_slot(val, slot_stores, reinterpret_cast<float*>(s_acc), slot_lane_base + slot_i);
-                hit |= 1ull << bit;
-                if constexpr (SHMM) {
-                    // column nb of the batch's B: this splat's aw at the wave's 64 pixels (0 where it does not contribute)
-                    s_B[(wave * MB + nb) * BROW + lane] = awz;
-                    if (lane == 0) s_bidx[wave * MB + nb] = s_idx[i];
-                    if (++nb == MB) {
-                        mma_flush(MB);
-                        nb = 0;
-                    }
-                }
-                continue;
-            }
-            T val[NV];
-#pragma unroll
-            for (int j = 0; j < NV; j++) val[j] = 0;
+            // ---- the visit (written for one colour coefficient per channel, the fused renderer's kernel;
+            // SHMM replaces the record's colour by the pixel's and the three colour sums by the batch) ----
+            // Per lane: aw = alpha * weight (colour gradient = aw * Y0 grad_image[ch]),
+            // w = norm_prob * grad_alpha (the opacity gradient term), and with t = k w,
+            // k = -0.5 opacity / det a per-splat constant applied in the flush:
+            //   grad_u = -2 (c du - b dv) t, grad_v = -2 (a dv - b du) t     (render_backward.cu:216-219)
+            //   grad_conic = (dv^2 - c mh, b mh - du dv, du^2 - a mh) t      (:221-229, cf = mh / det)
+            // The uv pair only needs the sums of w du and w dv (the flush forms the combinations);
+            // the conic terms are formed per pixel as the reference does -- their cancellation is
+            // benign there and would not be after the sum.  All nine are 0 for a lane that does not
+            // contribute, so the reduction needs no zero-filled value array.
+            const T* rec = s_geom + i * GS_PACKED_WIDTH;
+            const Vec4<T> g0 = *reinterpret_cast<const Vec4<T>*>(rec);       // u v r2 opacity
+            // the whole 48-byte record at once (one LDS round trip per visit instead of three dependent
+            // ones; LDS bandwidth is no longer what bounds this kernel): 0.70 -> 0.69 ms
+            const Vec4<T> g1 = *reinterpret_cast<const Vec4<T>*>(rec + 4);   // a b c det
+            const Vec4<T> g2 = *reinterpret_cast<const Vec4<T>*>(rec + 8);   // 1/det, colour
+            asm volatile("" ::"v"(g1.x), "v"(g1.y), "v"(g1.z), "v"(g1.w), "v"(g2.x), "v"(g2.y), "v"(g2.z), "v"(g2.w));
+            const T du = pu - g0.x, dv = pv - g0.y;
+            const T du2 = du * du, dv2 = dv * dv;
+            // aw, w and mh are formed by the lanes that pass the alpha test only; the others are cut out of the
+            // nine sums by `contrib` below -- no zero-filled registers in front of (and, for the ones the
+            // exponential reuses, again inside) the branches: they were 11 of the visit's ~120 vector instructions
+            T aw = unset<T>(), w = unset<T>(), mh = unset<T>(), duv = unset<T>();
             bool contrib = false;
-            if (reach) {
-                const T* rec = s_geom + i * GS_PACKED_WIDTH;
-                const Vec4<T> g0 = *reinterpret_cast<const Vec4<T>*>(rec);       // u v r2 opacity
-                const Vec4<T> g1 = *reinterpret_cast<const Vec4<T>*>(rec + 4);   // a b c det
-                const T du = pu - g0.x, dv = pv - g0.y;
-                const T a = g1.x, b = g1.y, c = g1.z, rdet = rec[8], opa = g0.w;
-                T norm_prob = 0, alpha = 0, mh = 0;
-                if (!(fast && du * du + dv * dv > g0.z)) {   // inside the cutoff radius
-                    GS_STAT_SET(st_in);
-                    // render_backward.cu:153-165 (multiplies by 1/det; forward divides)
-                    mh = (c * du * du - (b + b) * du * dv + a * dv * dv) * rdet;
-                    if (mh > T(0)) norm_prob = gexp<T>(T(-0.5) * mh);
-                    alpha = opa * norm_prob;
-                    if (alpha > Thr<T>::sat_gt()) alpha = Thr<T>::alpha_cap();   // min(0.9999, .)
-                }
-                if (!fast || alpha >= Thr<T>::alpha_min()) {
+            if (reach && !(du2 + dv2 > g0.z)) {   // inside the cutoff radius
+                GS_STAT_SET(st_in);
+                // render_backward.cu:153-165 (multiplies by 1/det; the forward divides)
+                duv = du * dv;
+                mh = (g1.z * du * du - g1.w * du * dv + g1.x * dv * dv) * g2.x;   // g1.w = b + b (stage_chunk)
+                // norm_prob = 0 unless mh > 0 (render_backward.cu:158-165) -- and then alpha = 0 fails the 1/255 test:
+                // `mh > 0` joins the test's lane mask (a scalar and), behind it norm_prob IS the exponential
+                const T norm_prob = exp_neg_half(mh);
+                T alpha = g0.w * norm_prob;
+                if (alpha > Thr<T>::sat_gt()) alpha = Thr<T>::alpha_cap();   // min(0.9999, .)
+                if ((mh > T(0)) & (alpha >= Thr<T>::alpha_min())) {
                     contrib = true;
                     if (!bg_init) {   // render_backward.cu:172-181
                         const T bw = background_weight<T>(alpha, weight);
@@ -1654,64 +1521,64 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
                         }
                         bg_init = true;
                     }
-                    // From here on only gradient VALUES are formed (no threshold depends on
-                    // them): evaluated in T with the reference's formulas factored
-                    // (render_backward.cu:183-234) and contraction allowed; checked at 1e-4.
+                    // values only from here on (no threshold depends on them): contraction allowed
                     {
 #pragma clang fp contract(fast)
                         const T r1ma = fast_rcp(T(1) - alpha);
                         if (kq < nsp - 1) weight = weight * r1ma;   // Q1 (chunk-local index) unless exact
-                        T col[3];
-                        splat_colour<T, N_SH>(s_geom, s_col, i, Y, col);
-                        const T aw = alpha * weight;
-                        T grad_alpha = 0;
-#pragma unroll
-                        for (int ch = 0; ch < 3; ch++) {
-                            const T grl = aw * gi[ch];
-#pragma unroll
-                            for (int s = 0; s < N_SH; s++) val[N_SH * ch + s] = Y[s] * grl;
-                            grad_alpha += (col[ch] * weight - color_accum[ch] * r1ma) * gi[ch];
-                            color_accum[ch] += col[ch] * aw;
+                        aw = alpha * weight;
+                        // grad_alpha (render_backward.cu:196-203); the record's colour is Y0 * coefficient
+                        T c0 = g2.y, c1 = g2.z, c2 = g2.w;
+                        if constexpr (SHMM) {   // colour at this pixel's view direction
+                            T col[3];
+                            sh_to_rgb_contracted<T, N_SH>(s_col + i * CW, Y, col);
+                            c0 = col[0]; c1 = col[1]; c2 = col[2];
                         }
-                        val[C + 0] = norm_prob * grad_alpha;
-                        // d alpha / d mh^2 = -alpha_unclamped / 2; t = rdet * grad_mh
-                        const T t = T(-0.5) * norm_prob * opa * grad_alpha * rdet;
-                        const T A = c * du - b * dv;
-                        const T B = a * dv - b * du;
-                        val[C + 1] = T(-2) * A * t;           // :216-217
-                        val[C + 2] = T(-2) * B * t;           // :218-219
-                        val[C + 3] = (dv * dv - c * mh) * t;  // :221-229 with cf = mh^2 * rdet
-                        val[C + 4] = (b * mh - du * dv) * t;
-                        val[C + 5] = (du * du - a * mh) * t;
+                        const T ga = (c0 * weight - color_accum[0] * r1ma) * gi[0] +
+                                     (c1 * weight - color_accum[1] * r1ma) * gi[1] +
+                                     (c2 * weight - color_accum[2] * r1ma) * gi[2];
+                        color_accum[0] += c0 * aw;
+                        color_accum[1] += c1 * aw;
+                        color_accum[2] += c2 * aw;
+                        w = norm_prob * ga;
                     }
                 }
             }
-            const unsigned long long cmask = __ballot(contrib);
-            GS_STAT(3, __ballot(st_in) != 0);
+            // a lane contributes iff it passed the alpha test; aw > 0 there (alpha >= 1/255, weight > 0)
+            const T awz = contrib ? aw : T(0);
+            const unsigned long long cmask = ballot(awz != T(0));
+            GS_STAT(3, ballot(st_in) != 0);
             GS_STAT(4, cmask != 0);
             GS_STAT(5, __popcll(cmask));
+            GS_HALF_VISIT(ballot(st_in));
             if (cmask == 0) continue;   // every reaching lane skipped the splat
-            GS_STAT(10, __popcll(cmask) <= 4);
-            if (fast && __popcll(cmask) <= 4) {
-                // few contributors: they add their own values (<= 4 lanes per LDS atomic, the same
-                // conflict degree as the row-leader form) and the DPP reduction is skipped
-                if (contrib) {
-#pragma unroll
-                    for (int j = 0; j < NV; j++) lds_add(&s_acc[i * NV + j], val[j]);
-                }
-                continue;
-            }
+            T val[9];
+            const T wz = contrib ? w : T(0);
+            const T awy = awz * Y[0];   // (the compiler re-formed Y0 * gi[ch] at every visit to save registers)
+            val[0] = awy * gi[0]; val[1] = awy * gi[1]; val[2] = awy * gi[2];
+            val[3] = wz; val[4] = wz * du; val[5] = wz * dv;
+            // (mh and duv of a lane that stayed outside are whatever an earlier visit left: 0 * x = 0 for every x)
             {
-#pragma unroll
-                for (int j = 0; j < NV; j++) val[j] = row_sum(val[j]);
-                if (row_leader<T>(lane)) {
-#pragma unroll
-                    for (int j = 0; j < NV; j++) lds_add(&s_acc[i * NV + j], val[j]);
+#pragma clang fp contract(fast)
+                val[6] = mul_zero_wins((dv2 - g1.z * mh), wz);
+                val[7] = mul_zero_wins((g1.y * mh - duv), wz);
+                val[8] = mul_zero_wins((du2 - g1.x * mh), wz);
+            }
+            int slot_i = i * SV;   // (kept scalar: the compiler otherwise folds it into a 64-bit vector multiply-add)
+            asm volatile("" : "+s"(slot_i));
+            reduce9_to_slot(val, slot_stores, reinterpret_cast<float*>(s_acc), slot_lane_base + slot_i);
+            hit |= 1ull << bit;
+            if constexpr (SHMM) {
+                // column nb of the batch's B: this splat's aw at the wave's 64 pixels (0 where it does not contribute)
+                s_B[(wave * MB + nb) * BROW + lane] = awz;
+                if (lane == 0) s_bidx[wave * MB + nb] = s_idx[i];
+                if (++nb == MB) {
+                    mma_flush(MB);
+                    nb = 0;
                 }
             }
           }
-          if constexpr (SLOTS)
-              if (lane == 0) s_hit[wave][word] = hit;
+          if (lane == 0) s_hit[wave][word] = hit;
         }
         if constexpr (SHMM) {
             if (nb > 0) {
@@ -1723,68 +1590,236 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
         GS_HALF_CHUNK(12);
         __syncthreads();
         GS_PHASE(3);
-        // one global atomic per value per (splat, tile)
-        if constexpr (SLOTS) {
-            // Phase 1, thread = splat: add the slots of the waves that wrote this splat, in wave order
-            // (deterministic per tile), apply the per-splat factors, and park the row in wave 0's slot of the
-            // same splat (each thread only ever touches its own splat's slots: no barrier needed before).
-            if (tid < cnt) {
-                T a[SV];
+        // the flush: one global atomic per value per (splat, tile)
+        // Phase 1, thread = splat: add the slots of the waves that wrote this splat, in wave order
+        // (deterministic per tile), apply the per-splat factors, and park the row in wave 0's slot of the
+        // same splat (each thread only ever touches its own splat's slots: no barrier needed before).
+        if (tid < cnt) {
+            T a[SV];
 #pragma unroll
-                for (int j = 0; j < SV; j++) a[j] = 0;
+            for (int j = 0; j < SV; j++) a[j] = 0;
 #pragma unroll
-                for (int w4 = 0; w4 < 4; w4++) {
-                    if ((s_hit[w4][tid >> 6] >> (tid & 63)) & 1ull) {
-                        const T* sl = s_acc + (w4 * RCHUNK + tid) * SV;
+            for (int w4 = 0; w4 < 4; w4++) {
+                if ((s_hit[w4][tid >> 6] >> (tid & 63)) & 1ull) {
+                    const T* sl = s_acc + (w4 * RCHUNK + tid) * SV;
 #pragma unroll
-                        for (int j = 0; j < SV; j++) a[j] += sl[j];
+                    for (int j = 0; j < SV; j++) a[j] += sl[j];
+                }
+            }
+            // sums of (w, w du, w dv) and of the per-pixel conic terms -> gradients (see the loop)
+            const T* rec = s_geom + tid * GS_PACKED_WIDTH;
+            const T ca = rec[4], cb = rec[5], cc = rec[6];
+            const T k = T(-0.5) * rec[3] * rec[8];
+            const T Mu = a[4], Mv = a[5];
+            a[4] = T(-2) * k * (cc * Mu - cb * Mv);
+            a[5] = T(-2) * k * (ca * Mv - cb * Mu);
+            a[6] *= k;
+            a[7] *= k;
+            a[8] *= k;
+            T* row = s_acc + tid * SV;
+#pragma unroll
+            for (int j = 0; j < SV; j++) row[j] = a[j];
+        }
+        __syncthreads();
+        // Phase 2, nine lanes = one row: a wave's atomic instruction then covers seven whole 36-byte
+        // rows with consecutive addresses, which the L2 handles per cache line -- 6x the rate of one
+        // thread per row with nine instructions (scripts/ubench/atomic_rows.hip: 0.094 vs 0.557 ms for
+        // the 1.25 M rows of a frame; the per-row form had become 0.17 ms of this kernel).
+        const int sub = lane / SV, col = lane - sub * SV;   // lane 63: idle
+        for (int r0 = wave * 7; r0 < cnt; r0 += 28) {
+            const int r = r0 + sub;
+            const bool in = lane < 63 && r < cnt && !(SHMM && col < 3);   // SHMM: the colour sums went out with the batches
+            const T v = in ? s_acc[r * SV + col] : T(0);
+            const unsigned long long nz = ballot(v != T(0));
+            const bool any = in && ((nz >> (sub * SV)) & 0x1ffull) != 0;   // rows of zeros stay untouched
+            GS_STAT(11, __popcll(ballot(any && col == 0)));   // flushed rows
+            if (any) {
+                const int g = s_idx[r];
+                T* dst;
+                if (slab) dst = g_rgb + (size_t)g * SV + col;   // [V, 9]: rgb 3 | opacity 1 | uv 2 | conic 3
+                else if (col < 3) dst = g_rgb + (size_t)g * 3 + col;
+                else if (col == 3) dst = g_opa + g;
+                else if (col < 6) dst = g_uv + (size_t)g * 2 + (col - 4);
+                else dst = g_conic + (size_t)g * 3 + (col - 6);
+                global_add(dst, v);
+            }
+        }
+        GS_PHASE(4);
+    }
+    GS_STAT_FLUSH(16);
+}
+
+// The fp64 reference kernel (gradcheck and the fp64 parity tests; never on a timed path): the same walk -- tile
+// prologue, chunks from the tile's deepest used splat to the front, touch masks, Q1 -- with the plainest accumulation.
+// One shared LDS row of 3 N_SH + 6 sums per staged splat, zero-filled per chunk; a visit sums each value over the wave
+// (wave_sum) and lane 63 adds it to the row with an LDS atomic; the flush issues one global atomic per value per
+// (splat, tile).  fp64 applies no cutoff radius and no alpha threshold (Thr<double>): every lane that reaches a
+// splat contributes.  No slab, segments, depth cut, tile order or handed-over masks: launch_render_bwd is its only caller.
+template <int N_SH>
+__global__ __launch_bounds__(RB) void k_render_bwd_ref(
+    const double* __restrict__ packed, const double* __restrict__ rgb, const double* __restrict__ view_dir,
+    const int* __restrict__ ranges, const int* __restrict__ sorted, const double* __restrict__ bg,
+    const int* __restrict__ nsp_in, const double* __restrict__ fw_in, const double* __restrict__ grad_image,
+    int W, int H, int ntx, int tile0, int nt, double* __restrict__ g_rgb, double* __restrict__ g_opa,
+    double* __restrict__ g_uv, double* __restrict__ g_conic, int exact, const double* __restrict__ src_opacity,
+    const double* __restrict__ src_conic) {
+    using T = double;
+    constexpr int CW = ColW<N_SH>::value;
+    constexpr int C = 3 * N_SH;
+    constexpr int NV = C + 6;   // rgb coeffs, opacity, u, v, conic x3
+    constexpr int REF_CH = ref_chunk<T>(N_SH);
+    constexpr int RCHUNK = Chunk<T, N_SH>::value;
+    constexpr int NWORD = RCHUNK / 64 > 0 ? RCHUNK / 64 : 1;
+    __shared__ alignas(16) T s_geom[RCHUNK * GS_PACKED_WIDTH];
+    __shared__ alignas(16) T s_col[N_SH > 1 ? RCHUNK * CW : 4];
+    __shared__ int s_idx[RCHUNK];
+    __shared__ T s_acc[RCHUNK * NV];   // [splat][NV]
+    __shared__ int s_max[4];
+    __shared__ unsigned long long s_mask[4][NWORD];
+
+    const int t_local = tile_of_block(blockIdx.x, nt);
+    if (t_local >= nt) return;
+    const int tile = tile0 + t_local;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const PixelMap px = pixel_of_thread(tile % ntx, tile / ntx, tid);
+    const bool valid = px.u < W && px.v < H;
+    const int s0 = ranges[tile];
+    const int n_tile = ranges[tile + 1] - s0;
+    if (n_tile <= 0) return;
+
+    int nsp = 0;
+    T weight = 0;
+    T gi[3] = {0, 0, 0};
+    T Y[N_SH];
+    {
+        T d[3] = {0, 0, 0};
+        if (valid) {
+            const size_t p = (size_t)px.v * W + px.u;
+            nsp = nsp_in[p];
+            weight = fw_in[p];
+            gi[0] = grad_image[p * 3 + 0];
+            gi[1] = grad_image[p * 3 + 1];
+            gi[2] = grad_image[p * 3 + 2];
+            if constexpr (N_SH > 1) {
+                d[0] = view_dir[p * 3 + 0]; d[1] = view_dir[p * 3 + 1]; d[2] = view_dir[p * 3 + 2];
+            }
+        }
+        if constexpr (N_SH > 1) sh_basis<T, N_SH>(d, Y);
+        else Y[0] = T(GS_SH_0);
+    }
+    // the tile's deepest used splat (render_backward.cu:131 makes everything beyond it a no-op)
+    int m = nsp;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) m = max(m, __shfl_xor(m, d));
+    if (lane == 0) s_max[wave] = m;
+    __syncthreads();
+    const int n_used = min(n_tile, max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3])));
+    if (n_used <= 0) return;
+
+    const T pu = T(px.u), pv = T(px.v);
+    T color_accum[3] = {0, 0, 0};
+    bool bg_init = false;
+    const T bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
+
+    // Q1 (render_backward.cu:185 compares a chunk-local index): k % REF_CH for k = base + i, i < RCHUNK <= REF_CH, is
+    // base % REF_CH + i with at most one wrap; exact mode never wraps
+    static_assert(RCHUNK <= REF_CH, "one wrap per chunk");
+    const int q1_wrap = exact ? 0x7fffffff : REF_CH;
+    for (int chunk = (n_used - 1) / RCHUNK; chunk >= 0; chunk--) {
+        const int base = chunk * RCHUNK;
+        const int base_q = exact ? base : base % REF_CH;
+        const int cnt = min(RCHUNK, n_used - base);
+        __syncthreads();   // previous chunk fully flushed
+        stage_chunk<T, N_SH>(packed, rgb, sorted, s0 + base, cnt, tid, s_geom, s_col, s_idx, src_opacity, src_conic);
+        for (int k = tid; k < cnt * NV; k += RB) s_acc[k] = 0;
+        // (no barrier in between: thread t tests the record thread t staged)
+        build_touch_masks<T, RCHUNK>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
+        __syncthreads();
+
+        for (int word = (cnt - 1) >> 6; word >= 0; word--) {
+          unsigned long long m = s_mask[wave][word];
+          m = wave_uniform(m);
+          while (m) {
+            const int bit = 63 - __builtin_clzll(m);
+            m &= ~(1ull << bit);
+            const int i = (word << 6) + bit;
+            const int k = base + i;
+            int kq = base_q + i;   // = exact ? k : k % REF_CH
+            kq = kq >= q1_wrap ? kq - q1_wrap : kq;
+            const bool reach = k < nsp;   // render_backward.cu:131 (nsp == 0 outside the image)
+            if (ballot(reach) == 0) continue;      // wave-uniform: no lane reaches this splat
+            T val[NV];
+#pragma unroll
+            for (int j = 0; j < NV; j++) val[j] = 0;
+            if (reach) {
+                const T* rec = s_geom + i * GS_PACKED_WIDTH;
+                const Vec4<T> g0 = *reinterpret_cast<const Vec4<T>*>(rec);       // u v r2 opacity
+                const Vec4<T> g1 = *reinterpret_cast<const Vec4<T>*>(rec + 4);   // a b c det
+                const T du = pu - g0.x, dv = pv - g0.y;
+                const T a = g1.x, b = g1.y, c = g1.z, rdet = rec[8], opa = g0.w;
+                // render_backward.cu:153-165 (multiplies by 1/det; forward divides)
+                T norm_prob = 0;
+                const T mh = (c * du * du - (b + b) * du * dv + a * dv * dv) * rdet;
+                if (mh > T(0)) norm_prob = gexp<T>(T(-0.5) * mh);
+                T alpha = opa * norm_prob;
+                if (alpha > Thr<T>::sat_gt()) alpha = Thr<T>::alpha_cap();   // min(0.9999, .)
+                if (!bg_init) {   // render_backward.cu:172-181
+                    const T bw = background_weight<T>(alpha, weight);
+                    if (bw > Thr<T>::bgw_gt()) {
+                        color_accum[0] += bg0 * bw;
+                        color_accum[1] += bg1 * bw;
+                        color_accum[2] += bg2 * bw;
                     }
+                    bg_init = true;
                 }
-                // sums of (w, w du, w dv) and of the per-pixel conic terms -> gradients (see the loop)
-                const T* rec = s_geom + tid * GS_PACKED_WIDTH;
-                const T ca = rec[4], cb = rec[5], cc = rec[6];
-                const T k = T(-0.5) * rec[3] * rec[8];
-                const T Mu = a[4], Mv = a[5];
-                a[4] = T(-2) * k * (cc * Mu - cb * Mv);
-                a[5] = T(-2) * k * (ca * Mv - cb * Mu);
-                a[6] *= k;
-                a[7] *= k;
-                a[8] *= k;
-                T* row = s_acc + tid * SV;
+                // From here on only gradient VALUES are formed (no threshold depends on
+                // them): evaluated in T with the reference's formulas factored
+                // (render_backward.cu:183-234) and contraction allowed; checked at 1e-4.
+                {
+#pragma clang fp contract(fast)
+                    const T r1ma = fast_rcp(T(1) - alpha);
+                    if (kq < nsp - 1) weight = weight * r1ma;   // Q1 (chunk-local index) unless exact
+                    T col[3];
+                    splat_colour<T, N_SH>(s_geom, s_col, i, Y, col);
+                    const T aw = alpha * weight;
+                    T grad_alpha = 0;
 #pragma unroll
-                for (int j = 0; j < SV; j++) row[j] = a[j];
-            }
-            __syncthreads();
-            // Phase 2, nine lanes = one row: a wave's atomic instruction then covers seven whole 36-byte
-            // rows with consecutive addresses, which the L2 handles per cache line -- 6x the rate of one
-            // thread per row with nine instructions (scripts/ubench/atomic_rows.hip: 0.094 vs 0.557 ms for
-            // the 1.25 M rows of a frame; the per-row form had become 0.17 ms of this kernel).
-            const int sub = lane / SV, col = lane - sub * SV;   // lane 63: idle
-            for (int r0 = wave * 7; r0 < cnt; r0 += 28) {
-                const int r = r0 + sub;
-                const bool in = lane < 63 && r < cnt && !(SHMM && col < 3);   // SHMM: the colour sums went out with the batches
-                const T v = in ? s_acc[r * SV + col] : T(0);
-                const unsigned long long nz = ballot(v != T(0));
-                const bool any = in && ((nz >> (sub * SV)) & 0x1ffull) != 0;   // rows of zeros stay untouched
-                GS_STAT(11, __popcll(ballot(any && col == 0)));   // flushed rows
-                if (any) {
-                    const int g = s_idx[r];
-                    T* dst;
-                    if (slab) dst = g_rgb + (size_t)g * SV + col;   // [V, 9]: rgb 3 | opacity 1 | uv 2 | conic 3
-                    else if (col < 3) dst = g_rgb + (size_t)g * 3 + col;
-                    else if (col == 3) dst = g_opa + g;
-                    else if (col < 6) dst = g_uv + (size_t)g * 2 + (col - 4);
-                    else dst = g_conic + (size_t)g * 3 + (col - 6);
-                    global_add(dst, v);
+                    for (int ch = 0; ch < 3; ch++) {
+                        const T grl = aw * gi[ch];
+#pragma unroll
+                        for (int s = 0; s < N_SH; s++) val[N_SH * ch + s] = Y[s] * grl;
+                        grad_alpha += (col[ch] * weight - color_accum[ch] * r1ma) * gi[ch];
+                        color_accum[ch] += col[ch] * aw;
+                    }
+                    val[C + 0] = norm_prob * grad_alpha;
+                    // d alpha / d mh^2 = -alpha_unclamped / 2; t = rdet * grad_mh
+                    const T t = T(-0.5) * norm_prob * opa * grad_alpha * rdet;
+                    const T A = c * du - b * dv;
+                    const T B = a * dv - b * du;
+                    val[C + 1] = T(-2) * A * t;           // :216-217
+                    val[C + 2] = T(-2) * B * t;           // :218-219
+                    val[C + 3] = (dv * dv - c * mh) * t;  // :221-229 with cf = mh^2 * rdet
+                    val[C + 4] = (b * mh - du * dv) * t;
+                    val[C + 5] = (du * du - a * mh) * t;
                 }
             }
-        } else if (tid < cnt) {
+#pragma unroll
+            for (int j = 0; j < NV; j++) val[j] = wave_sum(val[j]);   // total in lane 63
+            if (lane == 63) {
+#pragma unroll
+                for (int j = 0; j < NV; j++)
+                    __hip_atomic_fetch_add(&s_acc[i * NV + j], val[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+          }
+        }
+        __syncthreads();
+        // one global atomic per value per (splat, tile); rows of zeros stay untouched
+        if (tid < cnt) {
             const int g = s_idx[tid];
             const T* a = s_acc + tid * NV;
             bool any = false;
 #pragma unroll
             for (int j = 0; j < NV; j++) any |= (a[j] != T(0));
-            GS_STAT(11, __popcll(__ballot(any)));   // flushed rows
             if (any) {
 #pragma unroll
                 for (int j = 0; j < C; j++) global_add(g_rgb + (size_t)g * C + j, a[j]);
@@ -1796,9 +1831,7 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
                 global_add(g_conic + (size_t)g * 3 + 2, a[C + 5]);
             }
         }
-        GS_PHASE(4);
     }
-    GS_STAT_FLUSH(16);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2146,15 +2179,26 @@ static int launch_render_bwd(const void* packed_or_uvs, const void* opacity, con
     const int nt = (tile_row1 - tile_row0) * ntx;
     if (nt == 0) return GS_OK;
     const int grid = render_grid(nt);
-    DISPATCH_T(dtype,
-               DISPATCH_SH(n_sh, (k_render_bwd<T, N_SH><<<grid, RB, 0, s>>>(
-                                     (const T*)packed_or_uvs, (const T*)rgb, (const T*)view_dir_by_pixel,
-                                     tile_ranges, sorted_gaussians, (const T*)background_rgb,
-                                     num_splats_per_pixel, (const T*)final_weight_per_pixel,
-                                     (const T*)grad_image, W, H, ntx, tile_row0 * ntx, nt,
-                                     (T*)grad_rgb, (T*)grad_opacity, (T*)grad_uv,
-                                     (T*)grad_conic, 0, exact, nullptr, (const T*)opacity,
-                                     (const T*)conic, SEG_NONE, nullptr, nullptr, nullptr, nullptr))));
+    if (dtype == GS_F32) {
+        using T = float;
+        DISPATCH_SH(n_sh, (k_render_bwd<T, N_SH><<<grid, RB, 0, s>>>(
+                              (const T*)packed_or_uvs, (const T*)rgb, (const T*)view_dir_by_pixel, tile_ranges,
+                              sorted_gaussians, (const T*)background_rgb, num_splats_per_pixel,
+                              (const T*)final_weight_per_pixel, (const T*)grad_image, W, H, ntx, tile_row0 * ntx, nt,
+                              (T*)grad_rgb, (T*)grad_opacity, (T*)grad_uv, (T*)grad_conic, 0, exact, nullptr,
+                              (const T*)opacity, (const T*)conic, SEG_NONE, nullptr, nullptr, nullptr, nullptr)));
+    } else if (dtype == GS_F64) {
+        using T = double;
+        DISPATCH_SH(n_sh, (k_render_bwd_ref<N_SH><<<grid, RB, 0, s>>>(
+                              (const T*)packed_or_uvs, (const T*)rgb, (const T*)view_dir_by_pixel, tile_ranges,
+                              sorted_gaussians, (const T*)background_rgb, num_splats_per_pixel,
+                              (const T*)final_weight_per_pixel, (const T*)grad_image, W, H, ntx, tile_row0 * ntx, nt,
+                              (T*)grad_rgb, (T*)grad_opacity, (T*)grad_uv, (T*)grad_conic, exact, (const T*)opacity,
+                              (const T*)conic)));
+    } else {
+        gs::set_error("Inputs must be float32 or float64");
+        return GS_EINVAL;
+    }
     return check_launch("render_tiles_backward");
 }
 

@@ -459,6 +459,45 @@ def test_render_fp64_parity(hip_backend, n_sh):
         assert scaled_err(got[k], ref[k]) < 1e-11, f"{k}: {scaled_err(got[k], ref[k])}"
 
 
+@pytest.mark.parametrize("mode", ["compat", "exact"])
+@pytest.mark.parametrize("n_sh", [1, 16])
+def test_render_fp64_backward_second_chunk(hip_backend, n_sh, mode):
+    """The fp64 backward kernel stages its own chunks (256 splats with one colour coefficient, 64 with 16): one 16x16
+    tile with 300 faint splats (the recipe of test_exact_backward_mode_is_the_derivative_of_the_forward), which every
+    pixel composites to the end, so the kernel walks 2 resp. 5 chunks, the last one partial.  In compat mode the
+    16-coefficient kernel's Q1 index (render_backward.cu:185) wraps at every 64th entry."""
+    from gaussian_splatting_amd import _hip
+    orc = oracle()
+    gen = torch.Generator().manual_seed(7 + n_sh)
+    V, W, H = 300, 16, 16
+    rnd = lambda *s: torch.rand(*s, generator=gen, dtype=torch.float64)
+    d = dict(W=W, H=H, uv=rnd(V, 2) * 16,
+             conic=torch.stack([20 + 30 * rnd(V), 4 * (rnd(V) - 0.5), 20 + 30 * rnd(V)], dim=1),
+             opacity=0.002 + 0.004 * rnd(V, 1))
+    if n_sh == 1:
+        coeffs, rays = rnd(V, 3), torch.zeros(1, 1, 1, dtype=torch.float64)
+    else:
+        coeffs = torch.cat((rnd(V, 3, 1), 0.2 * (rnd(V, 3, n_sh - 1) - 0.5)), dim=2)
+        rays = torch.randn(H, W, 3, generator=gen, dtype=torch.float64)
+        rays = rays / rays.norm(dim=2, keepdim=True)
+    bg = torch.full((3,), 0.3, dtype=torch.float64)
+    gi = torch.randn(H, W, 3, generator=gen, dtype=torch.float64)
+    ranges = torch.tensor([0, V], dtype=torch.int32)
+    sorted_g = torch.arange(V, dtype=torch.int32)
+    try:
+        _hip.set_backward_mode(mode)
+        orc.set_backward_exact(int(mode == "exact"))
+        ref = render_case(orc, "cpu", d, coeffs, rays, bg, sorted_g, ranges, torch.float64, gi)
+        got = render_case(hip_backend, DEV, d, coeffs, rays, bg, sorted_g, ranges, torch.float64, gi)
+    finally:
+        _hip.set_backward_mode("compat")
+        orc.set_backward_exact(0)
+    assert int(ref["nsp"].min()) == V   # nobody saturates: every pixel walks all 300 splats
+    assert torch.equal(got["nsp"], ref["nsp"])
+    for k in ("image", "fw", "g_rgb", "g_opacity", "g_uv", "g_conic"):
+        assert scaled_err(got[k], ref[k]) < 1e-11, f"{k}: {scaled_err(got[k], ref[k])}"
+
+
 def test_render_tile_row_restriction(hip_backend):
     _needs_tile_rows_extension(hip_backend)
     orc = oracle()
