@@ -22,8 +22,11 @@
 //                      a flag-and-repair pass that keeps it exact); see "per-tile sort",
 //                      "wave-level sorts" and "prefix sort" below.
 // The Gaussians walked can be restricted to an index list (multi-GPU band mode, struct Items).
-// Tile grids too large for an LDS histogram (T > 16384) fall back to global-atomic counters
-// (k_tile_count / k_tile_emit).
+// Tile rows too many for an LDS histogram (more than 16384 tiles), and frames with few Gaussians per tile, take
+// global-atomic counters instead (k_tile_count<LPG> / k_tile_emit<LPG>, use_private).
+// Dense frames bin by depth bucket instead of by slice and emit only each tile's nearest ~1024 entries: steps 1-4 as
+// k_bin_count_buckets, k_bin_colscan_cut, k_scan_tiles_cut, k_bin_emit_buckets, step 5 as k_tile_sort_runs; see
+// "depth cut" below.  The depth order of all of it is tile_math.h's sortable_bits.
 // HBM traffic: 20 B in per Gaussian per pass, 8 B out + 8 B in + 4 B out per instance,
 // + 2 * NB * T * 4 B for the histogram matrix.
 //
@@ -35,6 +38,7 @@
 #include "tile_sort.h"
 
 #include <atomic>
+#include <type_traits>
 
 namespace gs {
 
@@ -388,13 +392,12 @@ constexpr int PRIV_BLOCK = 512;
 constexpr int PRIV_MAX_TILES = 16384;   // 64 KiB of LDS
 constexpr int PRIV_NB = 1024;           // workgroups = slices of the Gaussian list
 
-// slice of workgroup b.  A tile's segment is filled slice by slice (hist row = slice) and a slice's run in
+// Workgroup b walks slice b.  A tile's segment is filled slice by slice (hist row = slice) and a slice's run in
 // it is a few keys long.  Giving the workgroups of one XCD (b % 8) consecutive slices, so that runs sharing a cache
 // line go through the same L2, measured 0.293 -> 0.287 ms for the emit at workload D (and runs of 8 depth buckets per
 // XCD in the depth-bucketed emit 87.8 -> 87.2 us, round 6); fewer, larger slices (512 x 1024 threads, 256 x 1024) are
 // no faster either: the 2.6x write amplification of the scattered 8-byte keys is not what bounds the emit.  The A/B
 // branches are kept as scripts/experiments/binning_macro_experiments.patch.
-__device__ inline int slice_index(int b) { return b; }
 __device__ inline void slice_of(int sl, int V, int& g0, int& g1) {
     const int chunk = (V + PRIV_NB - 1) / PRIV_NB;
     g0 = min(V, sl * chunk);
@@ -413,7 +416,7 @@ __global__ __launch_bounds__(PRIV_BLOCK) void k_bin_count(const float* __restric
     for (int t = threadIdx.x; t < Tb; t += PRIV_BLOCK) s_hist[t] = 0;
     __syncthreads();
     int g0, g1;
-    const int sl = slice_index(blockIdx.x);
+    const int sl = blockIdx.x;
     slice_of(sl, item_count(items, V), g0, g1);
     for (int base = g0; base < g1; base += PRIV_BLOCK) {   // wave-uniform trip count
         const int i = base + threadIdx.x;
@@ -466,11 +469,6 @@ __global__ __launch_bounds__(1024) void k_bin_colscan(int* __restrict__ hist, in
     }
 }
 
-__device__ inline uint32_t sortable_bits(float z) {   // monotone float -> uint map
-    const uint32_t u = __float_as_uint(z);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // cursor[T] must be zero on entry and is zero again on exit: the hit that takes a tile's last slot resets its cursor
 // (gs_tile_count leaves the zeros: k_scan_tiles clears each count it has read), so a repeated emit of the same
 // frame -- a capacity miss -- starts clean as well and no fill kernel runs per frame.
@@ -505,7 +503,7 @@ __global__ __launch_bounds__(PRIV_BLOCK) void k_bin_emit(
     Items items, int64_t cap) {
     extern __shared__ int s_cursor[];
     const int t0 = row0 * ntx, Tb = (row1 - row0) * ntx;   // the histogram matrix covers the rows [row0, row1)
-    const int sl = slice_index(blockIdx.x);
+    const int sl = blockIdx.x;
     const int* row = hist + (size_t)sl * Tb;
     for (int t = threadIdx.x; t < Tb; t += PRIV_BLOCK) s_cursor[t] = ranges[t0 + t] + row[t];
     __syncthreads();
@@ -544,44 +542,28 @@ __global__ __launch_bounds__(PRIV_BLOCK) void k_bin_emit(
 //                     workgroup derives the same boundaries from a fine histogram) and counted per (partition
 //                     workgroup, bucket)
 //   k_depth_scatter   counting sort of the Gaussian indices by bucket: list[] + bucket offsets boff[NBK + 1]
-//   k_bin_count       workgroup b walks bucket b (32-byte binning records gathered through the list: one sector per
-//                     Gaussian); rows of hist as before
-//   k_bin_colscan     + per tile: b*(t), n'(t) = entries in buckets <= b*(t) (<= 1024; everything if the tile has
-//                     no more than that), n(t) = all entries
+//   k_bin_count_buckets  k_bin_count with workgroup b walking bucket b (32-byte binning records gathered through the
+//                     list: one sector per Gaussian); rows of hist as before
+//   k_bin_colscan_cut k_bin_colscan + per tile: b*(t), n'(t) = entries in buckets <= b*(t) (<= 1024; everything if the
+//                     tile has no more than that), n(t) = all entries
 //   k_scan_tiles_cut  tile_ranges from n' (the lists that are emitted), full_ranges from n (where the complete list
 //                     of a tile goes if it has to be repaired), the deepest bucket any tile still wants
-//   k_bin_emit<CUT>   workgroups behind the deepest wanted bucket exit; a candidate tile that is cut in front of the
-//                     bucket is skipped before its separating-axis test
+//   k_bin_emit_buckets<1, 1024>  k_bin_emit per bucket: workgroups behind the deepest wanted bucket exit; a candidate
+//                     tile that is cut in front of the bucket is skipped before its separating-axis test
+// The bucket kernels are the slice kernels with another source of Gaussians (boff2[b] .. boff2[b + 1] of cs.list and
+// the records, instead of slice b of the items and the per-Gaussian arrays); the walk itself is the same code, kept
+// as two copies because every shared body tried so far changed the machine code of all of them
+// (profiles/r09/binning_dedupe_isa.txt) -- a change to one copy's trip loop, histogram or cursor belongs in the other.
 // A truncated list is a true depth prefix of the complete one (buckets are depth intervals; equal depths share a
 // bucket), completely sorted by the ordinary <= 1024 sort.  It stays exact the way the prefix sort did: the
 // forward raises tile_flags[t] when a truncated tile reaches the end of its list with an unsaturated pixel, and
-// the same call enqueues k_bin_emit<REST> (complete lists of the flagged tiles into an overflow buffer at
+// the same call enqueues k_bin_emit_buckets<2, 512> (complete lists of the flagged tiles into an overflow buffer at
 // full_ranges), their sort and a second render; the backward reads a flagged tile's list from the overflow.
 // All of it is enqueued without a host read; the repair kernels exit at once while nothing is flagged.
 constexpr int NBK = PRIV_NB;            // depth buckets == workgroups of the count / emit passes
 constexpr int DC_BLOCK = 1024;
 static_assert(NBK == GS_CUT_BUCKETS && NBK == DC_BLOCK, "one thread per bucket in the partition kernels");
 static_assert(GS_SORT_PREFIX == 1024, "a truncated list must fit the <= 1024 sort of k_tile_sort");
-
-__device__ inline uint32_t sortable_bits_u(float z) {   // (defined again below as sortable_bits: same map)
-    const uint32_t u = __float_as_uint(z);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// first index k in [0, n) with a[k] >= x (n if none); a ascending, in LDS
-__device__ inline int lower_bound_u32(const uint32_t* a, int n, uint32_t x) {
-    int lo = 0, len = n;
-    while (len > 0) {
-        const int half = len >> 1;
-        if (a[lo + half] < x) {
-            lo += half + 1;
-            len -= half + 1;
-        } else {
-            len = half;
-        }
-    }
-    return lo;
-}
 
 // block-wide exclusive prefix of one int per thread (1024 threads); returns the prefix, *total = the sum
 __device__ inline int block_scan_1024(int v, int* s_wave /*[17]*/, int* total) {
@@ -924,7 +906,7 @@ __global__ __launch_bounds__(BLOCK) void k_bin_emit_buckets(const float* __restr
         TileWalk tw;
         uint64_t key = 0;
         if (active) {
-            key = ((uint64_t)sortable_bits_u(r.b.y) << 32) | (uint32_t)g;
+            key = ((uint64_t)sortable_bits(r.b.y) << 32) | (uint32_t)g;
             tw = tile_walk_setup(r, ntx, nty, mh, row0, row1);
         }
         wave_for_each_tile(
@@ -1468,6 +1450,31 @@ int depth_cut_repair(const float* bin_records, int N, int ntx, int nty, float mh
 
 int* depth_cut_flag_counter(int32_t* cut_ws, int N, int T) { return cut_state_of(cut_ws, N, T).ctrl + 1; }
 
+// ---- launch shapes that two entry points share ----------------------------------------------------
+// The atomic-counter kernels give a Gaussian a group of lanes while the frame has few of them (see wave_for_each_tile)
+// (workload B, 90 k visible Gaussians, gs_tile_count / gs_tile_emit_sort entries with their scans and sort: one lane
+// per Gaussian 41 / 58 us, 4 lanes 32.3 / 46.2, 8 lanes 30.3 / 40.1, 16 lanes 28.1 / 34.6, 32 lanes 36.4 / 43.9;
+// every lane of a group repeats the Gaussian's setup, so the group shrinks as the frame grows)
+constexpr int SUBGROUP_SMALL = 16, SUBGROUP_SMALL_MAX_V = 1 << 17;
+constexpr int SUBGROUP_MID = 8, SUBGROUP_MID_MAX_V = 1 << 18;
+template <int K>
+using IntC = std::integral_constant<int, K>;
+// launch(IntC<LPG>) with the lanes per Gaussian for a frame of V: the one place the thresholds are applied, so that
+// count and emit agree (grid: div_up(V * LPG, BIN_BLOCK) workgroups)
+template <typename F>
+static void for_subgroup_of(int V, F launch) {
+    if (V <= SUBGROUP_SMALL_MAX_V) launch(IntC<SUBGROUP_SMALL>());
+    else if (V <= SUBGROUP_MID_MAX_V) launch(IntC<SUBGROUP_MID>());
+    else launch(IntC<1>());
+}
+// launch(IntC<CS_TILES>) with the column scan's width for Tb tiles (grid: div_up(Tb, CS_TILES) workgroups): the narrow
+// form below 2048 tiles (see k_bin_colscan)
+template <typename F>
+static void for_colscan_width_of(int Tb, F launch) {
+    if (Tb >= 2048) launch(IntC<GS_CS_TILES>());
+    else launch(IntC<16>());
+}
+
 }  // namespace gs
 
 using namespace gs;
@@ -1477,12 +1484,6 @@ extern "C" {
 // LDS-histogram mode pays when there are many instances per tile; with few Gaussians the
 // NB x T histogram matrix costs more than the global atomics it saves.  The decision depends only
 // on (T, V) so that gs_tile_count and gs_tile_emit_sort agree.
-// The atomic-counter kernels give a Gaussian a group of lanes while the frame has few of them (see wave_for_each_tile)
-// (workload B, 90 k visible Gaussians, gs_tile_count / gs_tile_emit_sort entries with their scans and sort: one lane
-// per Gaussian 41 / 58 us, 4 lanes 32.3 / 46.2, 8 lanes 30.3 / 40.1, 16 lanes 28.1 / 34.6, 32 lanes 36.4 / 43.9;
-// every lane of a group repeats the Gaussian's setup, so the group shrinks as the frame grows)
-constexpr int SUBGROUP_SMALL = 16, SUBGROUP_SMALL_MAX_V = 1 << 17;
-constexpr int SUBGROUP_MID = 8, SUBGROUP_MID_MAX_V = 1 << 18;
 // Tb: tiles of the rows binned (a band, or the grid).  The histogram matrix (PRIV_NB x Tb ints) lives behind the
 // grid's T counters; gs_tile_workspace_ints reserves room for the largest matrix any row range of the grid can ask
 // for, PRIV_NB x min(T, PRIV_MAX_TILES) -- a band of a grid that is itself too large for the LDS histogram (4K and
@@ -1516,27 +1517,22 @@ int gs_tile_count(const void* uvs, const void* conic, int V, const int32_t* visi
         k_bin_count<<<PRIV_NB, PRIV_BLOCK, sizeof(int) * (size_t)Tb, s>>>(
             (const float*)uvs, (const float*)conic, V, n_tiles_x, n_tiles_y, mh_dist, tile_row0,
             tile_row1, hist, items);
-        if (Tb >= 2048) k_bin_colscan<GS_CS_TILES><<<div_up(Tb, GS_CS_TILES), 1024, 0, s>>>(hist, Tb, counts + t0);
-        else k_bin_colscan<16><<<div_up(Tb, 16), 1024, 0, s>>>(hist, Tb, counts + t0);
+        for_colscan_width_of(Tb, [&](auto w) {
+            constexpr int CS_TILES = decltype(w)::value;
+            k_bin_colscan<CS_TILES><<<div_up(Tb, CS_TILES), 1024, 0, s>>>(hist, Tb, counts + t0);
+        });
     } else {
         if (hipMemsetAsync(counts, 0, sizeof(int) * (size_t)T, s) != hipSuccess) {
             gs::set_error("tile_count: memset failed");
             return GS_EHIP;
         }
-        if (V > 0) {
-            if (V <= SUBGROUP_SMALL_MAX_V)
-                k_tile_count<SUBGROUP_SMALL><<<div_up(V * SUBGROUP_SMALL, BIN_BLOCK), BIN_BLOCK, 0, s>>>(
-                    (const float*)uvs, (const float*)conic, V, n_tiles_x, n_tiles_y, mh_dist,
-                    tile_row0, tile_row1, counts, items);
-            else if (V <= SUBGROUP_MID_MAX_V)
-                k_tile_count<SUBGROUP_MID><<<div_up(V * SUBGROUP_MID, BIN_BLOCK), BIN_BLOCK, 0, s>>>(
-                    (const float*)uvs, (const float*)conic, V, n_tiles_x, n_tiles_y, mh_dist,
-                    tile_row0, tile_row1, counts, items);
-            else
-                k_tile_count<1><<<div_up(V, BIN_BLOCK), BIN_BLOCK, 0, s>>>(
-                    (const float*)uvs, (const float*)conic, V, n_tiles_x, n_tiles_y, mh_dist,
-                    tile_row0, tile_row1, counts, items);
-        }
+        if (V > 0)
+            for_subgroup_of(V, [&](auto lpg) {
+                constexpr int LPG = decltype(lpg)::value;
+                k_tile_count<LPG><<<div_up(V * LPG, BIN_BLOCK), BIN_BLOCK, 0, s>>>(
+                    (const float*)uvs, (const float*)conic, V, n_tiles_x, n_tiles_y, mh_dist, tile_row0, tile_row1,
+                    counts, items);
+            });
     }
     // (the histogram path writes the counts of the rows' tiles only; the atomic path zero-fills all of them)
     k_scan_tiles<<<1, 1024, 0, s>>>(counts, T, tile_ranges, visible_count, private_hist ? t0 : 0, private_hist ? Tb : T,
@@ -1578,18 +1574,12 @@ int gs_tile_emit_sort_bounded(const void* uvs, const void* xyz_camera_frame, con
             n_tiles_y, mh_dist, tile_row0, tile_row1, tile_ranges, hist, keys, items, S);
     } else {
         int32_t* cursor = workspace;   // zero since gs_tile_count's scan, and again after every emit (k_tile_emit)
-        if (V <= SUBGROUP_SMALL_MAX_V)
-            k_tile_emit<SUBGROUP_SMALL><<<div_up(V * SUBGROUP_SMALL, BIN_BLOCK), BIN_BLOCK, 0, s>>>(
-                (const float*)uvs, (const float*)xyz_camera_frame, (const float*)conic, V, n_tiles_x,
-                n_tiles_y, mh_dist, tile_row0, tile_row1, tile_ranges, cursor, keys, items, S);
-        else if (V <= SUBGROUP_MID_MAX_V)
-            k_tile_emit<SUBGROUP_MID><<<div_up(V * SUBGROUP_MID, BIN_BLOCK), BIN_BLOCK, 0, s>>>(
-                (const float*)uvs, (const float*)xyz_camera_frame, (const float*)conic, V, n_tiles_x,
-                n_tiles_y, mh_dist, tile_row0, tile_row1, tile_ranges, cursor, keys, items, S);
-        else
-            k_tile_emit<1><<<div_up(V, BIN_BLOCK), BIN_BLOCK, 0, s>>>(
-                (const float*)uvs, (const float*)xyz_camera_frame, (const float*)conic, V, n_tiles_x,
-                n_tiles_y, mh_dist, tile_row0, tile_row1, tile_ranges, cursor, keys, items, S);
+        for_subgroup_of(V, [&](auto lpg) {
+            constexpr int LPG = decltype(lpg)::value;
+            k_tile_emit<LPG><<<div_up(V * LPG, BIN_BLOCK), BIN_BLOCK, 0, s>>>(
+                (const float*)uvs, (const float*)xyz_camera_frame, (const float*)conic, V, n_tiles_x, n_tiles_y, mh_dist,
+                tile_row0, tile_row1, tile_ranges, cursor, keys, items, S);
+        });
     }
     const int t0 = tile_row0 * n_tiles_x;
     const int nt = (tile_row1 - tile_row0) * n_tiles_x;
@@ -1636,12 +1626,11 @@ int gs_tile_count_cut(const void* bin_records, int N, const int32_t* visible_cou
     k_depth_scatter<<<DC_PART, DC_BLOCK, 0, s>>>(visible_count, cs);
     k_bin_count_buckets<<<NBK, PRIV_BLOCK, sizeof(int) * (size_t)Tb, s>>>((const float*)bin_records, n_tiles_x, n_tiles_y,
                                                                           mh_dist, tile_row0, tile_row1, hist, cs);
-    if (Tb >= 2048)
-        k_bin_colscan_cut<GS_CS_TILES><<<div_up(Tb, GS_CS_TILES), 1024, 0, s>>>(hist, Tb, counts + t0, cs.totals + t0,
-                                                                                 cs.bstar + t0, GS_SORT_PREFIX);
-    else
-        k_bin_colscan_cut<16><<<div_up(Tb, 16), 1024, 0, s>>>(hist, Tb, counts + t0, cs.totals + t0, cs.bstar + t0,
-                                                              GS_SORT_PREFIX);
+    for_colscan_width_of(Tb, [&](auto w) {
+        constexpr int CS_TILES = decltype(w)::value;
+        k_bin_colscan_cut<CS_TILES><<<div_up(Tb, CS_TILES), 1024, 0, s>>>(hist, Tb, counts + t0, cs.totals + t0,
+                                                                         cs.bstar + t0, GS_SORT_PREFIX);
+    });
     k_scan_tiles_cut<<<1, 1024, 0, s>>>(counts, cs.totals, cs.bstar, T, tile_ranges, full_ranges, visible_count, t0, Tb,
                                         cs.ctrl, host_mirror);
     return check_launch("tile_count_cut");

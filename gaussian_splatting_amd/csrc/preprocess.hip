@@ -67,16 +67,12 @@ __device__ inline bool is_culled(const float* c, const float* __restrict__ K, co
            (uv[1] < fr.v_lo) | (uv[1] > fr.v_hi);
 }
 
-// sortable bits of a depth (monotone float -> uint) and its bin in the quantile histogram: GS_CUT_HIST_BINS bins over
-// the sortable-bit range of [near, far] (a visible Gaussian's depth lies inside)
-__device__ inline uint32_t depth_bits(float z) {
-    const uint32_t u = __float_as_uint(z);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// a depth's bin in the quantile histogram: GS_CUT_HIST_BINS bins over the sortable-bit range (tile_math.h:
+// sortable_bits) of [near, far] (a visible Gaussian's depth lies inside)
 __device__ inline int depth_bin(float z, const Frustum& fr) {
-    const uint32_t lo = depth_bits(fr.near), hi = depth_bits(fr.far);
+    const uint32_t lo = sortable_bits(fr.near), hi = sortable_bits(fr.far);
     const uint64_t range = (uint64_t)(hi - lo) + 1;
-    const uint32_t x = min(max(depth_bits(z), lo), hi);
+    const uint32_t x = min(max(sortable_bits(z), lo), hi);
     return (int)(((uint64_t)(x - lo) * GS_CUT_HIST_BINS) / range);
 }
 
@@ -168,7 +164,7 @@ __global__ __launch_bounds__(1024) void k_scan_counts(const int* __restrict__ co
             const int j = min(lo_i, GS_CUT_HIST_BINS - 1);
             const int64_t prev = j > 0 ? s_cum[j - 1] : 0, h = max(s_cum[j] - (int)prev, 1);
             // position inside bin j: (target - prev) / h of its width
-            const uint32_t lo = depth_bits(fr.near), hi = depth_bits(fr.far);
+            const uint32_t lo = sortable_bits(fr.near), hi = sortable_bits(fr.far);
             const uint64_t range = (uint64_t)(hi - lo) + 1;
             // (double arithmetic: the boundaries only have to be ascending and the same for everybody who reads
             // them -- this workgroup is their one source; every step below is monotone in the position)
@@ -355,18 +351,7 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))
                 br[0] = make_float4(uv[0], uv[1], c3[0], c3[1]);
                 br[1] = make_float4(c3[2], c[2], 0.0f, 0.0f);
                 // the depth bucket: first boundary >= the depth's sortable bits (equal depths share a bucket)
-                const uint32_t x = depth_bits(c[2]);
-                int lo_i = 0, len = GS_CUT_BUCKETS - 1;
-                while (len > 0) {
-                    const int half = len >> 1;
-                    if (s_bounds[lo_i + half] < x) {
-                        lo_i += half + 1;
-                        len -= half + 1;
-                    } else {
-                        len = half;
-                    }
-                }
-                o.bucket_of[v] = (uint16_t)lo_i;
+                o.bucket_of[v] = (uint16_t)lower_bound_u32(s_bounds, GS_CUT_BUCKETS - 1, sortable_bits(c[2]));
             }
         }
 

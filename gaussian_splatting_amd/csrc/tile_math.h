@@ -1,7 +1,8 @@
 // tile_math.h -- oriented bounding box of a projected Gaussian and its candidate tile window
 // (tile_culling.cu:69-122,138-156), shared by the binning kernels and the band pre-cull of the fused
 // per-Gaussian stage.  fp32, no contraction, same operation order as the reference; cos/sin of the
-// OBB angle are formed algebraically (see binning.hip).
+// OBB angle are formed algebraically (see binning.hip).  Also the depth order the two stages share: sortable_bits
+// and the search of the bucket boundaries.
 #pragma once
 #include "gs_common.h"
 
@@ -60,6 +61,33 @@ __device__ inline Window candidate_window(float u, float v, int r, int ntx, int 
     w.sy = max(w.sy, row0);
     w.ey = min(w.ey, row1);
     return w;
+}
+
+// Monotone float -> uint map of a depth: a < b as floats iff sortable_bits(a) < sortable_bits(b) as unsigned.
+// Three uses must be this one function, or the depth cut loses its claim that a truncated tile list is a true depth
+// prefix of the complete one:
+//   - the bucket boundaries are quantiles of the visible depths' sortable bits (preprocess.hip: depth_bin, k_scan_counts)
+//   - k_preprocess assigns a Gaussian its depth bucket by searching those boundaries for its depth's sortable bits
+//   - the emit kernels build the sort key from them (binning.hip: bin_emit_body, k_tile_emit)
+// Buckets are then intervals of the very order the per-tile sort uses, and equal keys' depths share a bucket.
+__device__ inline uint32_t sortable_bits(float z) {
+    const uint32_t u = __float_as_uint(z);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// first index k in [0, n) with a[k] >= x (n if none); a ascending
+__device__ inline int lower_bound_u32(const uint32_t* a, int n, uint32_t x) {
+    int lo = 0, len = n;
+    while (len > 0) {
+        const int half = len >> 1;
+        if (a[lo + half] < x) {
+            lo += half + 1;
+            len -= half + 1;
+        } else {
+            len = half;
+        }
+    }
+    return lo;
 }
 
 }  // namespace gs
