@@ -5,20 +5,73 @@ raises.  Build it with `python -c "import __graft_entry__ as g; g.build()"` or
 `make -C gaussian_splatting_amd/csrc`.
 """
 import ctypes
+import functools
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSPLAT_HIP_LIB selects another build of the same library (tools only: the instrumented
 # libgsplat_hip_stats.so of `make stats`); there is still no fallback if it is missing
 LIB_PATH = os.environ.get("GSPLAT_HIP_LIB") or os.path.join(_HERE, "libgsplat_hip.so")
 
-GS_F32 = 0
-GS_F64 = 1
-GS_SORT_PREFIX = 1024
-GS_CUT_HIST_BINS = 8192   # include/gsplat_hip.h
-GS_BACKWARD_DEFAULT = -1  # per-call argument of the render-backward entry points: the process default
-GS_BACKWARD_COMPAT = 0   # render backward bug-compatible with render_backward.cu:185 (default)
-GS_BACKWARD_EXACT = 1    # the exact gradient of the forward pass
+# the one statement of the C ABI (in-tree, as csrc/Makefile assumes): entry points, prototypes and constants come from it
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gsplat_hip.h")
+
+
+class HipLibraryError(RuntimeError):
+    pass
+
+
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64,
+            "size_t": ctypes.c_size_t, "int32_t": ctypes.c_int32, "uint64_t": ctypes.c_uint64}
+
+
+def parse_header(text):
+    """-> ({gs_name: (restype, [argtypes])}, {GS_NAME: int}) of a header text.  Every pointer parameter is c_void_p (it
+    takes None, an address or a ctypes array), a `const char*` return c_char_p; a scalar type that _SCALARS does not list
+    raises HipLibraryError: nothing is guessed."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+    defines = {m.group(1): int(m.group(2))
+               for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(GS_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, flags=re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+
+    def ctype(decl, where, ret=False):
+        words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+        if "*" in words and (not ret or words == ["char", "*"]):
+            return ctypes.c_char_p if ret else ctypes.c_void_p
+        if "*" not in words and words and words[0] in _SCALARS and len(words) <= 2 - ret:   # `type`, or `type name`
+            return _SCALARS[words[0]]
+        raise HipLibraryError(f"{where} `{' '.join(decl.split())}` has no ctypes mapping")
+
+    protos = {}
+    for m in re.finditer(r"([\w\s\*]+?)\b(gs_\w+)\s*\(([^;{)]*)\)\s*;", text):
+        ret, name, params = m.group(1), m.group(2), m.group(3).strip()
+        params = [] if params in ("", "void") else params.split(",")
+        protos[name] = (ctype(ret, f"{name}: return type", ret=True),
+                        [ctype(p, f"{name}: parameter {i + 1}") for i, p in enumerate(params)])
+    return protos, defines
+
+
+@functools.lru_cache(maxsize=None)
+def _header():
+    if not os.path.exists(HEADER_PATH):
+        raise HipLibraryError(f"{HEADER_PATH} not found: the prototypes of the C ABI are read from it (no untyped calls)")
+    with open(HEADER_PATH) as fh:
+        return parse_header(fh.read())
+
+
+def __getattr__(name):
+    """EXPORTS (every entry point the header declares) and the header's integer constants (GS_F32, GS_SORT_PREFIX,
+    GS_BACKWARD_EXACT, ...), read on first use rather than at import"""
+    protos, defines = _header()
+    if name != "EXPORTS" and name not in defines:
+        raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+    return globals().setdefault(name, sorted(protos) if name == "EXPORTS" else defines[name])
+
+
+def ptr(t):
+    """a tensor's device address for a pointer parameter of the C ABI; None -> NULL"""
+    return None if t is None else t.data_ptr()
 
 
 def set_backward_mode(mode):
@@ -26,44 +79,16 @@ def set_backward_mode(mode):
     in the transmittance update: the mathematically exact gradient).  Sets the process-wide DEFAULT: the
     render-backward entry points take the mode per call (ABI 5) and the fused frames pass the default that
     was in force at their FORWARD, so changing it never affects a backward that is already queued"""
-    code = {"compat": GS_BACKWARD_COMPAT, "exact": GS_BACKWARD_EXACT}.get(mode, mode)
+    defines = _header()[1]
+    code = {"compat": defines["GS_BACKWARD_COMPAT"], "exact": defines["GS_BACKWARD_EXACT"]}.get(mode, mode)
     check(lib().gs_set_backward_mode(int(code)))
 
 
 def get_backward_mode():
     return int(lib().gs_get_backward_mode())
 
-# every entry point include/gsplat_hip.h declares
-EXPORTS = [
-    "gs_last_error", "gs_abi_version",
-    "gs_camera_projection", "gs_camera_projection_backward",
-    "gs_compute_sigma_world", "gs_compute_sigma_world_backward",
-    "gs_compute_projection_jacobian", "gs_compute_projection_jacobian_backward",
-    "gs_compute_conic", "gs_compute_conic_backward",
-    "gs_precompute_rgb_from_sh", "gs_precompute_rgb_from_sh_backward",
-    "gs_tile_workspace_ints", "gs_tile_count", "gs_tile_emit_sort", "gs_tile_emit_sort_bounded", "gs_tile_sort_flagged",
-    "gs_preprocess_workspace_ints", "gs_preprocess_forward", "gs_preprocess_backward",
-    "gs_preprocess_backward_adam", "gs_pose_workspace_floats", "gs_pose_backward",
-    "gs_pack_splats", "gs_render_tiles", "gs_render_tiles_packed", "gs_render_tiles_prefix", "gs_render_tiles_prefix_phased",
-    "gs_render_tiles_backward",
-    "gs_render_tiles_backward_packed", "gs_render_tiles_backward_slab", "gs_render_backward_prologue",
-    "gs_render_segment_workspace_bytes",
-    "gs_set_backward_mode", "gs_get_backward_mode", "gs_render_depth", "gs_halo_workspace_ints", "gs_halo_plan", "gs_halo_gather_sum",
-    "gs_band_project", "gs_halo_plan_masked", "gs_preprocess_forward_list",
-    "gs_band_frontend_workspace_ints", "gs_band_frontend", "gs_band_gather_sum", "gs_preprocess_backward_gathered",
-    "gs_render_tiles_prefix_phased_m", "gs_render_tiles_cut_m", "gs_render_tiles_backward_slab_m",
-    "gs_adam_step", "gs_accumulate_grad_stats", "gs_stream_copy", "gs_ssim_l1_workspace_bytes", "gs_ssim_l1_loss",
-    "gs_densify_move",
-    "gs_cut_workspace_ints", "gs_cut_sample_stride", "gs_cut_supported", "gs_preprocess_forward_cut", "gs_tile_count_cut",
-    "gs_tile_emit_sort_cut", "gs_cut_debug_views", "gs_render_tiles_cut",
-    "gs_band_row_costs", "gs_band_assemble",
-]
 
 _lib = None
-
-
-class HipLibraryError(RuntimeError):
-    pass
 
 
 def lib():
@@ -78,16 +103,12 @@ def lib():
         # it would pull in /opt/rocm's runtime instead, and the second runtime to initialise finds no
         # device ("no ROCm-capable device is detected").
         import torch  # noqa: F401
-        _lib = ctypes.CDLL(LIB_PATH)
-        _lib.gs_last_error.restype = ctypes.c_char_p
-        _lib.gs_preprocess_workspace_ints.restype = ctypes.c_size_t
-        _lib.gs_pose_workspace_floats.restype = ctypes.c_size_t
-        _lib.gs_tile_workspace_ints.restype = ctypes.c_size_t
-        _lib.gs_halo_workspace_ints.restype = ctypes.c_size_t
-        _lib.gs_band_frontend_workspace_ints.restype = ctypes.c_size_t
-        _lib.gs_ssim_l1_workspace_bytes.restype = ctypes.c_size_t
-        _lib.gs_render_segment_workspace_bytes.restype = ctypes.c_size_t
-        _lib.gs_cut_workspace_ints.restype = ctypes.c_size_t
+        protos = _header()[0]
+        loaded = ctypes.CDLL(LIB_PATH)
+        for name, (restype, argtypes) in protos.items():   # no call without its prototype
+            fn = getattr(loaded, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _lib = loaded
     return _lib
 
 

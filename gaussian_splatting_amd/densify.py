@@ -62,8 +62,7 @@ def inverse_sigmoid(x):   # utils.py:11-15
     return math.log(x / (1.0 - x))
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_p = _hip.ptr
 
 
 class DensityController:
@@ -251,11 +250,10 @@ class DensityController:
         widths = (ctypes.c_int32 * n)(*[int(t[0].numel()) if t.shape[0] else int(math.prod(t.shape[1:])) for t in src])
         kinds = (ctypes.c_int32 * n)(*[_KIND.get(k, 0) for k in names])
         xyz_s, scale_s, quat_s = (src[names.index(k)] for k in ("xyz", "scale", "quaternion"))
-        _hip.call("gs_densify_move", n, arr(src), arr(dst), arr(src_m), arr(dst_m), arr(src_v), arr(dst_v), widths, kinds,
-                  N0, _p(dst_self), _p(dst_clone), _p(spl_self), _p(spl_clone), _p(xyz_s), _p(scale_s), _p(quat_s),
-                  _p(self.xyz_grad_accum), _p(self.grad_accum_count), _p(random_samples.contiguous()), int(P),
-                  int(samples), int(sample_base), ctypes.c_float(cfg.split_scale_factor),
-                  _hip.current_stream())
+        _hip.call("gs_densify_move", n, arr(src), arr(dst), arr(src_m), arr(dst_m), arr(src_v), arr(dst_v), widths,
+                  kinds, N0, _p(dst_self), _p(dst_clone), _p(spl_self), _p(spl_clone), _p(xyz_s), _p(scale_s),
+                  _p(quat_s), _p(self.xyz_grad_accum), _p(self.grad_accum_count), _p(random_samples.contiguous()),
+                  int(P), int(samples), int(sample_base), cfg.split_scale_factor, _hip.current_stream())
         for k, d, m, v in zip(names, dst, dst_m, dst_v):
             self._swap(k, d, m, v)
         self.reset_grad_accum()

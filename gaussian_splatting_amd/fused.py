@@ -18,7 +18,6 @@ to the reference-shaped path in splat_py.rasterize (still HIP kernels, never a C
 The four stages are plain functions (preprocess_forward, render_forward, render_backward,
 preprocess_backward) that gaussian_splatting_amd.sharded composes differently for multi-GPU frames.
 """
-import ctypes
 import os
 from types import SimpleNamespace
 
@@ -30,17 +29,12 @@ from .splat_py.structs import TILE_EDGE_LENGTH_PX
 from .splat_py.utils import compute_rays_in_world_frame
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_p = _hip.ptr
 
 
 def _stream():
     # every stage asks once and passes it on
     return _hip.current_stream()
-
-
-def _cf(x):
-    return ctypes.c_float(float(x))
 
 
 # Prefix mode of the per-tile sort (include/gsplat_hip.h: gs_tile_emit_sort): order only the 1024
@@ -275,10 +269,9 @@ def preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world,
     f.opacity_act, f.rgb_render, f.packed = opa.view(N, 1), rgbr.view(N, 3), packed.view(N, 12)
     f.cut = None
     _hip.call("gs_preprocess_forward", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), n_sh,
-              _p(camera_T_world), _p(K), N, width, height, _cf(near_thresh), _cf(far_thresh),
-              _cf(cull_mask_padding), _cf(mh_dist), row0, row1, _p(f.ws), _p(f.center), _p(f.count),
-              _p(f.culling_mask), _p(f.rank), _p(f.vis_idx), _p(f.uv), _p(f.xyz_cam), _p(f.conic),
-              _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), stream)
+              _p(camera_T_world), _p(K), N, width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, row0,
+              row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx), _p(f.uv),
+              _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), stream)
 
     # the plan's record lives right behind (S, V) at the tail of ranges_buf: one host read gets both
     f.subset = (None, None)
@@ -287,15 +280,15 @@ def preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world,
         plan(f)
     subset, subset_n = f.subset
     _hip.call("gs_tile_count", _p(f.uv), _p(f.conic), N, _p(f.count), _p(subset), _p(subset_n), ntx, nty,
-              _cf(mh_dist), row0, row1, _p(f.tile_counts), _p(f.ranges_buf), None, stream)
+              mh_dist, row0, row1, _p(f.tile_counts), _p(f.ranges_buf), None, stream)
 
     def emit_sort(capacity):
         sorted_buf = torch.empty(capacity, **i32)
         keys = torch.empty(capacity, dtype=torch.int64, device=dev)
         if capacity > 0:
             _hip.call("gs_tile_emit_sort", _p(f.uv), _p(f.xyz_cam), _p(f.conic), N, _p(f.count), _p(subset),
-                      _p(subset_n), ntx, nty, _cf(mh_dist), row0, row1, _p(f.ranges_buf), _p(f.tile_counts), _p(keys),
-                      ctypes.c_int64(capacity), _p(sorted_buf), sort_prefix, stream)
+                      _p(subset_n), ntx, nty, mh_dist, row0, row1, _p(f.ranges_buf), _p(f.tile_counts), _p(keys),
+                      capacity, _p(sorted_buf), sort_prefix, stream)
         return sorted_buf, keys
 
     # The frame's only device->host read: (S, V) [+ the plan's record], to size the outputs.  If a
@@ -359,12 +352,11 @@ def _preprocess_forward_cut(f, xyz, quaternion, scale, opacity, rgb, sh, camera_
     f.uv, f.xyz_cam, f.conic = uv.view(N, 2), xyz_cam.view(N, 3), conic.view(N, 3)
     f.opacity_act, f.rgb_render, f.packed = opa.view(N, 1), rgbr.view(N, 3), packed.view(N, 12)
     _hip.call("gs_preprocess_forward_cut", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), f.n_sh,
-              _p(camera_T_world), _p(K), N, f.width, f.height, _cf(near_thresh), _cf(far_thresh),
-              _cf(cull_mask_padding), _cf(f.mh_dist), row0, row1, _p(f.ws), _p(f.center), _p(f.count),
-              _p(f.culling_mask), _p(f.rank), _p(f.vis_idx), _p(f.uv), _p(f.xyz_cam), _p(f.conic),
-              _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), _p(bin_rec), _p(cut_ws), _p(_depth_hist(dev)), stride,
-              stream)
-    _hip.call("gs_tile_count_cut", _p(bin_rec), N, _p(f.count), ntx, nty, _cf(f.mh_dist), row0, row1,
+              _p(camera_T_world), _p(K), N, f.width, f.height, near_thresh, far_thresh, cull_mask_padding, f.mh_dist,
+              row0, row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx), _p(f.uv),
+              _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), _p(bin_rec), _p(cut_ws),
+              _p(_depth_hist(dev)), stride, stream)
+    _hip.call("gs_tile_count_cut", _p(bin_rec), N, _p(f.count), ntx, nty, f.mh_dist, row0, row1,
               _p(f.tile_counts), _p(cut_ws), _p(f.ranges_buf), _p(full_ranges), None, stream)
     f.subset = (None, None)
     f.record = f.ranges_buf[T + 3:]
@@ -374,8 +366,8 @@ def _preprocess_forward_cut(f, xyz, quaternion, scale, opacity, rgb, sh, camera_
     sorted_buf = torch.empty(S, dtype=torch.int32, device=dev)
     keys = torch.empty(S, dtype=torch.int64, device=dev)
     if S > 0:
-        _hip.call("gs_tile_emit_sort_cut", _p(bin_rec), N, ntx, nty, _cf(f.mh_dist), row0, row1, _p(f.ranges_buf),
-                  _p(f.tile_counts), _p(cut_ws), _p(keys), ctypes.c_int64(S), _p(sorted_buf), stream)
+        _hip.call("gs_tile_emit_sort_cut", _p(bin_rec), N, ntx, nty, f.mh_dist, row0, row1, _p(f.ranges_buf),
+                  _p(f.tile_counts), _p(cut_ws), _p(keys), S, _p(sorted_buf), stream)
     c = _counters
     c["frames"] += 1
     c["depth_cut_frames"] += 1
@@ -435,9 +427,8 @@ def preprocess_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_ba
     grad_sh = gsh.view(n, 3, f.n_sh - 1) if f.n_sh > 1 else None
     if n > 0:
         _hip.call("gs_preprocess_backward", _p(xyz[i0:i1]), _p(quaternion[i0:i1]), _p(scale[i0:i1]), f.n_sh,
-                  _p(camera_T_world), _p(K), _p(f.center), _p(f.rank[i0:i1]), _p(f.opacity_act), _p(slab),
-                  int(v_base), n, _p(grad_xyz), _p(grad_q), _p(grad_scale), _p(grad_opacity), _p(grad_rgb),
-                  _p(grad_sh), _stream())
+                  _p(camera_T_world), _p(K), _p(f.center), _p(f.rank[i0:i1]), _p(f.opacity_act), _p(slab), v_base, n,
+                  _p(grad_xyz), _p(grad_q), _p(grad_scale), _p(grad_opacity), _p(grad_rgb), _p(grad_sh), _stream())
     return grad_xyz, grad_q, grad_scale, grad_opacity, grad_rgb, grad_sh
 
 
@@ -450,7 +441,7 @@ def pose_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_base=0):
     grad = torch.empty(4, 4, dtype=torch.float32, device=xyz.device)
     ws = torch.empty(_hip.lib().gs_pose_workspace_floats(n), dtype=torch.float32, device=xyz.device)
     _hip.call("gs_pose_backward", _p(xyz), _p(quaternion), _p(scale), _p(camera_T_world), _p(K), _p(f.rank), _p(slab),
-              int(v_base), n, _p(ws), _p(grad), _stream())
+              v_base, n, _p(ws), _p(grad), _stream())
     return grad
 
 
@@ -466,10 +457,9 @@ def preprocess_backward_adam(xyz, camera_T_world, K, f, slab, plan):
         args = []
         for r in rows:
             p, m, v, lr, step = r if r is not None else (None, None, None, 0.0, 1)
-            args += [_p(p), _p(m), _p(v), ctypes.c_double(lr), ctypes.c_int64(step)]
+            args += [_p(p), _p(m), _p(v), lr, step]
         _hip.call("gs_preprocess_backward_adam", _p(xyz), f.n_sh, _p(camera_T_world), _p(K), _p(f.center), _p(f.rank),
-                  _p(f.opacity_act), _p(slab), 0, n, _p(grad_xyz), *args, ctypes.c_double(beta1), ctypes.c_double(beta2),
-                  ctypes.c_double(eps), _stream())
+                  _p(f.opacity_act), _p(slab), 0, n, _p(grad_xyz), *args, beta1, beta2, eps, _stream())
         # the kernel wrote through raw pointers: bump the version counters like an in-place torch op would
         for r in rows:
             if r is not None:
@@ -559,9 +549,9 @@ def render_forward(packed, rgb, ranges, sorted_g, keys, background_rgb, height, 
         # (never empty: a frame without a visible Gaussian still hands the backward a non-null overflow list)
         okeys = torch.empty(max(cut.S_full, 1), dtype=torch.int64, device=dev)
         osorted = torch.empty(max(cut.S_full, 1), dtype=torch.int32, device=dev)
-        _hip.call("gs_render_tiles_cut", _p(packed), _p(rgb), _p(ranges), _p(sorted_g), ctypes.c_int64(sorted_g.shape[0]),
-                  _p(cut.full_ranges), _p(cut.bin_rec), cut.N, _cf(cut.mh_dist), _p(cut.tile_counts), _p(cut.cut_ws),
-                  _p(okeys), _p(osorted), ctypes.c_int64(cut.S_full), _p(background_rgb), width, height, row0, row1,
+        _hip.call("gs_render_tiles_cut", _p(packed), _p(rgb), _p(ranges), _p(sorted_g), sorted_g.shape[0],
+                  _p(cut.full_ranges), _p(cut.bin_rec), cut.N, cut.mh_dist, _p(cut.tile_counts), _p(cut.cut_ws),
+                  _p(okeys), _p(osorted), cut.S_full, _p(background_rgb), width, height, row0, row1,
                   _p(flags), _p(nsp), _p(fw), _p(image), _p(cost), None, stream)
         cut.flags, cut.overflow_sorted = flags, osorted
         global last_tile_flags
@@ -575,7 +565,7 @@ def render_forward(packed, rgb, ranges, sorted_g, keys, background_rgb, height, 
         scratch = torch.empty(2 * ntx * nty, dtype=torch.int32, device=dev)
         flags, cost = scratch[:ntx * nty], scratch[ntx * nty:]
         _hip.call("gs_render_tiles_prefix", _p(packed), _p(rgb), _p(ranges), _p(sorted_g), _p(keys),
-                  ctypes.c_int64(sorted_g.shape[0]), _p(background_rgb), width, height, row0, row1, _p(flags),
+                  sorted_g.shape[0], _p(background_rgb), width, height, row0, row1, _p(flags),
                   _p(nsp), _p(fw), _p(image), _p(cost), seg_p, stream)
         last_tile_flags = flags
         if len(_flag_log) < 512:
@@ -606,14 +596,12 @@ def render_backward(packed, rgb, ranges, sorted_g, background_rgb, nsp, fw, grad
         cost = tile_cost
         order = torch.empty(tile_cost.numel() + 8, dtype=torch.int32, device=packed.device)
     # one prologue launch (clear the slab + order the tiles), then the render kernel alone in its entry
-    _hip.call("gs_render_backward_prologue", _p(slab), ctypes.c_int64(slab.shape[0]), _p(cost) if cost is not None else None,
-              _p(order) if order is not None else None, width, height, row0, row1, _stream())
+    _hip.call("gs_render_backward_prologue", _p(slab), slab.shape[0], _p(cost), _p(order), width, height, row0, row1,
+              _stream())
     _hip.call("gs_render_tiles_backward_slab", _p(packed), _p(rgb), _p(ranges), _p(sorted_g), _p(background_rgb),
-              _p(nsp), _p(fw), _p(grad_image), width, height, row0, row1, _p(slab), ctypes.c_int64(0),
-              None, _p(order) if order is not None else None,
-              _p(seg_state) if seg_on else None,
-              _p(cut.flags) if cut is not None else None, _p(cut.full_ranges) if cut is not None else None,
-              _p(cut.overflow_sorted) if cut is not None else None,
+              _p(nsp), _p(fw), _p(grad_image), width, height, row0, row1, _p(slab), 0, None, _p(order),
+              _p(seg_state) if seg_on else None, _p(cut.flags) if cut is not None else None,
+              _p(cut.full_ranges) if cut is not None else None, _p(cut.overflow_sorted) if cut is not None else None,
               _hip.GS_BACKWARD_DEFAULT if backward_mode is None else int(backward_mode), _stream())
     return slab[:V]
 
@@ -828,7 +816,7 @@ def render_depth(gaussians, alpha_threshold, camera_T_world, camera, near_thresh
                                camera.K.contiguous(), W, H, near_thresh, 3.0e38, cull_mask_padding, mh_dist, None, 0)
         depth = torch.full((H, W, 1), -1.0, dtype=torch.float32, device=g.xyz.device)
         _hip.call("gs_render_depth", _p(f.packed), _p(f.xyz_cam), _p(f.ranges), _p(f.sorted_g), W, H,
-                  _cf(alpha_threshold), _p(depth), _stream())
+                  alpha_threshold, _p(depth), _stream())
         return depth
 
 

@@ -167,10 +167,9 @@ class HaloPlan:
                 offsets.append(off)
                 off += c
             offs = (ctypes.c_int32 * len(offsets))(*offsets)
-            _hip.call("gs_halo_gather_sum", ctypes.c_void_p(self.mask.data_ptr()),
-                      ctypes.c_void_p(workspace.data_ptr()), N, self.world_size, self.rank, self.v_lo, self.v_hi,
-                      ctypes.c_void_p(recv.data_ptr()), offs, ctypes.c_void_p(out.data_ptr()),
-                      _hip.current_stream())
+            p = _hip.ptr
+            _hip.call("gs_halo_gather_sum", p(self.mask), p(workspace), N, self.world_size, self.rank, self.v_lo,
+                      self.v_hi, p(recv), offs, p(out), _hip.current_stream())
             return out
         mine = self.mask[self.v_lo:self.v_hi]
         off = 0
@@ -215,10 +214,9 @@ def enqueue_hip_plan(f, world_size, rank, bounds=None):
     f.halo_mask, f.halo_send_index, f.halo_ws = buf[:f.N], buf[f.N:2 * f.N], buf[2 * f.N:]
     rows = (ctypes.c_int32 * (G + 1))(*(bounds if bounds is not None else _band_rows(f.nty, G)))
     blks = (ctypes.c_int32 * (G + 1))(*owner_blocks(f.N, G))
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
-    _hip.call("gs_halo_plan", p(f.uv), p(f.conic), f.N, p(f.count), p(f.ws), f.ntx, f.nty,
-              ctypes.c_float(float(f.mh_dist)), rows, blks, G, rank, p(f.halo_mask), p(f.halo_ws),
-              p(f.halo_send_index), p(f.record), f.stream)
+    p = _hip.ptr
+    _hip.call("gs_halo_plan", p(f.uv), p(f.conic), f.N, p(f.count), p(f.ws), f.ntx, f.nty, f.mh_dist, rows, blks, G, rank,
+              p(f.halo_mask), p(f.halo_ws), p(f.halo_send_index), p(f.record), f.stream)
     if G > 1:
         f.subset = (f.halo_send_index, f.record)   # record[0] = length of the list
 

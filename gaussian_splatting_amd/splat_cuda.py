@@ -17,15 +17,13 @@ import sys
 import torch
 
 from . import _hip
-from ._hip import GS_F32, GS_F64
 
 
 def install(name="splat_cuda"):
     sys.modules[name] = sys.modules[__name__]
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
+_p = _hip.ptr
 
 
 def _stream():
@@ -53,14 +51,14 @@ def _valid(**tensors):
 
 def _dtype(first, **others):
     if first.dtype == torch.float32:
-        code = GS_F32
+        code = _hip.GS_F32
     elif first.dtype == torch.float64:
-        code = GS_F64
+        code = _hip.GS_F64
     else:
         raise RuntimeError("Inputs must be float32 or float64")
     for name, t in others.items():
         if t.dtype != first.dtype:
-            kind = "float" if code == GS_F32 else "double"
+            kind = "float" if code == _hip.GS_F32 else "double"
             raise RuntimeError(f"{name} is not a {kind} tensor")
     return code
 
@@ -221,16 +219,14 @@ def get_sorted_gaussian_list(max_tiles_per_gaussian, uvs, xyz_camera_frame, coni
     dev = uvs.device
     counts = torch.empty(_hip.lib().gs_tile_workspace_ints(T), dtype=torch.int32, device=dev)
     ranges = torch.empty(T + 1, dtype=torch.int32, device=dev)
-    mh = ctypes.c_float(mh_dist)
-    _hip.call("gs_tile_count", _p(uvs), _p(conic), V, None, None, None, int(n_tiles_x), int(n_tiles_y), mh, row0, row1, _p(counts),
-                          _p(ranges), None, _stream())
+    _hip.call("gs_tile_count", _p(uvs), _p(conic), V, None, None, None, int(n_tiles_x), int(n_tiles_y), mh_dist, row0, row1,
+              _p(counts), _p(ranges), None, _stream())
     S = int(ranges[T].item())   # the one host read: sizes the result
     sorted_g = torch.empty(S, dtype=torch.int32, device=dev)
     if S > 0:
         keys = torch.empty(S, dtype=torch.int64, device=dev)
-        _hip.call("gs_tile_emit_sort", _p(uvs), _p(xyz_camera_frame), _p(conic), V, None, None, None, int(n_tiles_x), int(n_tiles_y), mh,
-                                  row0, row1, _p(ranges), _p(counts), _p(keys), ctypes.c_int64(S), _p(sorted_g),
-                                  0, _stream())
+        _hip.call("gs_tile_emit_sort", _p(uvs), _p(xyz_camera_frame), _p(conic), V, None, None, None, int(n_tiles_x), int(n_tiles_y), mh_dist,
+                                  row0, row1, _p(ranges), _p(counts), _p(keys), S, _p(sorted_g), 0, _stream())
     return sorted_g, ranges
 
 
@@ -252,9 +248,8 @@ def band_mask(uvs, conic, n_tiles_x, n_tiles_y, mh_dist, band_rows):
     plan = torch.empty(4 + 2 * G, **i32)
     rows = (ctypes.c_int32 * (G + 1))(*[int(r) for r in band_rows])
     blks = (ctypes.c_int32 * (G + 1))(*([0] * G + [nblk]))
-    _hip.call("gs_halo_plan", _p(uvs), _p(conic), V, _p(count), _p(pre_ws), int(n_tiles_x), int(n_tiles_y),
-              ctypes.c_float(float(mh_dist)), rows, blks, G, 0, _p(mask), _p(ws), _p(send_index), _p(plan),
-              _stream())
+    _hip.call("gs_halo_plan", _p(uvs), _p(conic), V, _p(count), _p(pre_ws), int(n_tiles_x), int(n_tiles_y), mh_dist,
+              rows, blks, G, 0, _p(mask), _p(ws), _p(send_index), _p(plan), _stream())
     return mask
 
 
@@ -357,7 +352,6 @@ def render_depth_cuda(xyz_camera_frame, uvs, opacity, conic, splat_start_end_idx
     _int(splat_start_end_idx_by_tile_idx=splat_start_end_idx_by_tile_idx,
          gaussian_idx_by_splat_idx=gaussian_idx_by_splat_idx)
     H, W = depth_image.shape[0], depth_image.shape[1]
-    packed = _pack(uvs, opacity, conic, GS_F32)
+    packed = _pack(uvs, opacity, conic, _hip.GS_F32)
     _hip.call("gs_render_depth", _p(packed), _p(xyz_camera_frame), _p(splat_start_end_idx_by_tile_idx),
-                                     _p(gaussian_idx_by_splat_idx), W, H, ctypes.c_float(alpha_threshold),
-                                     _p(depth_image), _stream())
+              _p(gaussian_idx_by_splat_idx), W, H, alpha_threshold, _p(depth_image), _stream())

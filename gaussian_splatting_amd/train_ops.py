@@ -74,10 +74,8 @@ class Adam(torch.optim.Adam):
             ptrs = lambda k: (ctypes.c_void_p * n)(*[t[k].data_ptr() for t in chunk])
             _hip.call("gs_adam_step", n, ptrs(0), ptrs(1), ptrs(2), ptrs(3),
                       (ctypes.c_int64 * n)(*[t[0].numel() for t in chunk]),
-                      (ctypes.c_double * n)(*[t[4] for t in chunk]),
-                      (ctypes.c_int64 * n)(*[t[5] for t in chunk]),
-                      ctypes.c_double(chunk[0][6]), ctypes.c_double(chunk[0][7]), ctypes.c_double(chunk[0][8]),
-                      stream)
+                      (ctypes.c_double * n)(*[t[4] for t in chunk]), (ctypes.c_int64 * n)(*[t[5] for t in chunk]),
+                      chunk[0][6], chunk[0][7], chunk[0][8], stream)
             i = j
         # the kernel wrote through raw pointers: bump the version counters like an in-place torch op would,
         # so that autograd's saved-tensor check still catches a backward over stale parameters
@@ -252,10 +250,9 @@ def accumulate_grad_stats(uv_grad, culling_mask, xyz_grad, camera, uv_grad_accum
         uv_grad = uv_grad.contiguous()
     K = camera.K if (camera.K.dtype == torch.float32 and camera.K.is_contiguous()) else \
         camera.K.to(torch.float32).contiguous()
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-    _hip.call("gs_accumulate_grad_stats", p(uv_grad), int(uv_grad.stride(0)) if uv_grad.shape[0] else 2, p(rank),
-              p(xyz_grad), p(K), N, p(uv_grad_accum), p(xyz_grad_accum),
-              p(grad_accum_count), _hip.current_stream())
+    p = _hip.ptr
+    _hip.call("gs_accumulate_grad_stats", p(uv_grad), uv_grad.stride(0) if uv_grad.shape[0] else 2, p(rank),
+              p(xyz_grad), p(K), N, p(uv_grad_accum), p(xyz_grad_accum), p(grad_accum_count), _hip.current_stream())
 
 
 class _SsimL1Loss(torch.autograd.Function):
@@ -269,9 +266,8 @@ class _SsimL1Loss(torch.autograd.Function):
         out = torch.empty(4, dtype=torch.float32, device=dev)
         need_grad = image.requires_grad
         grad = torch.empty_like(image) if need_grad else None
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        _hip.call("gs_ssim_l1_loss", p(image), p(target), H, W, ctypes.c_float(float(ssim_frac)), p(ws), p(out),
-                  p(grad), _hip.current_stream())
+        p = _hip.ptr
+        _hip.call("gs_ssim_l1_loss", p(image), p(target), H, W, ssim_frac, p(ws), p(out), p(grad), _hip.current_stream())
         ctx.grad = grad
         ctx.mark_non_differentiable(out)
         return out[0], out

@@ -12,7 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from gaussian_splatting_amd import _hip, fused
-from gaussian_splatting_amd.fused import _cf, _p
+from gaussian_splatting_amd._hip import ptr as _p
 from gaussian_splatting_amd.synthetic import DEFAULTS, WORKLOADS, make_scene
 
 ap = argparse.ArgumentParser()
@@ -31,7 +31,7 @@ out = [torch.empty(N, k, device="cuda") for k in (3, 4, 3, 1, 3)] + [torch.empty
 
 
 def count(stream):
-    _hip.call("gs_tile_count", _p(f.uv), _p(f.conic), N, _p(f.count), None, None, ntx, nty, _cf(DEFAULTS["mh_dist"]),
+    _hip.call("gs_tile_count", _p(f.uv), _p(f.conic), N, _p(f.count), None, None, ntx, nty, DEFAULTS["mh_dist"],
               0, nty, _p(f.tile_counts), _p(f.ranges_buf), None, stream)
 
 

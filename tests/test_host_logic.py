@@ -190,10 +190,8 @@ def test_depth_cut_policy_and_size_helpers(monkeypatch):
     """fused.want_depth_cut ("auto": whole frames in the LDS-histogram regime whose lists averaged >= 1 280 entries per
     tile in an earlier frame of the shape) and the C ABI's size helpers of the depth-bucketed binning (no GPU needed:
     they only compute)."""
-    import ctypes
     from gaussian_splatting_amd import _hip, fused
     lib = _hip.lib()
-    lib.gs_cut_workspace_ints.restype = ctypes.c_size_t
     # every 44th Gaussian of workload D is sampled (<= 65 536 samples), small scenes sample everything
     assert lib.gs_cut_sample_stride(2_860_000) == 44 and lib.gs_cut_sample_stride(65_536) == 1
     assert lib.gs_cut_sample_stride(65_537) == 2 and lib.gs_cut_sample_stride(1) == 1
