@@ -9,18 +9,28 @@
 // are laid out so that each XCD renders a contiguous band of tiles (block b runs on XCD b%8):
 // neighbouring tiles share Gaussians and hit the same 4 MiB L2.
 //
-// Data flow.  Per chunk of splats (256 in the fp32 forward, 64 in its backward) the workgroup gathers the
+// Data flow.  Per chunk of splats (256 in the fused forward, 64 in its backward) the workgroup gathers the
 // 48-byte packed record (gs_pack_splats / gs_preprocess_forward: u v r2 opacity | a b c det | 1/det colour --
 // three 16-byte loads; or forms it from the reference's separate arrays, stage_chunk) and, for per-pixel SH,
 // the colour coefficients of the depth-sorted Gaussians into LDS; every thread then tests the record it
 // staged against the tile's four 8x8 patches (build_touch_masks) and a wave walks only the splats whose
-// cutoff ellipse reaches its patch, with wave-uniform (broadcast) LDS reads -- in the fp32 forward the next
-// visit's record is requested while the current one is composited (lds_record_fetch).  Barriers are uniform
+// cutoff ellipse reaches its patch, with wave-uniform (broadcast) LDS reads.  Barriers are uniform
 // (Q2 of SURVEY.md is not replicated).  Forward leaves the chunk loop as soon as every pixel of the tile is
 // saturated (result-preserving: a saturated pixel ignores all later splats, render.cu:106).
 //
+// Forward: two bodies.
+//   render_tile_fwd_fused<CK>, fp32 with one colour coefficient -- the fused renderer's, in k_render_fwd<float, 1>,
+//   k_render_fwd_ck (CK: leaves the depth-segment state for the backward) and k_render_fwd_flagged<CK> (repair pass);
+//   also what gs_render_tiles / gs_render_tiles_packed run for float32 with n_sh == 1.  The record of the next visit
+//   is requested while the current one is composited (lds_record_fetch, b + b staged in the record).  It alone
+//   carries the prefix mode, the depth cut, tile_flags / flag_counter, the speculative list capacity, the tile costs
+//   and the touch masks handed to the backward.
+//   render_tile_fwd_general<T, N_SH> in k_render_fwd_general, every other pair (float at 4 / 9 / 16 coefficients,
+//   double at 1 / 4 / 9 / 16: gradcheck and the parity tests): whole lists, the plain walk -- one record read per
+//   visit -- and the colour from the staged coefficients at the pixel's view direction (sh_basis, splat_colour).
+//
 // Prefix mode (binning.hip "prefix sort"): a long tile list may have only its 1024 nearest entries
-// ordered; the forward reads no further, raises tile_flags[t] if a pixel is still unsaturated there,
+// ordered; the fused forward reads no further, raises tile_flags[t] if a pixel is still unsaturated there,
 // and k_render_fwd_flagged renders such tiles again after their full sort -- results are exact.
 //
 // Backward: two kernels.  Both start at the tile's largest num_splats_per_pixel instead of the end of the list and
@@ -669,27 +679,29 @@ __host__ __device__ inline SegState seg_state_of(void* ws, int W, int H, int row
 // ---------------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------------
-// One tile by one workgroup.  sort_prefix > 0: prefix mode (binning.hip "prefix sort"), only the
+// Two bodies, one tile by one workgroup each: render_tile_fwd_fused (fp32, one colour coefficient: the fused
+// renderer's kernels) and render_tile_fwd_general (every other dtype and coefficient count: the reference-shaped
+// entry points, gradcheck and the parity tests).  The tile prologue and the pixel epilogue are the same text in both
+// (a shared epilogue function changed the register allocation of the four fused kernels: profiles/r10/fwd_split_isa.txt).
+//
+// The fused renderer's forward.  sort_prefix > 0: prefix mode (binning.hip "prefix sort"), only the
 // first sort_prefix entries of a prefix-sorted tile's segment are there; tile_flags[tile] is set to
 // whether the tile ran out of them.  flagged_only: the repair call, full list, flags untouched.
-template <typename T, int N_SH, bool CK = false>
-__device__ __forceinline__ void render_tile_fwd(
-    const int tile, const T* __restrict__ packed, const T* __restrict__ rgb,
-    const T* __restrict__ view_dir, const int* __restrict__ ranges, const int* __restrict__ sorted,
-    const T* __restrict__ bg, int W, int H, int ntx, int* __restrict__ nsp_out,
-    T* __restrict__ fw_out, T* __restrict__ image, int sort_prefix, int* __restrict__ tile_flags,
-    bool flagged_only, int64_t cap, int* __restrict__ tile_cost = nullptr,
-    const T* __restrict__ src_opacity = nullptr, const T* __restrict__ src_conic = nullptr,
-    const SegState seg = SEG_NONE, const int* __restrict__ full_ranges = nullptr,
-    int* __restrict__ flag_counter = nullptr, unsigned long long* __restrict__ touch_masks = nullptr) {
-    static_assert(!CK || (sizeof(T) == 4 && N_SH == 1), "segment checkpoints: the fused renderer's kernel only");
-    constexpr bool fast = sizeof(T) == 4;
+// CK: also leaves the state for the depth-segmented backward ("depth segments" above).
+template <bool CK>
+__device__ __forceinline__ void render_tile_fwd_fused(
+    const int tile, const float* __restrict__ packed, const float* __restrict__ rgb,
+    const int* __restrict__ ranges, const int* __restrict__ sorted,
+    const float* __restrict__ bg, int W, int H, int ntx, int* __restrict__ nsp_out,
+    float* __restrict__ fw_out, float* __restrict__ image, int sort_prefix, int* __restrict__ tile_flags,
+    bool flagged_only, int64_t cap, int* __restrict__ tile_cost,
+    const float* __restrict__ src_opacity, const float* __restrict__ src_conic,
+    const SegState seg, const int* __restrict__ full_ranges,
+    int* __restrict__ flag_counter, unsigned long long* __restrict__ touch_masks) {
     // the tile's own duration in 16-cycle units: the launch-order key of the backward (tile_order_body)
     const unsigned long long cost_c0 = tile_cost ? __builtin_readcyclecounter() : 0ull;
-    constexpr int CW = ColW<N_SH>::value;
-    constexpr int RCHUNK = Chunk<T, N_SH>::value;
-    __shared__ alignas(16) T s_geom[RCHUNK * GS_PACKED_WIDTH];
-    __shared__ alignas(16) T s_col[N_SH > 1 ? RCHUNK * CW : 4];
+    constexpr int RCHUNK = Chunk<float, 1>::value;
+    __shared__ alignas(16) float s_geom[RCHUNK * GS_PACKED_WIDTH];
 
     const int tid = threadIdx.x;
     const PixelMap px = pixel_of_thread(tile % ntx, tile / ntx, tid);
@@ -709,36 +721,24 @@ __device__ __forceinline__ void render_tile_fwd(
     // complete ones; a tile whose list was cut short and that reaches its end unsaturated is flagged and redone
     const bool truncated = !flagged_only && full_ranges != nullptr && full_ranges[tile + 1] - full_ranges[tile] > n_tile;
 
-    T Y[N_SH];
-    if constexpr (N_SH > 1) {
-        T d[3] = {0, 0, 0};
-        if (valid) {
-            const T* vd = view_dir + ((size_t)px.v * W + px.u) * 3;
-            d[0] = vd[0]; d[1] = vd[1]; d[2] = vd[2];
-        }
-        sh_basis<T, N_SH>(d, Y);
-    } else {
-        Y[0] = T(GS_SH_0);
-    }
-
     // A pixel is done when its accumulated alpha exceeds 0.9999 (render.cu:146,162) -- or when it lies outside the
     // image: those lanes start saturated.  "done" is READ OFF acc (one compare per visit) instead of being carried as a
     // flag: the compiler kept the flag as a 0/1 VGPR across the pipelined visits and spent an and, a compare and five
     // moves of every visit's ~52 vector instructions on it.  acc of an outside lane is never used (nothing is stored).
-    T acc = valid ? T(0) : T(2), fw = 0;
-    auto is_done = [&]() { return acc > Thr<T>::sat_gt(); };
-    T img[3] = {0, 0, 0};
+    float acc = valid ? 0.0f : 2.0f, fw = 0;
+    auto is_done = [&]() { return acc > Thr<float>::sat_gt(); };
+    float img[3] = {0, 0, 0};
     // num_splats_per_pixel == index of the first splat at whose turn the pixel is saturated
     // (render.cu:106,146,162), or the list length: set when the pixel saturates
     int nsp = n_tile;
-    const T pu = T(px.u), pv = T(px.v);
+    const float pu = float(px.u), pv = float(px.v);
     const int wave = tid >> 6;
     constexpr int NW = RCHUNK / 64 > 0 ? RCHUNK / 64 : 1;
     __shared__ unsigned long long s_mask[4][NW];
 
     // CK: state for the depth-segmented backward (see "depth segments" above)
-    T segL = 1;                    // product of (1 - alpha) over the current segment's contributors so far
-    T sg0 = 0, sg1 = 0, sg2 = 0;   // sum of colour * alpha * (that product before the splat): the segment's colour
+    float segL = 1;                    // product of (1 - alpha) over the current segment's contributors so far
+    float sg0 = 0, sg1 = 0, sg2 = 0;   // sum of colour * alpha * (that product before the splat): the segment's colour
     int kend = 0;                  // index after the last contributing splat
     int b_cur = 0;                 // current segment (wave-uniform)
     bool wave_fin = false;         // the wave's last record is written (every pixel of the patch saturated)
@@ -760,182 +760,135 @@ __device__ __forceinline__ void render_tile_fwd(
         const int cnt = min(RCHUNK, n_list - base);
         GS_STAT(1, 1);      // chunks
         GS_STAT(8, cnt);    // list entries staged
-        constexpr bool B2 = fast && N_SH == 1;   // the pipelined walk below reads b + b from the record
-        stage_chunk<T, N_SH, B2 ? 2 : 0>(packed, rgb, sorted, s0 + base, cnt, tid, s_geom, s_col, nullptr, src_opacity, src_conic);
+        // TWO_B = 2 / B_DOUBLED: the walk below reads b + b from the record
+        stage_chunk<float, 1, 2>(packed, rgb, sorted, s0 + base, cnt, tid, s_geom, nullptr, nullptr, src_opacity, src_conic);
         GS_PHASE(0);
         // (no barrier in between: thread t tests the record thread t staged)
-        build_touch_masks<T, RCHUNK, B2>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
+        build_touch_masks<float, RCHUNK, true>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
         __syncthreads();
-        if constexpr (fast && N_SH == 1) {
-            // the chunk's masks for the backward (see GS_MASK_WORDS): thread (word, patch) stores one 8-byte word
-            if (touch_masks != nullptr && tid < 4 * NW) {
-                const int word = base / 64 + (tid >> 2);
-                if (word < GS_MASK_WORDS) touch_masks[((size_t)tile * GS_MASK_WORDS + word) * 4 + (tid & 3)] = s_mask[tid & 3][tid >> 2];
-            }
+        // the chunk's masks for the backward (see GS_MASK_WORDS): thread (word, patch) stores one 8-byte word
+        if (touch_masks != nullptr && tid < 4 * NW) {
+            const int word = base / 64 + (tid >> 2);
+            if (word < GS_MASK_WORDS) touch_masks[((size_t)tile * GS_MASK_WORDS + word) * 4 + (tid & 3)] = s_mask[tid & 3][tid >> 2];
         }
         GS_PHASE(1);
-        if constexpr (fast && N_SH == 1) {
-            // pipelined walk: the record of the next visit is in flight while this one is composited
-            auto visit = [&](const LdsRecord& r, int i) {
-                GS_STAT(2, 1);
-                GS_STAT(6, __popcll(ballot(!is_done())));
-                GS_STAT_FLAG(st_in);
-                GS_STAT_FLAG(st_hit);
-                if (!is_done()) {
-                    const T du = pu - r.g0.x, dv = pv - r.g0.y;
-                    if (!(du * du + dv * dv > r.g0.z)) {
-                        GS_STAT_SET(st_in);
-                        const T a = r.g1.x, tb = r.g1.y, c = r.g1.z, det = r.g1.w;   // tb = b + b (stage_chunk)
-                        const T mh_num = c * du * du - tb * du * dv + a * dv * dv;
-                        const T mh = div_by_reciprocal(mh_num, det, r.g2.x);
-                        T alpha = r.g0.w * exp_neg_half(mh);
-                        // render.cu:133: alpha = 0 unless mh > 0 -- and a zero alpha fails the 1/255 test below.  Without
-                        // the segment state only that test reads alpha before it is known to pass: `mh > 0` joins the
-                        // test's lane mask (one scalar and) instead of a select in front of it
-                        const bool mh_pos = mh > T(0);
-                        if constexpr (CK) alpha = mh_pos ? alpha : T(0);
-                        if constexpr (CK) {
-                            // What the BACKWARD's walk will see at this entry.  It forms alpha from mh * (1 / det)
-                            // (render_backward.cu:153-157; the forward divides), a last-ulp difference that matters
-                            // in two places: next to the 1/255 threshold, where the two forms can disagree on whether
-                            // the splat contributes at all (~50 (pixel, splat) pairs of a frame at workload D; the
-                            // reference's walk then carries one factor 1 / (1 - 1/255) more or less than its forward
-                            // did, and so must the segments), and in 1 - alpha for alpha near 1 (6e-8 / (1 - alpha)
-                            // relative on the walk's factor).  There the backward's alpha is evaluated as well
-                            // (a few percent of the visits); elsewhere the forward's is within 6e-7 of it.
-                            // Values for the backward only: contraction allowed.
-#pragma clang fp contract(fast)
-                            T ab = alpha;
-                            const bool near = __builtin_fabsf(alpha - Thr<T>::alpha_min()) < T(4e-8) || alpha > T(0.9);
-                            if (near) {   // (skipped by the whole wave when no lane is near: s_cbranch_execz)
-                                const T mh_b = mh_num * r.g2.x;
-                                const T e_b = exp_neg_half(mh_b);
-                                ab = r.g0.w * ((mh_b > T(0)) ? e_b : T(0));
-                            }
-                            // branch-free: a splat the backward skips enters with alpha 0 (changes nothing)
-                            const bool cb = ab >= Thr<T>::alpha_min();
-                            const T cap = Thr<T>::alpha_cap();
-                            if (b_cur > 0) {   // (wave-uniform; nobody reads segment 0's record: no segment lies in front of it)
-                                const T ac = cb ? ((ab > cap) ? cap : ab) : T(0);   // the backward caps alpha
-                                const T aL = ac * segL;
-                                sg0 += r.g2.y * aL; sg1 += r.g2.z * aL; sg2 += r.g2.w * aL;
-                                segL -= aL;   // segL (1 - ac)
-                            }
-                            kend = cb ? base + i + 1 : kend;
-                        }
-                        if (mh_pos & !(alpha < Thr<T>::alpha_min())) {      // render.cu:145
-                            GS_STAT_SET(st_hit);
-                            // render.cu:149-150: final_weight = 1.0 - acc and weight = alpha * (1.0 - acc), the literal
-                            // making both double expressions that are narrowed to float -- six fp64-rate instructions
-                            // per contributing visit when written that way.  acc is 0 or >= 1/255 here (it only grows,
-                            // and the first weight is an alpha >= 1/255), so 1.0 - (double)acc is EXACT; hence
-                            // (a) its narrowing is the correctly rounded float difference, i.e. the float subtraction;
-                            // (b) alpha (1 - acc) = alpha - alpha acc as real numbers, and one double fma rounds that
-                            // once, exactly as the reference's double multiplication rounds its exact operands.
-                            // Same bits, four fp64-rate instructions and one fp32.
-                            fw = 1.0f - acc;
-                            const T weight = (T)__builtin_fma((double)alpha, -(double)acc, (double)alpha);
-                            img[0] += r.g2.y * weight;
-                            img[1] += r.g2.z * weight;
-                            img[2] += r.g2.w * weight;
-                            acc += weight;
-                            if (acc > Thr<T>::sat_gt()) {   // saturated: the next splat's check fails
-                                nsp = base + i + 1;
-                            }
-                        }
-                    }
-                }
-                GS_STAT(3, ballot(st_in) != 0);
-                GS_STAT(4, ballot(st_hit) != 0);
-                GS_STAT(5, __popcll(ballot(st_hit)));
-                GS_HALF_VISIT(ballot(st_in));
-            };
-            for (int word = 0; word < NW && word * 64 < cnt; word++) {
-                if constexpr (CK) {
-                    // crossing into the next depth segment: leave the state at the boundary behind
-                    const int sidx = min((base + word * 64) / SEG_LEN, SEG_MAX - 1);
-                    if (sidx != b_cur && !wave_fin) {
-                        write_record();
-                        b_cur = sidx;
-                    }
-                }
-                if (ballot(!is_done()) == 0) {   // wave-uniform: every pixel of the patch saturated
+        // pipelined walk: the record of the next visit is in flight while this one is composited
+        auto visit = [&](const LdsRecord& r, int i) {
+            GS_STAT(2, 1);                              // visits (touch-mask bits walked)
+            GS_STAT(6, __popcll(ballot(!is_done())));   // live lanes at the visit
+            GS_STAT_FLAG(st_in);
+            GS_STAT_FLAG(st_hit);
+            if (!is_done()) {
+                const float du = pu - r.g0.x, dv = pv - r.g0.y;
+                // beyond the cutoff radius alpha < 1/255 is certain: same outcome as render.cu:145-148
+                if (!(du * du + dv * dv > r.g0.z)) {
+                    GS_STAT_SET(st_in);
+                    const float a = r.g1.x, tb = r.g1.y, c = r.g1.z, det = r.g1.w;   // tb = b + b (stage_chunk)
+                    const float mh_num = c * du * du - tb * du * dv + a * dv * dv;
+                    const float mh = div_by_reciprocal(mh_num, det, r.g2.x);
+                    float alpha = r.g0.w * exp_neg_half(mh);
+                    // render.cu:133: alpha = 0 unless mh > 0 -- and a zero alpha fails the 1/255 test below.  Without
+                    // the segment state only that test reads alpha before it is known to pass: `mh > 0` joins the
+                    // test's lane mask (one scalar and) instead of a select in front of it
+                    const bool mh_pos = mh > 0.0f;
+                    if constexpr (CK) alpha = mh_pos ? alpha : 0.0f;
                     if constexpr (CK) {
-                        if (!wave_fin) write_record();
-                        wave_fin = true;
+                        // What the BACKWARD's walk will see at this entry.  It forms alpha from mh * (1 / det)
+                        // (render_backward.cu:153-157; the forward divides), a last-ulp difference that matters
+                        // in two places: next to the 1/255 threshold, where the two forms can disagree on whether
+                        // the splat contributes at all (~50 (pixel, splat) pairs of a frame at workload D; the
+                        // reference's walk then carries one factor 1 / (1 - 1/255) more or less than its forward
+                        // did, and so must the segments), and in 1 - alpha for alpha near 1 (6e-8 / (1 - alpha)
+                        // relative on the walk's factor).  There the backward's alpha is evaluated as well
+                        // (a few percent of the visits); elsewhere the forward's is within 6e-7 of it.
+                        // Values for the backward only: contraction allowed.
+#pragma clang fp contract(fast)
+                        float ab = alpha;
+                        const bool near = __builtin_fabsf(alpha - Thr<float>::alpha_min()) < 4e-8f || alpha > 0.9f;
+                        if (near) {   // (skipped by the whole wave when no lane is near: s_cbranch_execz)
+                            const float mh_b = mh_num * r.g2.x;
+                            const float e_b = exp_neg_half(mh_b);
+                            ab = r.g0.w * ((mh_b > 0.0f) ? e_b : 0.0f);
+                        }
+                        // branch-free: a splat the backward skips enters with alpha 0 (changes nothing)
+                        const bool cb = ab >= Thr<float>::alpha_min();
+                        const float a_cap = Thr<float>::alpha_cap();
+                        if (b_cur > 0) {   // (wave-uniform; nobody reads segment 0's record: no segment lies in front of it)
+                            const float ac = cb ? ((ab > a_cap) ? a_cap : ab) : 0.0f;   // the backward caps alpha
+                            const float aL = ac * segL;
+                            sg0 += r.g2.y * aL; sg1 += r.g2.z * aL; sg2 += r.g2.w * aL;
+                            segL -= aL;   // segL (1 - ac)
+                        }
+                        kend = cb ? base + i + 1 : kend;
                     }
-                    break;
-                }
-                unsigned long long m = wave_uniform(s_mask[wave][word]);
-                if (m == 0) continue;
-                LdsRecord ra, rb;
-                int cur = word * 64 + __builtin_ctzll(m), nxt;
-                m &= m - 1;
-                lds_record_fetch(ra, s_geom + cur * GS_PACKED_WIDTH);
-                while (true) {
-                    nxt = -1;
-                    if (m) {
-                        nxt = word * 64 + __builtin_ctzll(m);
-                        m &= m - 1;
-                        lds_record_fetch(rb, s_geom + nxt * GS_PACKED_WIDTH);
+                    if (mh_pos & !(alpha < Thr<float>::alpha_min())) {      // render.cu:145
+                        GS_STAT_SET(st_hit);
+                        // render.cu:149-150: final_weight = 1.0 - acc and weight = alpha * (1.0 - acc), the literal
+                        // making both double expressions that are narrowed to float -- six fp64-rate instructions
+                        // per contributing visit when written that way.  acc is 0 or >= 1/255 here (it only grows,
+                        // and the first weight is an alpha >= 1/255), so 1.0 - (double)acc is EXACT; hence
+                        // (a) its narrowing is the correctly rounded float difference, i.e. the float subtraction;
+                        // (b) alpha (1 - acc) = alpha - alpha acc as real numbers, and one double fma rounds that
+                        // once, exactly as the reference's double multiplication rounds its exact operands.
+                        // Same bits, four fp64-rate instructions and one fp32.
+                        fw = 1.0f - acc;
+                        const float weight = (float)__builtin_fma((double)alpha, -(double)acc, (double)alpha);
+                        img[0] += r.g2.y * weight;
+                        img[1] += r.g2.z * weight;
+                        img[2] += r.g2.w * weight;
+                        acc += weight;
+                        if (acc > Thr<float>::sat_gt()) {   // saturated: the next splat's check fails
+                            nsp = base + i + 1;
+                        }
                     }
-                    visit(ra, cur);
-                    if (nxt < 0) break;
-                    cur = nxt;
-                    nxt = -1;
-                    if (m) {
-                        nxt = word * 64 + __builtin_ctzll(m);
-                        m &= m - 1;
-                        lds_record_fetch(ra, s_geom + nxt * GS_PACKED_WIDTH);
-                    }
-                    visit(rb, cur);
-                    if (nxt < 0) break;
-                    cur = nxt;
                 }
             }
-        } else {
-            for (int word = 0; word < NW && word * 64 < cnt; word++) {
-                if (ballot(!is_done()) == 0) break;   // wave-uniform: every pixel of the patch saturated
-                unsigned long long m = wave_uniform(s_mask[wave][word]);
-                while (m) {
-                    const int i = word * 64 + __builtin_ctzll(m);
-                    m &= m - 1;
-                    GS_STAT(2, 1);                        // visits (touch-mask bits walked)
-                    GS_STAT(6, __popcll(ballot(!is_done())));   // live lanes at the visit
-                    GS_STAT_FLAG(st_in);
-                    GS_STAT_FLAG(st_hit);
-                    if (!is_done()) {
-                        const T* rec = s_geom + i * GS_PACKED_WIDTH;
-                        const Vec4<T> g0 = *reinterpret_cast<const Vec4<T>*>(rec);   // u v r2 opacity
-                        const T du = pu - g0.x, dv = pv - g0.y;
-                        // beyond the cutoff radius alpha < 1/255 is certain: same outcome as :145-148
-                        if (!(fast && du * du + dv * dv > g0.z)) {
-                            GS_STAT_SET(st_in);
-                            const Vec4<T> g1 = *reinterpret_cast<const Vec4<T>*>(rec + 4);   // a b c det
-                            const Vec4<T> g2 = *reinterpret_cast<const Vec4<T>*>(rec + 8);   // 1/det, colour
-                            const T a = g1.x, b = g1.y, c = g1.z, det = g1.w;
-                            const T mh = div_by_reciprocal(c * du * du - (b + b) * du * dv + a * dv * dv, det, g2.x);
-                            T alpha = g0.w * exp_neg_half(mh);
-                            alpha = (mh > T(0)) ? alpha : T(0);                 // render.cu:133
-                            if (!(fast && alpha < Thr<T>::alpha_min())) {       // render.cu:145
-                                GS_STAT_SET(st_hit);
-                                fw = 1.0 - acc;
-                                const T weight = alpha * (1.0 - acc);           // double, narrowed
-                                T col[3];
-                                splat_colour<T, N_SH>(s_geom, s_col, i, Y, col);
-#pragma unroll
-                                for (int ch = 0; ch < 3; ch++) img[ch] += col[ch] * weight;
-                                acc += weight;
-                                if (acc > Thr<T>::sat_gt()) {   // saturated: the next splat's check fails
-                                    nsp = base + i + 1;
-                                }
-                            }
-                        }
-                    }
-                    GS_STAT(3, ballot(st_in) != 0);           // visits with a lane inside the cutoff circle
-                    GS_STAT(4, ballot(st_hit) != 0);          // visits with a contributing lane
-                    GS_STAT(5, __popcll(ballot(st_hit)));     // contributing (pixel, splat) pairs
+            GS_STAT(3, ballot(st_in) != 0);           // visits with a lane inside the cutoff circle
+            GS_STAT(4, ballot(st_hit) != 0);          // visits with a contributing lane
+            GS_STAT(5, __popcll(ballot(st_hit)));     // contributing (pixel, splat) pairs
+            GS_HALF_VISIT(ballot(st_in));
+        };
+        for (int word = 0; word < NW && word * 64 < cnt; word++) {
+            if constexpr (CK) {
+                // crossing into the next depth segment: leave the state at the boundary behind
+                const int sidx = min((base + word * 64) / SEG_LEN, SEG_MAX - 1);
+                if (sidx != b_cur && !wave_fin) {
+                    write_record();
+                    b_cur = sidx;
                 }
+            }
+            if (ballot(!is_done()) == 0) {   // wave-uniform: every pixel of the patch saturated
+                if constexpr (CK) {
+                    if (!wave_fin) write_record();
+                    wave_fin = true;
+                }
+                break;
+            }
+            unsigned long long m = wave_uniform(s_mask[wave][word]);
+            if (m == 0) continue;
+            LdsRecord ra, rb;
+            int cur = word * 64 + __builtin_ctzll(m), nxt;
+            m &= m - 1;
+            lds_record_fetch(ra, s_geom + cur * GS_PACKED_WIDTH);
+            while (true) {
+                nxt = -1;
+                if (m) {
+                    nxt = word * 64 + __builtin_ctzll(m);
+                    m &= m - 1;
+                    lds_record_fetch(rb, s_geom + nxt * GS_PACKED_WIDTH);
+                }
+                visit(ra, cur);
+                if (nxt < 0) break;
+                cur = nxt;
+                nxt = -1;
+                if (m) {
+                    nxt = word * 64 + __builtin_ctzll(m);
+                    m &= m - 1;
+                    lds_record_fetch(ra, s_geom + nxt * GS_PACKED_WIDTH);
+                }
+                visit(rb, cur);
+                if (nxt < 0) break;
+                cur = nxt;
             }
         }
         GS_PHASE(2);
@@ -959,19 +912,19 @@ __device__ __forceinline__ void render_tile_fwd(
         if (valid) {
             // the pixel's last contributor once more, in the BACKWARD's arithmetic (k_render_bwd: alpha from
             // mh * (1 / det), capped at 0.9999): what its first step does to weight and colour_accum
-            T oma_last = 1, bgw = 0;
+            float oma_last = 1, bgw = 0;
             if (kend > 0) {
                 const int g = sorted[s0 + kend - 1];
-                const Vec4<T>* rec = reinterpret_cast<const Vec4<T>*>(packed + (size_t)g * GS_PACKED_WIDTH);
-                const Vec4<T> g0 = rec[0], g1 = rec[1], g2 = rec[2];
-                const T du = pu - g0.x, dv = pv - g0.y;
-                const T mh = (g1.z * du * du - (g1.y + g1.y) * du * dv + g1.x * dv * dv) * g2.x;
-                const T e = exp_neg_half(mh);
-                T alpha = g0.w * ((mh > T(0)) ? e : T(0));
-                if (alpha > Thr<T>::sat_gt()) alpha = Thr<T>::alpha_cap();
-                const T bw = background_weight<T>(alpha, fw);   // render_backward.cu:172-181
-                if (bw > Thr<T>::bgw_gt()) bgw = bw;
-                oma_last = T(1) - alpha;
+                const Vec4<float>* rec = reinterpret_cast<const Vec4<float>*>(packed + (size_t)g * GS_PACKED_WIDTH);
+                const Vec4<float> g0 = rec[0], g1 = rec[1], g2 = rec[2];
+                const float du = pu - g0.x, dv = pv - g0.y;
+                const float mh = (g1.z * du * du - (g1.y + g1.y) * du * dv + g1.x * dv * dv) * g2.x;
+                const float e = exp_neg_half(mh);
+                float alpha = g0.w * ((mh > 0.0f) ? e : 0.0f);
+                if (alpha > Thr<float>::sat_gt()) alpha = Thr<float>::alpha_cap();
+                const float bw = background_weight<float>(alpha, fw);   // render_backward.cu:172-181
+                if (bw > Thr<float>::bgw_gt()) bgw = bw;
+                oma_last = 1.0f - alpha;
             }
             const size_t p = (size_t)px.v * W + px.u - seg.pix0;
             seg.kend[p] = kend;
@@ -979,6 +932,131 @@ __device__ __forceinline__ void render_tile_fwd(
             seg.bgw[p] = bgw;
         }
     }
+    if (valid) {
+        if (acc < Thr<float>::bg_lt()) {   // render.cu:169
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) img[ch] += bg[ch] * (1.0 - acc);
+        }
+        const size_t p = (size_t)px.v * W + px.u;
+        nsp_out[p] = nsp;
+        fw_out[p] = fw;
+        image[p * 3 + 0] = img[0];
+        image[p * 3 + 1] = img[1];
+        image[p * 3 + 2] = img[2];
+    }
+}
+
+// The general forward: fp64, and fp32 with per-pixel SH (N_SH > 1: the colour is evaluated from the staged
+// coefficients at the pixel's view direction).  Plain walk of the touch masks, one record read per visit; whole
+// lists, no flags, no hand-over to a backward.  In fp32 (fast_mode) the cutoff radius and the 1/255 threshold
+// skip what cannot contribute; fp64 evaluates every visit as render.cu does.
+template <typename T, int N_SH>
+__device__ __forceinline__ void render_tile_fwd_general(
+    const int tile, const T* __restrict__ packed, const T* __restrict__ rgb,
+    const T* __restrict__ view_dir, const int* __restrict__ ranges, const int* __restrict__ sorted,
+    const T* __restrict__ bg, int W, int H, int ntx, int* __restrict__ nsp_out,
+    T* __restrict__ fw_out, T* __restrict__ image, const T* __restrict__ src_opacity,
+    const T* __restrict__ src_conic) {
+    static_assert(!(sizeof(T) == 4 && N_SH == 1), "fp32 with one coefficient is render_tile_fwd_fused");
+    constexpr int CW = ColW<N_SH>::value;
+    constexpr int RCHUNK = Chunk<T, N_SH>::value;
+    __shared__ alignas(16) T s_geom[RCHUNK * GS_PACKED_WIDTH];
+    __shared__ alignas(16) T s_col[N_SH > 1 ? RCHUNK * CW : 4];
+
+    const int tid = threadIdx.x;
+    const PixelMap px = pixel_of_thread(tile % ntx, tile / ntx, tid);
+    const bool valid = px.u < W && px.v < H;
+    const int s0 = ranges[tile];
+    const int n_tile = ranges[tile + 1] - s0;
+
+    T Y[N_SH];
+    if constexpr (N_SH > 1) {
+        T d[3] = {0, 0, 0};
+        if (valid) {
+            const T* vd = view_dir + ((size_t)px.v * W + px.u) * 3;
+            d[0] = vd[0]; d[1] = vd[1]; d[2] = vd[2];
+        }
+        sh_basis<T, N_SH>(d, Y);
+    } else {
+        Y[0] = T(GS_SH_0);
+    }
+
+    // A pixel is done when its accumulated alpha exceeds 0.9999 (render.cu:146,162) -- or when it lies outside the
+    // image: those lanes start saturated.  acc of an outside lane is never used (nothing is stored).
+    T acc = valid ? T(0) : T(2), fw = 0;
+    auto is_done = [&]() { return acc > Thr<T>::sat_gt(); };
+    T img[3] = {0, 0, 0};
+    // num_splats_per_pixel == index of the first splat at whose turn the pixel is saturated
+    // (render.cu:106,146,162), or the list length: set when the pixel saturates
+    int nsp = n_tile;
+    const T pu = T(px.u), pv = T(px.v);
+    const int wave = tid >> 6;
+    constexpr int NW = RCHUNK / 64 > 0 ? RCHUNK / 64 : 1;
+    __shared__ unsigned long long s_mask[4][NW];
+
+    GS_STAT_DECL;
+    GS_STAT(0, 1);          // waves
+    GS_STAT(7, n_tile);     // list entries of the wave's tile
+    for (int base = 0; base < n_tile; base += RCHUNK) {
+        const int cnt = min(RCHUNK, n_tile - base);
+        GS_STAT(1, 1);      // chunks
+        GS_STAT(8, cnt);    // list entries staged
+        stage_chunk<T, N_SH>(packed, rgb, sorted, s0 + base, cnt, tid, s_geom, s_col, nullptr, src_opacity, src_conic);
+        GS_PHASE(0);
+        // (no barrier in between: thread t tests the record thread t staged)
+        build_touch_masks<T, RCHUNK>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
+        __syncthreads();
+        GS_PHASE(1);
+        for (int word = 0; word < NW && word * 64 < cnt; word++) {
+            if (ballot(!is_done()) == 0) break;   // wave-uniform: every pixel of the patch saturated
+            unsigned long long m = wave_uniform(s_mask[wave][word]);
+            while (m) {
+                const int i = word * 64 + __builtin_ctzll(m);
+                m &= m - 1;
+                GS_STAT(2, 1);                        // visits (touch-mask bits walked)
+                GS_STAT(6, __popcll(ballot(!is_done())));   // live lanes at the visit
+                GS_STAT_FLAG(st_in);
+                GS_STAT_FLAG(st_hit);
+                if (!is_done()) {
+                    const T* rec = s_geom + i * GS_PACKED_WIDTH;
+                    const Vec4<T> g0 = *reinterpret_cast<const Vec4<T>*>(rec);   // u v r2 opacity
+                    const T du = pu - g0.x, dv = pv - g0.y;
+                    // beyond the cutoff radius alpha < 1/255 is certain: same outcome as :145-148
+                    if (!(fast_mode<T>() && du * du + dv * dv > g0.z)) {
+                        GS_STAT_SET(st_in);
+                        const Vec4<T> g1 = *reinterpret_cast<const Vec4<T>*>(rec + 4);   // a b c det
+                        const Vec4<T> g2 = *reinterpret_cast<const Vec4<T>*>(rec + 8);   // 1/det, colour
+                        const T a = g1.x, b = g1.y, c = g1.z, det = g1.w;
+                        const T mh = div_by_reciprocal(c * du * du - (b + b) * du * dv + a * dv * dv, det, g2.x);
+                        T alpha = g0.w * exp_neg_half(mh);
+                        alpha = (mh > T(0)) ? alpha : T(0);                 // render.cu:133
+                        if (!(fast_mode<T>() && alpha < Thr<T>::alpha_min())) {       // render.cu:145
+                            GS_STAT_SET(st_hit);
+                            fw = 1.0 - acc;
+                            const T weight = alpha * (1.0 - acc);           // double, narrowed
+                            T col[3];
+                            splat_colour<T, N_SH>(s_geom, s_col, i, Y, col);
+#pragma unroll
+                            for (int ch = 0; ch < 3; ch++) img[ch] += col[ch] * weight;
+                            acc += weight;
+                            if (acc > Thr<T>::sat_gt()) {   // saturated: the next splat's check fails
+                                nsp = base + i + 1;
+                            }
+                        }
+                    }
+                }
+                GS_STAT(3, ballot(st_in) != 0);           // visits with a lane inside the cutoff circle
+                GS_STAT(4, ballot(st_hit) != 0);          // visits with a contributing lane
+                GS_STAT(5, __popcll(ballot(st_hit)));     // contributing (pixel, splat) pairs
+            }
+        }
+        GS_PHASE(2);
+        const bool all_done = __syncthreads_and(is_done());
+        GS_PHASE(3);
+        if (all_done) break;
+    }
+    GS_STAT_FLUSH(0);
+
     if (valid) {
         if (acc < Thr<T>::bg_lt()) {   // render.cu:169
 #pragma unroll
@@ -993,6 +1071,8 @@ __device__ __forceinline__ void render_tile_fwd(
     }
 }
 
+// the fused renderer's forward: whole frame, prefix mode or depth-cut lists.  (The parameter list is the one every
+// fp32 / fp64, 1..16-coefficient forward had while they were one kernel: view_dir is unused.)
 template <typename T, int N_SH>
 __global__ __launch_bounds__(RB) void k_render_fwd(
     const T* __restrict__ packed, const T* __restrict__ rgb, const T* __restrict__ view_dir,
@@ -1001,11 +1081,24 @@ __global__ __launch_bounds__(RB) void k_render_fwd(
     T* __restrict__ image, int sort_prefix, int* __restrict__ tile_flags, int64_t cap,
     int* __restrict__ tile_cost, const T* __restrict__ src_opacity, const T* __restrict__ src_conic,
     const int* __restrict__ full_ranges, int* __restrict__ flag_counter, unsigned long long* __restrict__ touch_masks) {
+    static_assert(sizeof(T) == 4 && N_SH == 1, "the fused fp32 kernel; everything else goes to k_render_fwd_general");
     const int t_local = tile_of_block(blockIdx.x, nt);
     if (t_local >= nt) return;
-    render_tile_fwd<T, N_SH>(tile0 + t_local, packed, rgb, view_dir, ranges, sorted, bg, W, H, ntx,
-                             nsp_out, fw_out, image, sort_prefix, tile_flags, false, cap, tile_cost, src_opacity,
-                             src_conic, SEG_NONE, full_ranges, flag_counter, touch_masks);
+    render_tile_fwd_fused<false>(tile0 + t_local, packed, rgb, ranges, sorted, bg, W, H, ntx,
+                                 nsp_out, fw_out, image, sort_prefix, tile_flags, false, cap, tile_cost, src_opacity,
+                                 src_conic, SEG_NONE, full_ranges, flag_counter, touch_masks);
+}
+
+template <typename T, int N_SH>
+__global__ __launch_bounds__(RB) void k_render_fwd_general(
+    const T* __restrict__ packed, const T* __restrict__ rgb, const T* __restrict__ view_dir,
+    const int* __restrict__ ranges, const int* __restrict__ sorted, const T* __restrict__ bg,
+    int W, int H, int ntx, int tile0, int nt, int* __restrict__ nsp_out, T* __restrict__ fw_out,
+    T* __restrict__ image, const T* __restrict__ src_opacity, const T* __restrict__ src_conic) {
+    const int t_local = tile_of_block(blockIdx.x, nt);
+    if (t_local >= nt) return;
+    render_tile_fwd_general<T, N_SH>(tile0 + t_local, packed, rgb, view_dir, ranges, sorted, bg, W, H, ntx,
+                                     nsp_out, fw_out, image, src_opacity, src_conic);
 }
 
 // the fused renderer's forward that also leaves the state for the depth-segmented backward
@@ -1020,9 +1113,9 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(GS_FWD_CK_WA
     unsigned long long* __restrict__ touch_masks) {
     const int t_local = tile_of_block(blockIdx.x, nt);
     if (t_local >= nt) return;
-    render_tile_fwd<float, 1, true>(tile0 + t_local, packed, rgb, nullptr, ranges, sorted, bg, W, H, ntx, nsp_out,
-                                    fw_out, image, sort_prefix, tile_flags, false, cap, tile_cost, nullptr, nullptr,
-                                    seg, nullptr, nullptr, touch_masks);
+    render_tile_fwd_fused<true>(tile0 + t_local, packed, rgb, ranges, sorted, bg, W, H, ntx, nsp_out,
+                                fw_out, image, sort_prefix, tile_flags, false, cap, tile_cost, nullptr, nullptr,
+                                seg, nullptr, nullptr, touch_masks);
 }
 
 // repair pass of the prefix mode / of the depth cut, ONE launch: a small grid walks the flags; a flagged tile's list is
@@ -1064,9 +1157,9 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(GS_FWD_CK_WA
             }
             __syncthreads();   // the list is in place for every thread of the workgroup (workgroup-scope fence + barrier)
         }
-        render_tile_fwd<float, 1, CK>(tile, packed, rgb, nullptr, ranges, sorted, bg, W, H, ntx,
-                                      nsp_out, fw_out, image, 0, tile_flags, true, cap, tile_cost, nullptr, nullptr,
-                                      seg, nullptr, nullptr, touch_masks);
+        render_tile_fwd_fused<CK>(tile, packed, rgb, ranges, sorted, bg, W, H, ntx,
+                                  nsp_out, fw_out, image, 0, tile_flags, true, cap, tile_cost, nullptr, nullptr,
+                                  seg, nullptr, nullptr, touch_masks);
         __syncthreads();
     }
 }
@@ -1079,6 +1172,19 @@ template <bool CK> static void repair_attr_once() {
     if ((seen.fetch_or(bit) & bit) == 0)
         (void)hipFuncSetAttribute((const void*)k_render_fwd_flagged<CK>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)sort_lds_bytes(SORT_MAX_LDS_KEYS));
+}
+// the repair launch: at most 512 workgroups walk the flags of the nt tiles from tile0 on, `lds` bytes for the sort
+template <bool CK>
+static void launch_render_fwd_flagged(
+    hipStream_t s, size_t lds, const void* packed, const void* rgb, const int* ranges, int* sorted, const void* bg, int W,
+    int H, int ntx, int tile0, int nt, int* nsp_out, void* fw_out, void* image, int* tile_flags, int64_t cap,
+    int* tile_cost, const SegState seg, const int* flag_counter, int* host_flagged, uint64_t* sort_keys,
+    int sort_prefix, int sort_beyond, uint64_t* touch_masks) {
+    repair_attr_once<CK>();
+    k_render_fwd_flagged<CK><<<nt < 512 ? nt : 512, RB, lds, s>>>(
+        (const float*)packed, (const float*)rgb, ranges, sorted, (const float*)bg, W, H, ntx, tile0, nt, nsp_out,
+        (float*)fw_out, (float*)image, tile_flags, cap, tile_cost, seg, flag_counter, host_flagged, sort_keys,
+        sort_prefix, sort_beyond, (unsigned long long*)touch_masks);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1947,6 +2053,19 @@ static int resolve_backward_mode(int mode, int* exact) {
     return GS_OK;
 }
 
+// the general forward of one (dtype, coefficient count).  fp32 with one coefficient never gets here (launch_render_fwd
+// launches the fused kernel itself), but DISPATCH_SH names that pair too and k_render_fwd_general refuses it
+template <typename T, int N_SH>
+static void launch_render_fwd_general(hipStream_t s, int grid, const void* packed_or_uvs, const void* opacity,
+                                      const void* conic, const void* rgb, const void* view_dir, const int* ranges,
+                                      const int* sorted, const void* bg, int W, int H, int ntx, int tile0, int nt,
+                                      int* nsp_out, void* fw_out, void* image) {
+    if constexpr (!(sizeof(T) == 4 && N_SH == 1))
+        k_render_fwd_general<T, N_SH><<<grid, RB, 0, s>>>(
+            (const T*)packed_or_uvs, (const T*)rgb, (const T*)view_dir, ranges, sorted, (const T*)bg, W, H, ntx, tile0,
+            nt, nsp_out, (T*)fw_out, (T*)image, (const T*)opacity, (const T*)conic);
+}
+
 extern "C" {
 
 int gs_set_backward_mode(int mode) {
@@ -2006,14 +2125,18 @@ static int launch_render_fwd(const void* packed_or_uvs, const void* opacity, con
             seg_state_of(segment_state, W, H, tile_row0, tile_row1), nullptr);
         return check_launch("render_tiles");
     }
-    DISPATCH_T(dtype, DISPATCH_SH(n_sh, (k_render_fwd<T, N_SH><<<grid, RB, 0, s>>>(
-                                            (const T*)packed_or_uvs, (const T*)rgb,
-                                            (const T*)view_dir_by_pixel, tile_ranges,
-                                            sorted_gaussians, (const T*)background_rgb, W, H, ntx,
-                                            tile_row0 * ntx, nt, num_splats_per_pixel,
-                                            (T*)final_weight_per_pixel, (T*)image, 0,
-                                            nullptr, INT64_MAX, nullptr, (const T*)opacity, (const T*)conic, nullptr,
-                                            nullptr, nullptr))));
+    if (dtype == GS_F32 && n_sh == 1) {   // the fused renderer's kernel on whole lists: no prefix, flags, cost or hand-over
+        k_render_fwd<float, 1><<<grid, RB, 0, s>>>(
+            (const float*)packed_or_uvs, (const float*)rgb, nullptr, tile_ranges, sorted_gaussians,
+            (const float*)background_rgb, W, H, ntx, tile_row0 * ntx, nt, num_splats_per_pixel,
+            (float*)final_weight_per_pixel, (float*)image, 0, nullptr, INT64_MAX, nullptr, (const float*)opacity,
+            (const float*)conic, nullptr, nullptr, nullptr);
+        return check_launch("render_tiles");
+    }
+    DISPATCH_T(dtype, DISPATCH_SH(n_sh, (launch_render_fwd_general<T, N_SH>(
+                                            s, grid, packed_or_uvs, opacity, conic, rgb, view_dir_by_pixel, tile_ranges,
+                                            sorted_gaussians, background_rgb, W, H, ntx, tile_row0 * ntx, nt,
+                                            num_splats_per_pixel, final_weight_per_pixel, image))));
     return check_launch("render_tiles");
 }
 
@@ -2089,19 +2212,10 @@ int gs_render_tiles_prefix_phased_m(const void* packed, const void* rgb, const i
     if ((phases & GS_PREFIX_REPAIR) && S > GS_SORT_PREFIX) {
         // 2. flagged tiles: full sort + render again, one launch (exits at once on a dense scene)
         const size_t lds = sort_lds_bytes(S <= 4096 ? 4096 : SORT_MAX_LDS_KEYS);
-        if (segment_state) {
-            repair_attr_once<true>();
-            k_render_fwd_flagged<true><<<nt < 512 ? nt : 512, RB, lds, s>>>(
-                (const float*)packed, (const float*)rgb, tile_ranges, sorted_gaussians, (const float*)background_rgb, W, H, ntx,
-                t0, nt, num_splats_per_pixel, (float*)final_weight_per_pixel, (float*)image, tile_flags, S, tile_cost, seg,
-                nullptr, nullptr, const_cast<uint64_t*>(keys), GS_SORT_PREFIX, 0, (unsigned long long*)touch_masks);
-        } else {
-            repair_attr_once<false>();
-            k_render_fwd_flagged<false><<<nt < 512 ? nt : 512, RB, lds, s>>>(
-                (const float*)packed, (const float*)rgb, tile_ranges, sorted_gaussians, (const float*)background_rgb, W, H, ntx,
-                t0, nt, num_splats_per_pixel, (float*)final_weight_per_pixel, (float*)image, tile_flags, S, tile_cost, seg,
-                nullptr, nullptr, const_cast<uint64_t*>(keys), GS_SORT_PREFIX, 0, (unsigned long long*)touch_masks);
-        }
+        const auto repair = segment_state ? launch_render_fwd_flagged<true> : launch_render_fwd_flagged<false>;
+        repair(s, lds, packed, rgb, tile_ranges, sorted_gaussians, background_rgb, W, H, ntx, t0, nt, num_splats_per_pixel,
+               final_weight_per_pixel, image, tile_flags, S, tile_cost, seg, nullptr, nullptr,
+               const_cast<uint64_t*>(keys), GS_SORT_PREFIX, 0, touch_masks);
     }
     return check_launch("render_tiles_prefix");
 }
@@ -2143,11 +2257,10 @@ int gs_render_tiles_cut_m(const void* packed, const void* rgb, const int32_t* ti
     if (int e = depth_cut_repair((const float*)bin_records, N, ntx, nty, mh_dist, tile_row0, tile_row1, full_ranges, workspace,
                                  cut_workspace, overflow_keys, overflow_capacity, overflow_sorted, tile_flags, s, false))
         return e;
-    repair_attr_once<false>();
-    k_render_fwd_flagged<false><<<nt < 512 ? nt : 512, RB, sort_lds_bytes(SORT_MAX_LDS_KEYS), s>>>(
-        (const float*)packed, (const float*)rgb, full_ranges, overflow_sorted, (const float*)background_rgb, W, H, ntx, t0,
-        nt, num_splats_per_pixel, (float*)final_weight_per_pixel, (float*)image, tile_flags, overflow_capacity, tile_cost,
-        SEG_NONE, flag_counter, host_flagged, overflow_keys, 0, 1, (unsigned long long*)touch_masks);
+    launch_render_fwd_flagged<false>(s, sort_lds_bytes(SORT_MAX_LDS_KEYS), packed, rgb, full_ranges, overflow_sorted,
+                                     background_rgb, W, H, ntx, t0, nt, num_splats_per_pixel, final_weight_per_pixel, image,
+                                     tile_flags, overflow_capacity, tile_cost, SEG_NONE, flag_counter, host_flagged,
+                                     overflow_keys, 0, 1, touch_masks);
     return check_launch("render_tiles_cut");
 }
 

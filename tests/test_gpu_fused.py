@@ -816,3 +816,54 @@ def test_packed_render_entry_points_equal_the_reference_signature_ones(deg):
     assert torch.equal(img_a, img0.detach())
     for a, b in zip(ga, gb):
         assert scaled_err(b, a) < 2e-6
+
+
+@pytest.mark.parametrize("dtype,n_sh", [(torch.float32, 16), (torch.float64, 1), (torch.float64, 16)])
+def test_general_forward_staging_forms_and_bands(dtype, n_sh):
+    """k_render_fwd_general (every forward but fp32 with one coefficient) rendered three ways: gs_render_tiles on the
+    separate arrays (record formed while staging), gs_render_tiles_packed on records of gs_pack_splats, and the latter
+    in two calls over the tile rows [0, 1) and [1, nty) into one set of buffers.  The same kernel on the same record
+    values, no atomics: num_splats, final weight and image bit-equal.  faint_300: one tile, 300 faint splats that no
+    pixel saturates on (the CPU oracle walks all 300 at every pixel) -- 5 chunks of 64 with a partial last one at 16
+    coefficients, 256 + 44 in fp64 with one.  partial_48x40: 3 x 3 tiles, partial right and bottom tiles, empty tiles
+    and single-entry ones."""
+    import ctypes
+
+    from gaussian_splatting_amd import _hip
+
+    from . import render_ref64 as R
+    gs_dtype = _hip.GS_F32 if dtype == torch.float32 else _hip.GS_F64
+    p = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
+    stream = _hip.current_stream()
+    for name in ("faint_300", "partial_48x40"):
+        sc = R.render_scenes()[name]
+        W, H, V, nty = sc.W, sc.H, sc.V, (sc.H + 15) // 16
+        rays = (sc.rays if n_sh > 1 else torch.zeros(1, 1, 1)).to(dtype)
+        uv, opa, coeff, conic, bg = (x.to(dtype).contiguous() for x in (sc.uv, sc.opacity, R.scene_coeff(sc, n_sh),
+                                                                        sc.conic, sc.bg))
+        if name == "faint_300":
+            nsp, fw, img = torch.zeros(H, W, dtype=torch.int32), torch.zeros(H, W, dtype=dtype), torch.zeros(H, W, 3, dtype=dtype)
+            oracle().render_tiles_cuda(uv, opa, coeff, conic, rays, sc.ranges, sc.sorted_g, bg, nsp, fw, img)
+            assert (nsp == 300).all()   # the last, partial chunk is reached by every pixel
+        uv, opa, coeff, conic, bg, rays, ranges, sorted_g = (x.to(DEV) for x in (uv, opa, coeff, conic, bg, rays, sc.ranges,
+                                                                                 sc.sorted_g))
+
+        def outputs():
+            return (torch.zeros(H, W, dtype=torch.int32, device=DEV), torch.zeros(H, W, dtype=dtype, device=DEV),
+                    torch.zeros(H, W, 3, dtype=dtype, device=DEV))
+
+        nsp_a, fw_a, img_a = outputs()
+        _hip.call("gs_render_tiles", p(uv), p(opa), p(coeff), p(conic), p(rays), p(ranges), p(sorted_g), p(bg), p(nsp_a),
+                  p(fw_a), p(img_a), W, H, n_sh, 0, nty, gs_dtype, stream)
+        packed = torch.empty(V, 12, dtype=dtype, device=DEV)
+        _hip.call("gs_pack_splats", p(uv), p(opa), p(conic), p(coeff if n_sh == 1 else None), V, p(packed), gs_dtype, stream)
+        nsp_b, fw_b, img_b = outputs()
+        _hip.call("gs_render_tiles_packed", p(packed), p(coeff), p(rays), p(ranges), p(sorted_g), p(bg), W, H, n_sh, 0, nty,
+                  p(nsp_b), p(fw_b), p(img_b), gs_dtype, None, stream)
+        nsp_c, fw_c, img_c = outputs()
+        for row0, row1 in ((0, 1), (1, nty)):
+            _hip.call("gs_render_tiles_packed", p(packed), p(coeff), p(rays), p(ranges), p(sorted_g), p(bg), W, H, n_sh, row0,
+                      row1, p(nsp_c), p(fw_c), p(img_c), gs_dtype, None, stream)
+        assert int(nsp_a.max()) > 0 and bool(img_a.any())
+        for got in ((nsp_b, fw_b, img_b), (nsp_c, fw_c, img_c)):
+            assert torch.equal(nsp_a, got[0]) and torch.equal(fw_a, got[1]) and torch.equal(img_a, got[2]), name
