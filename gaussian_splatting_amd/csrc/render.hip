@@ -33,15 +33,18 @@
 // ordered; the fused forward reads no further, raises tile_flags[t] if a pixel is still unsaturated there,
 // and k_render_fwd_flagged renders such tiles again after their full sort -- results are exact.
 //
-// Backward: two kernels.  Both start at the tile's largest num_splats_per_pixel instead of the end of the list and
-// skip the reduction for waves none of whose lanes the splat reaches.
-//   k_render_bwd<float, N_SH>, every fp32 backward (the fused renderer's is <float, 1>): sums nine per-splat values
-//   over the wave with a transposing DPP / permlane-swap reduction into a wave-private LDS slot (plain store, no LDS
-//   atomics); the flush adds the four waves' slots and issues the global atomics nine lanes per 36-byte row (of the
-//   [V, 9] slab, or of the separate gradient arrays).  With per-pixel SH (N_SH > 1) the colour-coefficient gradients
-//   leave the slots: a matrix-core contraction over the wave's 64 pixels per batch of 16 contributing splats (SHMM).
-//   It alone carries the fused frame's depth segments, depth-cut overflow lists, handed-over touch masks and the
-//   longest-first tile order (durations the forward measured; k_bwd_prologue: tile_order_body).
+// Backward: three kernels, each with its walk written out.  All start at the tile's largest num_splats_per_pixel
+// instead of the end of the list and skip the reduction for waves none of whose lanes the splat reaches.
+//   k_render_bwd<float, 1>, fp32 with one colour coefficient -- the fused renderer's, and what gs_render_tiles_backward /
+//   _packed run for float32 with n_sh == 1: sums nine per-splat values over the wave with a transposing DPP /
+//   permlane-swap reduction into a wave-private LDS slot (plain store, no LDS atomics); the flush adds the four waves'
+//   slots and issues the global atomics nine lanes per 36-byte row (of the [V, 9] slab, or of the separate gradient
+//   arrays).  It alone carries the fused frame's depth segments, depth-cut overflow lists, handed-over touch masks and
+//   the longest-first tile order (durations the forward measured; k_bwd_prologue: tile_order_body).
+//   k_render_bwd_sh<N_SH>, fp32 with per-pixel SH (4 / 9 / 16 coefficients): the same slots for the six geometric sums,
+//   whole lists, separate gradient arrays; the colour is evaluated at the pixel's view direction and the
+//   colour-coefficient gradients are a matrix-core contraction over the wave's 64 pixels per batch of 16 contributing
+//   splats.
 //   k_render_bwd_ref<N_SH>, fp64 (gradcheck and the fp64 parity tests): one shared LDS row of 3 N_SH + 6 sums per
 //   staged splat, shuffle wave sums + one LDS atomic per value per visit, one global atomic per value per
 //   (splat, tile) -- the reference issues eight (one per warp), unconditionally.
@@ -317,8 +320,8 @@ template <> __device__ __forceinline__ double background_weight<double>(double a
 
 // a register the compiler must treat as defined without an instruction that defines it (its content is whatever the
 // lane held): for values only SOME lanes compute and the others are masked out of afterwards
-template <typename T> __device__ __forceinline__ T unset() {
-    T x;
+__device__ __forceinline__ float unset() {
+    float x;
     asm volatile("" : "=v"(x));
     return x;
 }
@@ -329,7 +332,6 @@ __device__ __forceinline__ float mul_zero_wins(float a, float b) {
     asm("v_mul_legacy_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-__device__ __forceinline__ double mul_zero_wins(double a, double b) { return b == 0.0 ? 0.0 : a * b; }
 
 template <typename T> __device__ inline T tmin(T a, T b) { return b < a ? b : a; }
 template <typename T> __device__ inline T tmax(T a, T b) { return b > a ? b : a; }
@@ -421,46 +423,47 @@ __device__ inline void build_touch_masks(const T* s_geom, int cnt, int tid, int 
 // the barrier (the masks were 9 % of the backward's wave time, profiles/r04/wave_timeline_D.json).  Every
 // (record, patch) pair is tested with the very expressions of build_touch_masks: the same bits.  The records must be
 // visible to all waves (barrier after staging).
-template <typename T>
-__device__ inline void build_touch_masks_by_patch(const T* s_geom, int cnt, int tid, int tile_x, int tile_y,
-                                                  unsigned long long (*s_mask)[1]) {
+// (NWORD: the mask words per patch of the caller's array -- 1 at the 64-entry chunk this is for; word 0 is written)
+template <int NWORD>
+__device__ inline void build_touch_masks_by_patch(const float* s_geom, int cnt, int tid, int tile_x, int tile_y,
+                                                  unsigned long long (*s_mask)[NWORD]) {
     const int r = tid & 63, p = tid >> 6;
     bool hit = false;
     if (r < cnt) {
-        const T* rec = s_geom + r * GS_PACKED_WIDTH;
-        const T u = rec[0], v = rec[1], r2 = rec[2];
+        const float* rec = s_geom + r * GS_PACKED_WIDTH;
+        const float u = rec[0], v = rec[1], r2 = rec[2];
         bool use_q = false;
-        T a = 0, b = 0, c = 0, rdet = 0, tau_m = 0, b_over_a = 0, b_over_c = 0;
-        if (fast_mode<T>() && r2 > T(0) && r2 < T(1e30)) {
+        float a = 0, b = 0, c = 0, rdet = 0, tau_m = 0, b_over_a = 0, b_over_c = 0;
+        if (r2 > 0.0f && r2 < 1e30f) {
             a = rec[4]; b = rec[5]; c = rec[6]; rdet = rec[8];
-            const T half = T(0.5) * (a + c);
-            const T lmax = half + fast_sqrt(T(0.25) * (a - c) * (a - c) + b * b);
-            tau_m = (r2 * fast_rcp(lmax)) * T(1.001);
-            use_q = a > T(0) && c > T(0) && rdet > T(0);
+            const float half = 0.5f * (a + c);
+            const float lmax = half + fast_sqrt(0.25f * (a - c) * (a - c) + b * b);
+            tau_m = (r2 * fast_rcp(lmax)) * 1.001f;
+            use_q = a > 0.0f && c > 0.0f && rdet > 0.0f;
             b_over_a = b * fast_rcp(a);
             b_over_c = b * fast_rcp(c);
         }
-        const T x0 = T(tile_x * 16 + ((p & 1) << 3)), y0 = T(tile_y * 16 + ((p >> 1) << 3));
-        const T x1 = x0 + T(7), y1 = y0 + T(7);
-        T dx = T(0), dy = T(0);
+        const float x0 = float(tile_x * 16 + ((p & 1) << 3)), y0 = float(tile_y * 16 + ((p >> 1) << 3));
+        const float x1 = x0 + 7.0f, y1 = y0 + 7.0f;
+        float dx = 0.0f, dy = 0.0f;
         if (u < x0) dx = x0 - u;
         if (u > x1) dx = x1 - u;
         if (v < y0) dy = y0 - v;
         if (v > y1) dy = y1 - v;
         hit = !(dx * dx + dy * dy > r2);
-        if (hit && use_q && (dx != T(0) || dy != T(0))) {
-            const T X0 = x0 - u, X1 = x1 - u, Y0 = y0 - v, Y1 = y1 - v;
-            T qmin = T(3.0e38);
+        if (hit && use_q && (dx != 0.0f || dy != 0.0f)) {
+            const float X0 = x0 - u, X1 = x1 - u, Y0 = y0 - v, Y1 = y1 - v;
+            float qmin = 3.0e38f;
 #pragma unroll
             for (int e = 0; e < 2; e++) {
-                const T X = e ? X1 : X0;
-                T yy = b_over_a * X;
-                yy = tmin<T>(tmax<T>(yy, Y0), Y1);
-                qmin = tmin<T>(qmin, (c * X * X - T(2) * b * X * yy + a * yy * yy) * rdet);
-                const T Y = e ? Y1 : Y0;
-                T xx = b_over_c * Y;
-                xx = tmin<T>(tmax<T>(xx, X0), X1);
-                qmin = tmin<T>(qmin, (c * xx * xx - T(2) * b * xx * Y + a * Y * Y) * rdet);
+                const float X = e ? X1 : X0;
+                float yy = b_over_a * X;
+                yy = tmin(tmax(yy, Y0), Y1);
+                qmin = tmin(qmin, (c * X * X - 2.0f * b * X * yy + a * yy * yy) * rdet);
+                const float Y = e ? Y1 : Y0;
+                float xx = b_over_c * Y;
+                xx = tmin(tmax(xx, X0), X1);
+                qmin = tmin(qmin, (c * xx * xx - 2.0f * b * xx * Y + a * Y * Y) * rdet);
             }
             hit = !(qmin > tau_m);
         }
@@ -1293,7 +1296,7 @@ __device__ __forceinline__ void reduce9_to_slot(const float* val, bool stores, f
 // ---------------------------------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------------------------------
-// The fp32 kernel.  At most 7 waves per SIMD (no minimum: the per-pixel-SH instantiations sit far below).  Squeezed into the 64
+// The fp32 kernels.  At most 7 waves per SIMD (no minimum: k_render_bwd_sh sits far below).  Squeezed into the 64
 // registers of 8 waves, k_render_bwd<float, 1> reloads a coefficient of the exponential in every visit; with the 72
 // of 7 it stays resident (104 -> 103 vector instructions per visit, 0.4506 -> 0.4466 ms at D alternating on one box),
 // and the kernel never held 8 waves anyway (5-7).
@@ -1302,6 +1305,18 @@ __device__ __forceinline__ void reduce9_to_slot(const float* val, bool stores, f
 #else
 #define GS_BWD_OCC __attribute__((amdgpu_waves_per_eu(1, 7)))
 #endif
+//
+// k_render_bwd<float, 1>: the fused renderer's backward, fp32 with one colour coefficient per channel (the record's
+// colour is Y0 * coefficient; per-pixel SH is k_render_bwd_sh, fp64 k_render_bwd_ref).  Three launches:
+//   launch_render_bwd (gs_render_tiles_backward / _packed, float32, n_sh == 1): whole lists in grid order into the four
+//     separate gradient arrays (slab == 0), records staged from packed ones or from the reference's separate arrays
+//     (src_opacity / src_conic);
+//   gs_render_tiles_backward_slab: into the [V, 9] slab, tiles in tile_order (longest first) when given, depth-cut
+//     overflow lists and handed-over touch masks when given;
+//   the same with segment_state: work items (tile, depth segment), each resuming the pixels' walks from the state the
+//     forward left (SegState).
+// The template header and the full parameter list (view_dir: unused) are kept: profiles and scripts know the kernel
+// under this name, and its argument layout is the one they recorded.
 template <typename T, int N_SH>
 __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
     const T* __restrict__ packed, const T* __restrict__ rgb, const T* __restrict__ view_dir,
@@ -1312,30 +1327,16 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
     const T* __restrict__ src_opacity, const T* __restrict__ src_conic, const SegState seg,
     const int* __restrict__ cut_flags, const int* __restrict__ full_ranges, const int* __restrict__ overflow_sorted,
     const unsigned long long* __restrict__ touch_masks) {
-    static_assert(sizeof(T) == 4, "the fp32 slot kernel; fp64 goes to k_render_bwd_ref");
-    constexpr int CW = ColW<N_SH>::value;
-    constexpr int C = 3 * N_SH;
-    constexpr int REF_CH = ref_chunk<T>(N_SH);
+    static_assert(sizeof(T) == 4 && N_SH == 1, "the fused fp32 kernel; per-pixel SH goes to k_render_bwd_sh, fp64 to k_render_bwd_ref");
+    constexpr int REF_CH = ref_chunk<float>(1);
     // Every wave owns a slot of nine sums per staged splat and writes it once (plain store after a full-wave
     // reduction), the flush adds the slots of the waves that wrote -- no LDS atomics, no zero fill.
-    // SHMM: per-pixel SH (render_backward.cu:422-488).  The gradient of coefficient (ch, s) of a
-    // splat is sum over pixels of Y_s(p) gi_ch(p) * aw(p): a contraction over the wave's 64 pixels whose left
-    // factor does not depend on the splat -- a GEMM [16 x 64] x [64 x 16 splats] per channel, done with
-    // v_mfma_f32_16x16x4_f32 (exact fp32) on batches of 16 contributing splats instead of 3 * N_SH cross-lane
-    // reductions per visit.  The slots then carry only the six geometric sums.
-    constexpr bool SHMM = N_SH > 1;
-    constexpr int SV = 9;   // width of a slot: colour 3 (unused with SHMM) | w, w du, w dv | conic terms 3
+    constexpr int SV = 9;   // width of a slot: colour 3 | w, w du, w dv | conic terms 3
     constexpr int RCHUNK = GS_BWD_CHUNK;
     constexpr int NWORD = RCHUNK / 64 > 0 ? RCHUNK / 64 : 1;
-    constexpr int MB = 16;        // splats per MFMA batch (the N of 16x16x4)
-    constexpr int BROW = 64 + 4;  // floats per row of the batch's aw matrix [slot][pixel] (16-byte aligned rows)
-    __shared__ alignas(16) T s_geom[RCHUNK * GS_PACKED_WIDTH];
-    __shared__ alignas(16) T s_col[N_SH > 1 ? RCHUNK * CW : 4];
+    __shared__ alignas(16) float s_geom[RCHUNK * GS_PACKED_WIDTH];
     __shared__ int s_idx[RCHUNK];
-    __shared__ T s_acc[4 * RCHUNK * SV];                         // [wave][splat][9]
-    __shared__ alignas(16) float s_B[SHMM ? 4 * MB * BROW : 4];  // SHMM: [wave][slot][pixel] aw of the open batch
-    __shared__ int s_bidx[SHMM ? 4 * MB : 1];                     // SHMM: [wave][slot] Gaussian index of the splat
-    __shared__ alignas(16) float s_gi[SHMM ? 4 * 3 * 64 : 4];    // SHMM: [wave][ch][pixel] grad_image
+    __shared__ float s_acc[4 * RCHUNK * SV];                     // [wave][splat][9]
     __shared__ int s_max[4];
     __shared__ unsigned long long s_mask[4][NWORD];
     __shared__ unsigned long long s_hit[4][NWORD];               // slots written by each wave
@@ -1366,31 +1367,22 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
     if (n_tile <= 0) return;
 
     int nsp = 0;
-    T weight = 0;
-    T gi[3] = {0, 0, 0};
-    T Y[N_SH];
+    float weight = 0;
+    float gi[3] = {0, 0, 0};
     int kend = 0;                 // segments: index after the pixel's last contributor, and what the backward's
     float oma_last = 1, bgw = 0;  // first step at that splat does (written by the forward's epilogue)
-    {
-        T d[3] = {0, 0, 0};
-        if (valid) {
-            const size_t p = (size_t)px.v * W + px.u;
-            nsp = nsp_in[p];
-            weight = fw_in[p];
-            if (seg_on) {
-                kend = seg.kend[p - seg.pix0];
-                oma_last = seg.oma_last[p - seg.pix0];
-                bgw = seg.bgw[p - seg.pix0];
-            }
-            gi[0] = grad_image[p * 3 + 0];
-            gi[1] = grad_image[p * 3 + 1];
-            gi[2] = grad_image[p * 3 + 2];
-            if constexpr (N_SH > 1) {
-                d[0] = view_dir[p * 3 + 0]; d[1] = view_dir[p * 3 + 1]; d[2] = view_dir[p * 3 + 2];
-            }
+    if (valid) {
+        const size_t p = (size_t)px.v * W + px.u;
+        nsp = nsp_in[p];
+        weight = fw_in[p];
+        if (seg_on) {
+            kend = seg.kend[p - seg.pix0];
+            oma_last = seg.oma_last[p - seg.pix0];
+            bgw = seg.bgw[p - seg.pix0];
         }
-        if constexpr (N_SH > 1) sh_basis<T, N_SH>(d, Y);
-        else Y[0] = T(GS_SH_0);
+        gi[0] = grad_image[p * 3 + 0];
+        gi[1] = grad_image[p * 3 + 1];
+        gi[2] = grad_image[p * 3 + 2];
     }
     // the tile's deepest used splat (render_backward.cu:131 makes everything beyond it a no-op)
     int m = nsp;
@@ -1401,95 +1393,13 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
     const int n_used = min(n_tile, max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3])));
     if (n_used <= 0) return;
 
-    const T pu = T(px.u), pv = T(px.v);
+    const float pu = float(px.u), pv = float(px.v);
     const int slot_off = slot_lane_offset(lane);
     const bool slot_stores = slot_off >= 0;
     const int slot_lane_base = wave * RCHUNK * SV + (slot_stores ? slot_off : 0);
-    T color_accum[3] = {0, 0, 0};
+    float color_accum[3] = {0, 0, 0};
     bool bg_init = false;
-    const T bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
-
-    // SHMM: the batch GEMM, per channel  D[s][j] = sum_k A[s][k] B[k][j]  with
-    //   A[s][k] = Y_s(pixel k)                  (constant over the walk: registers y_op)
-    //   B[k][j] = aw of batch slot j at pixel k * grad_image_ch(pixel k)
-    // The contraction index of MFMA step t, sub-index q (= lane >> 4) is pixel 16 q + t of the wave -- any bijection
-    // serves a sum -- so that lane 16 q + j finds its sixteen B values (slot j, pixels 16 q .. 16 q + 15) and its
-    // sixteen grad_image values contiguous in LDS:   y_op[t] = Y_{lane & 15}(pixel 16 q + t)   (rows s >= N_SH: 0)
-    float y_op[SHMM ? 16 : 1];
-    int nb = 0;   // SHMM: filled slots of the wave's open batch (wave-uniform)
-    if constexpr (SHMM) {
-        float* tmp = s_B + wave * MB * BROW;   // [pixel][17]: 64 * 17 == MB * BROW floats of this wave
-        static_assert(64 * 17 <= MB * BROW && MB * 48 <= MB * BROW, "scratch uses of the wave's B rows");
-#pragma unroll
-        for (int s2 = 0; s2 < 16; s2++) tmp[lane * 17 + s2] = s2 < N_SH ? float(Y[s2 < N_SH ? s2 : 0]) : 0.0f;
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) s_gi[(wave * 3 + ch) * 64 + lane] = float(gi[ch]);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-        for (int t = 0; t < 16; t++) y_op[t] = tmp[(16 * (lane >> 4) + t) * 17 + (lane & 15)];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-    // SHMM: the GEMM of the open batch; its results are the wave's complete sums for (tile patch, splat): they go
-    // straight to the global gradient rows (an LDS accumulator shared by the four waves needs 768 LDS float
-    // atomics per batch, which cost more than the MFMAs: 0.15 of 0.69 ms at workload B)
-    auto mma_flush = [&](int n_filled) {
-        if constexpr (SHMM) {
-            typedef float f32x4 __attribute__((ext_vector_type(4)));
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const int j = lane & 15, q = lane >> 4;
-            float* mine = s_B + wave * MB * BROW;
-            const Vec4<float>* brow = reinterpret_cast<const Vec4<float>*>(mine + j * BROW + 16 * q);
-            float b[16];
-#pragma unroll
-            for (int m4 = 0; m4 < 4; m4++) {
-                const Vec4<float> v4 = brow[m4];
-                b[4 * m4 + 0] = v4.x; b[4 * m4 + 1] = v4.y; b[4 * m4 + 2] = v4.z; b[4 * m4 + 3] = v4.w;
-            }
-            f32x4 acc[3];
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) {
-                const Vec4<float>* grow = reinterpret_cast<const Vec4<float>*>(s_gi + (wave * 3 + ch) * 64 + 16 * q);
-                float g[16];
-#pragma unroll
-                for (int m4 = 0; m4 < 4; m4++) {
-                    const Vec4<float> v4 = grow[m4];
-                    g[4 * m4 + 0] = v4.x; g[4 * m4 + 1] = v4.y; g[4 * m4 + 2] = v4.z; g[4 * m4 + 3] = v4.w;
-                }
-                f32x4 even = {0, 0, 0, 0}, odd = {0, 0, 0, 0};   // two chains: the dependent-issue latency is 40 cycles
-#pragma unroll
-                for (int t = 0; t < 16; t += 2) {
-                    even = __builtin_amdgcn_mfma_f32_16x16x4f32(y_op[t], b[t] * g[t], even, 0, 0, 0);
-                    odd = __builtin_amdgcn_mfma_f32_16x16x4f32(y_op[t + 1], b[t + 1] * g[t + 1], odd, 0, 0, 0);
-                }
-                acc[ch] = even + odd;
-            }
-            // D: column j = lane & 15 (the batch slot), rows s = 4 q + r  ->  the wave's scratch as [slot][ch][16]
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();   // every lane has read its B values
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) {
-                Vec4<float> v4;
-                v4.x = acc[ch][0]; v4.y = acc[ch][1]; v4.z = acc[ch][2]; v4.w = acc[ch][3];
-                *reinterpret_cast<Vec4<float>*>(mine + j * 48 + ch * 16 + 4 * q) = v4;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // consecutive lanes, consecutive words of a gradient row
-            for (int k = lane; k < n_filled * 48; k += 64) {
-                const int row = k / 48, c = k - row * 48;
-                const int ch = c >> 4, s2 = c & 15;
-                if (s2 < N_SH) global_add(g_rgb + (size_t)s_bidx[wave * MB + row] * C + ch * N_SH + s2, mine[k]);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
-    };
+    const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
 
     GS_STAT_DECL;
     GS_HALF_DECL;
@@ -1514,8 +1424,8 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
             const bool first_divides = (exact ? k_m : k_m % REF_CH) < nsp - 1;   // Q1 at the first contributor
             // weight after the walk's first step, with the last contributor's own factor taken out again
             // (it is inside P of its segment)
-            T wb = (first_divides ? weight * fast_rcp(oma_last) : weight) * oma_last;
-            T d0 = 0, d1 = 0, d2 = 0;
+            float wb = (first_divides ? weight * fast_rcp(oma_last) : weight) * oma_last;
+            float d0 = 0, d1 = 0, d2 = 0;
             for (int s2 = e_tile; s2 > seg_id; s2--) {   // deepest first, as the walk accumulates
                 if (s2 <= e_p) {
                     const Vec4<float> r4 = rec[s2 * RB];
@@ -1543,7 +1453,7 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
         const int cnt = min(RCHUNK, seg_hi - base);
         GS_STAT(1, 1);
         __syncthreads();   // previous chunk fully flushed
-        stage_chunk<T, N_SH, 1>(packed, rgb, sorted, s0 + base, cnt, tid, s_geom, s_col, s_idx, src_opacity, src_conic);
+        stage_chunk<float, 1, 1>(packed, rgb, sorted, s0 + base, cnt, tid, s_geom, nullptr, s_idx, src_opacity, src_conic);
         GS_PHASE(0);
         if constexpr (RCHUNK == 64) {
             if (touch_masks != nullptr && chunk < GS_MASK_WORDS) {
@@ -1555,11 +1465,11 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
             } else {
                 // one patch per wave (round 6): the records wave 0 staged have to be visible to the other three first
                 __syncthreads();
-                build_touch_masks_by_patch<T>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
+                build_touch_masks_by_patch(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
             }
         } else {
             // (no barrier in between: thread t tests the record thread t staged)
-            build_touch_masks<T, RCHUNK>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
+            build_touch_masks<float, RCHUNK>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
         }
         __syncthreads();
         GS_PHASE(1);
@@ -1581,8 +1491,7 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
             GS_STAT(9, 1);                          // visits with a reaching lane
             GS_STAT(6, __popcll(ballot(reach)));
             GS_STAT_FLAG(st_in);
-            // ---- the visit (written for one colour coefficient per channel, the fused renderer's kernel;
-            // SHMM replaces the record's colour by the pixel's and the three colour sums by the batch) ----
+            // ---- the visit ----
             // Per lane: aw = alpha * weight (colour gradient = aw * Y0 grad_image[ch]),
             // w = norm_prob * grad_alpha (the opacity gradient term), and with t = k w,
             // k = -0.5 opacity / det a per-splat constant applied in the flush:
@@ -1592,19 +1501,19 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
             // the conic terms are formed per pixel as the reference does -- their cancellation is
             // benign there and would not be after the sum.  All nine are 0 for a lane that does not
             // contribute, so the reduction needs no zero-filled value array.
-            const T* rec = s_geom + i * GS_PACKED_WIDTH;
-            const Vec4<T> g0 = *reinterpret_cast<const Vec4<T>*>(rec);       // u v r2 opacity
+            const float* rec = s_geom + i * GS_PACKED_WIDTH;
+            const Vec4<float> g0 = *reinterpret_cast<const Vec4<float>*>(rec);       // u v r2 opacity
             // the whole 48-byte record at once (one LDS round trip per visit instead of three dependent
             // ones; LDS bandwidth is no longer what bounds this kernel): 0.70 -> 0.69 ms
-            const Vec4<T> g1 = *reinterpret_cast<const Vec4<T>*>(rec + 4);   // a b c det
-            const Vec4<T> g2 = *reinterpret_cast<const Vec4<T>*>(rec + 8);   // 1/det, colour
+            const Vec4<float> g1 = *reinterpret_cast<const Vec4<float>*>(rec + 4);   // a b c det
+            const Vec4<float> g2 = *reinterpret_cast<const Vec4<float>*>(rec + 8);   // 1/det, colour
             asm volatile("" ::"v"(g1.x), "v"(g1.y), "v"(g1.z), "v"(g1.w), "v"(g2.x), "v"(g2.y), "v"(g2.z), "v"(g2.w));
-            const T du = pu - g0.x, dv = pv - g0.y;
-            const T du2 = du * du, dv2 = dv * dv;
+            const float du = pu - g0.x, dv = pv - g0.y;
+            const float du2 = du * du, dv2 = dv * dv;
             // aw, w and mh are formed by the lanes that pass the alpha test only; the others are cut out of the
             // nine sums by `contrib` below -- no zero-filled registers in front of (and, for the ones the
             // exponential reuses, again inside) the branches: they were 11 of the visit's ~120 vector instructions
-            T aw = unset<T>(), w = unset<T>(), mh = unset<T>(), duv = unset<T>();
+            float aw = unset(), w = unset(), mh = unset(), duv = unset();
             bool contrib = false;
             if (reach && !(du2 + dv2 > g0.z)) {   // inside the cutoff radius
                 GS_STAT_SET(st_in);
@@ -1613,14 +1522,14 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
                 mh = (g1.z * du * du - g1.w * du * dv + g1.x * dv * dv) * g2.x;   // g1.w = b + b (stage_chunk)
                 // norm_prob = 0 unless mh > 0 (render_backward.cu:158-165) -- and then alpha = 0 fails the 1/255 test:
                 // `mh > 0` joins the test's lane mask (a scalar and), behind it norm_prob IS the exponential
-                const T norm_prob = exp_neg_half(mh);
-                T alpha = g0.w * norm_prob;
-                if (alpha > Thr<T>::sat_gt()) alpha = Thr<T>::alpha_cap();   // min(0.9999, .)
-                if ((mh > T(0)) & (alpha >= Thr<T>::alpha_min())) {
+                const float norm_prob = exp_neg_half(mh);
+                float alpha = g0.w * norm_prob;
+                if (alpha > Thr<float>::sat_gt()) alpha = Thr<float>::alpha_cap();   // min(0.9999, .)
+                if ((mh > 0.0f) & (alpha >= Thr<float>::alpha_min())) {
                     contrib = true;
                     if (!bg_init) {   // render_backward.cu:172-181
-                        const T bw = background_weight<T>(alpha, weight);
-                        if (bw > Thr<T>::bgw_gt()) {
+                        const float bw = background_weight<float>(alpha, weight);
+                        if (bw > Thr<float>::bgw_gt()) {
                             color_accum[0] += bg0 * bw;
                             color_accum[1] += bg1 * bw;
                             color_accum[2] += bg2 * bw;
@@ -1630,37 +1539,31 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
                     // values only from here on (no threshold depends on them): contraction allowed
                     {
 #pragma clang fp contract(fast)
-                        const T r1ma = fast_rcp(T(1) - alpha);
+                        const float r1ma = fast_rcp(1.0f - alpha);
                         if (kq < nsp - 1) weight = weight * r1ma;   // Q1 (chunk-local index) unless exact
                         aw = alpha * weight;
                         // grad_alpha (render_backward.cu:196-203); the record's colour is Y0 * coefficient
-                        T c0 = g2.y, c1 = g2.z, c2 = g2.w;
-                        if constexpr (SHMM) {   // colour at this pixel's view direction
-                            T col[3];
-                            sh_to_rgb_contracted<T, N_SH>(s_col + i * CW, Y, col);
-                            c0 = col[0]; c1 = col[1]; c2 = col[2];
-                        }
-                        const T ga = (c0 * weight - color_accum[0] * r1ma) * gi[0] +
-                                     (c1 * weight - color_accum[1] * r1ma) * gi[1] +
-                                     (c2 * weight - color_accum[2] * r1ma) * gi[2];
-                        color_accum[0] += c0 * aw;
-                        color_accum[1] += c1 * aw;
-                        color_accum[2] += c2 * aw;
+                        const float ga = (g2.y * weight - color_accum[0] * r1ma) * gi[0] +
+                                         (g2.z * weight - color_accum[1] * r1ma) * gi[1] +
+                                         (g2.w * weight - color_accum[2] * r1ma) * gi[2];
+                        color_accum[0] += g2.y * aw;
+                        color_accum[1] += g2.z * aw;
+                        color_accum[2] += g2.w * aw;
                         w = norm_prob * ga;
                     }
                 }
             }
             // a lane contributes iff it passed the alpha test; aw > 0 there (alpha >= 1/255, weight > 0)
-            const T awz = contrib ? aw : T(0);
-            const unsigned long long cmask = ballot(awz != T(0));
+            const float awz = contrib ? aw : 0.0f;
+            const unsigned long long cmask = ballot(awz != 0.0f);
             GS_STAT(3, ballot(st_in) != 0);
             GS_STAT(4, cmask != 0);
             GS_STAT(5, __popcll(cmask));
             GS_HALF_VISIT(ballot(st_in));
             if (cmask == 0) continue;   // every reaching lane skipped the splat
-            T val[9];
-            const T wz = contrib ? w : T(0);
-            const T awy = awz * Y[0];   // (the compiler re-formed Y0 * gi[ch] at every visit to save registers)
+            float val[9];
+            const float wz = contrib ? w : 0.0f;
+            const float awy = awz * float(GS_SH_0);   // Y0 (the compiler re-formed Y0 * gi[ch] at every visit to save registers)
             val[0] = awy * gi[0]; val[1] = awy * gi[1]; val[2] = awy * gi[2];
             val[3] = wz; val[4] = wz * du; val[5] = wz * dv;
             // (mh and duv of a lane that stayed outside are whatever an earlier visit left: 0 * x = 0 for every x)
@@ -1672,25 +1575,10 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
             }
             int slot_i = i * SV;   // (kept scalar: the compiler otherwise folds it into a 64-bit vector multiply-add)
             asm volatile("" : "+s"(slot_i));
-            reduce9_to_slot(val, slot_stores, reinterpret_cast<float*>(s_acc), slot_lane_base + slot_i);
+            reduce9_to_slot(val, slot_stores, s_acc, slot_lane_base + slot_i);
             hit |= 1ull << bit;
-            if constexpr (SHMM) {
-                // column nb of the batch's B: this splat's aw at the wave's 64 pixels (0 where it does not contribute)
-                s_B[(wave * MB + nb) * BROW + lane] = awz;
-                if (lane == 0) s_bidx[wave * MB + nb] = s_idx[i];
-                if (++nb == MB) {
-                    mma_flush(MB);
-                    nb = 0;
-                }
-            }
           }
           if (lane == 0) s_hit[wave][word] = hit;
-        }
-        if constexpr (SHMM) {
-            if (nb > 0) {
-                mma_flush(nb);
-                nb = 0;
-            }
         }
         GS_PHASE(2);
         GS_HALF_CHUNK(12);
@@ -1701,28 +1589,28 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
         // (deterministic per tile), apply the per-splat factors, and park the row in wave 0's slot of the
         // same splat (each thread only ever touches its own splat's slots: no barrier needed before).
         if (tid < cnt) {
-            T a[SV];
+            float a[SV];
 #pragma unroll
             for (int j = 0; j < SV; j++) a[j] = 0;
 #pragma unroll
             for (int w4 = 0; w4 < 4; w4++) {
                 if ((s_hit[w4][tid >> 6] >> (tid & 63)) & 1ull) {
-                    const T* sl = s_acc + (w4 * RCHUNK + tid) * SV;
+                    const float* sl = s_acc + (w4 * RCHUNK + tid) * SV;
 #pragma unroll
                     for (int j = 0; j < SV; j++) a[j] += sl[j];
                 }
             }
             // sums of (w, w du, w dv) and of the per-pixel conic terms -> gradients (see the loop)
-            const T* rec = s_geom + tid * GS_PACKED_WIDTH;
-            const T ca = rec[4], cb = rec[5], cc = rec[6];
-            const T k = T(-0.5) * rec[3] * rec[8];
-            const T Mu = a[4], Mv = a[5];
-            a[4] = T(-2) * k * (cc * Mu - cb * Mv);
-            a[5] = T(-2) * k * (ca * Mv - cb * Mu);
+            const float* rec = s_geom + tid * GS_PACKED_WIDTH;
+            const float ca = rec[4], cb = rec[5], cc = rec[6];
+            const float k = -0.5f * rec[3] * rec[8];
+            const float Mu = a[4], Mv = a[5];
+            a[4] = -2.0f * k * (cc * Mu - cb * Mv);
+            a[5] = -2.0f * k * (ca * Mv - cb * Mu);
             a[6] *= k;
             a[7] *= k;
             a[8] *= k;
-            T* row = s_acc + tid * SV;
+            float* row = s_acc + tid * SV;
 #pragma unroll
             for (int j = 0; j < SV; j++) row[j] = a[j];
         }
@@ -1734,17 +1622,374 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
         const int sub = lane / SV, col = lane - sub * SV;   // lane 63: idle
         for (int r0 = wave * 7; r0 < cnt; r0 += 28) {
             const int r = r0 + sub;
-            const bool in = lane < 63 && r < cnt && !(SHMM && col < 3);   // SHMM: the colour sums went out with the batches
-            const T v = in ? s_acc[r * SV + col] : T(0);
-            const unsigned long long nz = ballot(v != T(0));
+            const bool in = lane < 63 && r < cnt;
+            const float v = in ? s_acc[r * SV + col] : 0.0f;
+            const unsigned long long nz = ballot(v != 0.0f);
             const bool any = in && ((nz >> (sub * SV)) & 0x1ffull) != 0;   // rows of zeros stay untouched
             GS_STAT(11, __popcll(ballot(any && col == 0)));   // flushed rows
             if (any) {
                 const int g = s_idx[r];
-                T* dst;
+                float* dst;
                 if (slab) dst = g_rgb + (size_t)g * SV + col;   // [V, 9]: rgb 3 | opacity 1 | uv 2 | conic 3
                 else if (col < 3) dst = g_rgb + (size_t)g * 3 + col;
                 else if (col == 3) dst = g_opa + g;
+                else if (col < 6) dst = g_uv + (size_t)g * 2 + (col - 4);
+                else dst = g_conic + (size_t)g * 3 + (col - 6);
+                global_add(dst, v);
+            }
+        }
+        GS_PHASE(4);
+    }
+    GS_STAT_FLUSH(16);
+}
+
+// The fp32 backward with per-pixel SH (N_SH = 4 / 9 / 16 coefficients per channel; render_backward.cu:422-488), behind
+// gs_render_tiles_backward / _packed only: launch_render_bwd is its one caller.  The same walk as k_render_bwd --
+// chunks of GS_BWD_CHUNK from the tile's deepest used splat to the front, touch masks built here, Q1, the wave's slot
+// per staged splat, the two-phase flush -- over whole lists and into the four separate gradient arrays: no slab, tile
+// order, depth segments, depth-cut lists or handed-over masks.  A splat's colour is evaluated at the pixel's view
+// direction from the staged coefficients (s_col), and the colour-coefficient gradients leave the slots: the gradient
+// of coefficient (ch, s) of a splat is sum over pixels of Y_s(p) gi_ch(p) * aw(p), a contraction over the wave's 64
+// pixels whose left factor does not depend on the splat -- a GEMM [16 x 64] x [64 x 16 splats] per channel, done with
+// v_mfma_f32_16x16x4_f32 (exact fp32) on batches of 16 contributing splats instead of 3 * N_SH cross-lane reductions
+// per visit.  The slot stays nine wide with its three colour sums unused: a six-value reduction would change the
+// kernel's speed, which the split that gave it a body of its own did not set out to do.
+template <int N_SH>
+__global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd_sh(
+    const float* __restrict__ packed, const float* __restrict__ rgb, const float* __restrict__ view_dir,
+    const int* __restrict__ ranges, const int* __restrict__ sorted, const float* __restrict__ bg,
+    const int* __restrict__ nsp_in, const float* __restrict__ fw_in, const float* __restrict__ grad_image,
+    int W, int H, int ntx, int tile0, int nt, float* __restrict__ g_rgb, float* __restrict__ g_opa,
+    float* __restrict__ g_uv, float* __restrict__ g_conic, int exact, const float* __restrict__ src_opacity,
+    const float* __restrict__ src_conic) {
+    static_assert(N_SH > 1, "per-pixel SH; one coefficient goes to k_render_bwd<float, 1>");
+    constexpr int CW = ColW<N_SH>::value;
+    constexpr int C = 3 * N_SH;
+    constexpr int REF_CH = ref_chunk<float>(N_SH);
+    constexpr int SV = 9;   // width of a slot: colour 3 (unused) | w, w du, w dv | conic terms 3
+    constexpr int RCHUNK = GS_BWD_CHUNK;
+    constexpr int NWORD = RCHUNK / 64 > 0 ? RCHUNK / 64 : 1;
+    constexpr int MB = 16;        // splats per MFMA batch (the N of 16x16x4)
+    constexpr int BROW = 64 + 4;  // floats per row of the batch's aw matrix [slot][pixel] (16-byte aligned rows)
+    __shared__ alignas(16) float s_geom[RCHUNK * GS_PACKED_WIDTH];
+    __shared__ alignas(16) float s_col[RCHUNK * CW];
+    __shared__ int s_idx[RCHUNK];
+    __shared__ float s_acc[4 * RCHUNK * SV];              // [wave][splat][9]
+    __shared__ alignas(16) float s_B[4 * MB * BROW];      // [wave][slot][pixel] aw of the open batch
+    __shared__ int s_bidx[4 * MB];                         // [wave][slot] Gaussian index of the splat
+    __shared__ alignas(16) float s_gi[4 * 3 * 64];        // [wave][ch][pixel] grad_image
+    __shared__ int s_max[4];
+    __shared__ unsigned long long s_mask[4][NWORD];
+    __shared__ unsigned long long s_hit[4][NWORD];        // slots written by each wave
+
+    const int t_local = tile_of_block(blockIdx.x, nt);
+    if (t_local >= nt) return;
+    const int tile = tile0 + t_local;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const PixelMap px = pixel_of_thread(tile % ntx, tile / ntx, tid);
+    const bool valid = px.u < W && px.v < H;
+    const int s0 = ranges[tile];
+    const int n_tile = ranges[tile + 1] - s0;
+    if (n_tile <= 0) return;
+
+    int nsp = 0;
+    float weight = 0;
+    float gi[3] = {0, 0, 0};
+    float Y[N_SH];
+    {
+        float d[3] = {0, 0, 0};
+        if (valid) {
+            const size_t p = (size_t)px.v * W + px.u;
+            nsp = nsp_in[p];
+            weight = fw_in[p];
+            gi[0] = grad_image[p * 3 + 0];
+            gi[1] = grad_image[p * 3 + 1];
+            gi[2] = grad_image[p * 3 + 2];
+            d[0] = view_dir[p * 3 + 0]; d[1] = view_dir[p * 3 + 1]; d[2] = view_dir[p * 3 + 2];
+        }
+        sh_basis<float, N_SH>(d, Y);
+    }
+    // the tile's deepest used splat (render_backward.cu:131 makes everything beyond it a no-op)
+    int m = nsp;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) m = max(m, __shfl_xor(m, d));
+    if (lane == 0) s_max[wave] = m;
+    __syncthreads();
+    const int n_used = min(n_tile, max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3])));
+    if (n_used <= 0) return;
+
+    const float pu = float(px.u), pv = float(px.v);
+    const int slot_off = slot_lane_offset(lane);
+    const bool slot_stores = slot_off >= 0;
+    const int slot_lane_base = wave * RCHUNK * SV + (slot_stores ? slot_off : 0);
+    float color_accum[3] = {0, 0, 0};
+    bool bg_init = false;
+    const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
+
+    // The batch GEMM, per channel  D[s][j] = sum_k A[s][k] B[k][j]  with
+    //   A[s][k] = Y_s(pixel k)                  (constant over the walk: registers y_op)
+    //   B[k][j] = aw of batch slot j at pixel k * grad_image_ch(pixel k)
+    // The contraction index of MFMA step t, sub-index q (= lane >> 4) is pixel 16 q + t of the wave -- any bijection
+    // serves a sum -- so that lane 16 q + j finds its sixteen B values (slot j, pixels 16 q .. 16 q + 15) and its
+    // sixteen grad_image values contiguous in LDS:   y_op[t] = Y_{lane & 15}(pixel 16 q + t)   (rows s >= N_SH: 0)
+    float y_op[16];
+    int nb = 0;   // filled slots of the wave's open batch (wave-uniform)
+    {
+        float* tmp = s_B + wave * MB * BROW;   // [pixel][17]: 64 * 17 == MB * BROW floats of this wave
+        static_assert(64 * 17 <= MB * BROW && MB * 48 <= MB * BROW, "scratch uses of the wave's B rows");
+#pragma unroll
+        for (int s2 = 0; s2 < 16; s2++) tmp[lane * 17 + s2] = s2 < N_SH ? Y[s2 < N_SH ? s2 : 0] : 0.0f;
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) s_gi[(wave * 3 + ch) * 64 + lane] = gi[ch];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int t = 0; t < 16; t++) y_op[t] = tmp[(16 * (lane >> 4) + t) * 17 + (lane & 15)];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    // The GEMM of the open batch; its results are the wave's complete sums for (tile patch, splat): they go
+    // straight to the global gradient rows (an LDS accumulator shared by the four waves needs 768 LDS float
+    // atomics per batch, which cost more than the MFMAs: 0.15 of 0.69 ms at workload B)
+    auto mma_flush = [&](int n_filled) {
+        typedef float f32x4 __attribute__((ext_vector_type(4)));
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const int j = lane & 15, q = lane >> 4;
+        float* mine = s_B + wave * MB * BROW;
+        const Vec4<float>* brow = reinterpret_cast<const Vec4<float>*>(mine + j * BROW + 16 * q);
+        float b[16];
+#pragma unroll
+        for (int m4 = 0; m4 < 4; m4++) {
+            const Vec4<float> v4 = brow[m4];
+            b[4 * m4 + 0] = v4.x; b[4 * m4 + 1] = v4.y; b[4 * m4 + 2] = v4.z; b[4 * m4 + 3] = v4.w;
+        }
+        f32x4 acc[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            const Vec4<float>* grow = reinterpret_cast<const Vec4<float>*>(s_gi + (wave * 3 + ch) * 64 + 16 * q);
+            float g[16];
+#pragma unroll
+            for (int m4 = 0; m4 < 4; m4++) {
+                const Vec4<float> v4 = grow[m4];
+                g[4 * m4 + 0] = v4.x; g[4 * m4 + 1] = v4.y; g[4 * m4 + 2] = v4.z; g[4 * m4 + 3] = v4.w;
+            }
+            f32x4 even = {0, 0, 0, 0}, odd = {0, 0, 0, 0};   // two chains: the dependent-issue latency is 40 cycles
+#pragma unroll
+            for (int t = 0; t < 16; t += 2) {
+                even = __builtin_amdgcn_mfma_f32_16x16x4f32(y_op[t], b[t] * g[t], even, 0, 0, 0);
+                odd = __builtin_amdgcn_mfma_f32_16x16x4f32(y_op[t + 1], b[t + 1] * g[t + 1], odd, 0, 0, 0);
+            }
+            acc[ch] = even + odd;
+        }
+        // D: column j = lane & 15 (the batch slot), rows s = 4 q + r  ->  the wave's scratch as [slot][ch][16]
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();   // every lane has read its B values
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            Vec4<float> v4;
+            v4.x = acc[ch][0]; v4.y = acc[ch][1]; v4.z = acc[ch][2]; v4.w = acc[ch][3];
+            *reinterpret_cast<Vec4<float>*>(mine + j * 48 + ch * 16 + 4 * q) = v4;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // consecutive lanes, consecutive words of a gradient row
+        for (int k = lane; k < n_filled * 48; k += 64) {
+            const int row = k / 48, c = k - row * 48;
+            const int ch = c >> 4, s2 = c & 15;
+            if (s2 < N_SH) global_add(g_rgb + (size_t)s_bidx[wave * MB + row] * C + ch * N_SH + s2, mine[k]);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+
+    GS_STAT_DECL;
+    GS_HALF_DECL;
+    GS_STAT(0, 1);          // waves
+    GS_STAT(7, n_tile);
+    GS_STAT(8, n_used);
+    // Q1 (render_backward.cu:185 compares a chunk-local index): k % REF_CH for k = base + i, i < RCHUNK <= REF_CH, is
+    // base % REF_CH + i with at most one wrap -- one scalar division per CHUNK instead of a multiply-high sequence
+    // (9 scalar instructions) per visit; exact mode never wraps
+    static_assert(RCHUNK <= REF_CH, "one wrap per chunk");
+    const int q1_wrap = exact ? 0x7fffffff : REF_CH;
+    for (int chunk = (n_used - 1) / RCHUNK; chunk >= 0; chunk--) {
+        const int base = chunk * RCHUNK;
+        const int base_q = exact ? base : base % REF_CH;
+        const int cnt = min(RCHUNK, n_used - base);
+        GS_STAT(1, 1);
+        __syncthreads();   // previous chunk fully flushed
+        stage_chunk<float, N_SH, 1>(packed, rgb, sorted, s0 + base, cnt, tid, s_geom, s_col, s_idx, src_opacity, src_conic);
+        GS_PHASE(0);
+        if constexpr (RCHUNK == 64) {
+            // one patch per wave: the records wave 0 staged have to be visible to the other three first
+            __syncthreads();
+            build_touch_masks_by_patch(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
+        } else {
+            // (no barrier in between: thread t tests the record thread t staged)
+            build_touch_masks<float, RCHUNK>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
+        }
+        __syncthreads();
+        GS_PHASE(1);
+
+        for (int word = (cnt - 1) >> 6; word >= 0; word--) {
+          unsigned long long m = s_mask[wave][word];
+          m = wave_uniform(m);
+          unsigned long long hit = 0;   // the splats of this word whose slot the wave wrote
+          while (m) {
+            const int bit = 63 - __builtin_clzll(m);
+            m &= ~(1ull << bit);
+            const int i = (word << 6) + bit;
+            const int k = base + i;
+            int kq = base_q + i;   // = exact ? k : k % REF_CH
+            kq = kq >= q1_wrap ? kq - q1_wrap : kq;
+            const bool reach = k < nsp;   // render_backward.cu:131 (nsp == 0 outside the image)
+            GS_STAT(2, 1);                          // visits
+            if (ballot(reach) == 0) continue;      // wave-uniform: no lane reaches this splat
+            GS_STAT(9, 1);                          // visits with a reaching lane
+            GS_STAT(6, __popcll(ballot(reach)));
+            GS_STAT_FLAG(st_in);
+            // ---- the visit: k_render_bwd's (see there for the nine sums), with the record's colour replaced by the
+            // pixel's and the three colour sums by the batch ----
+            const float* rec = s_geom + i * GS_PACKED_WIDTH;
+            const Vec4<float> g0 = *reinterpret_cast<const Vec4<float>*>(rec);       // u v r2 opacity
+            const Vec4<float> g1 = *reinterpret_cast<const Vec4<float>*>(rec + 4);   // a b c det
+            const Vec4<float> g2 = *reinterpret_cast<const Vec4<float>*>(rec + 8);   // 1/det (the colour words: unused)
+            asm volatile("" ::"v"(g1.x), "v"(g1.y), "v"(g1.z), "v"(g1.w), "v"(g2.x), "v"(g2.y), "v"(g2.z), "v"(g2.w));
+            const float du = pu - g0.x, dv = pv - g0.y;
+            const float du2 = du * du, dv2 = dv * dv;
+            // formed by the lanes that pass the alpha test only; `contrib` cuts the others out of the sums
+            float aw = unset(), w = unset(), mh = unset(), duv = unset();
+            bool contrib = false;
+            if (reach && !(du2 + dv2 > g0.z)) {   // inside the cutoff radius
+                GS_STAT_SET(st_in);
+                // render_backward.cu:153-165 (multiplies by 1/det; the forward divides)
+                duv = du * dv;
+                mh = (g1.z * du * du - g1.w * du * dv + g1.x * dv * dv) * g2.x;   // g1.w = b + b (stage_chunk)
+                // norm_prob = 0 unless mh > 0 (render_backward.cu:158-165) -- and then alpha = 0 fails the 1/255 test
+                const float norm_prob = exp_neg_half(mh);
+                float alpha = g0.w * norm_prob;
+                if (alpha > Thr<float>::sat_gt()) alpha = Thr<float>::alpha_cap();   // min(0.9999, .)
+                if ((mh > 0.0f) & (alpha >= Thr<float>::alpha_min())) {
+                    contrib = true;
+                    if (!bg_init) {   // render_backward.cu:172-181
+                        const float bw = background_weight<float>(alpha, weight);
+                        if (bw > Thr<float>::bgw_gt()) {
+                            color_accum[0] += bg0 * bw;
+                            color_accum[1] += bg1 * bw;
+                            color_accum[2] += bg2 * bw;
+                        }
+                        bg_init = true;
+                    }
+                    // values only from here on (no threshold depends on them): contraction allowed
+                    {
+#pragma clang fp contract(fast)
+                        const float r1ma = fast_rcp(1.0f - alpha);
+                        if (kq < nsp - 1) weight = weight * r1ma;   // Q1 (chunk-local index) unless exact
+                        aw = alpha * weight;
+                        // grad_alpha (render_backward.cu:196-203), with the colour at this pixel's view direction
+                        float col[3];
+                        sh_to_rgb_contracted<float, N_SH>(s_col + i * CW, Y, col);
+                        const float ga = (col[0] * weight - color_accum[0] * r1ma) * gi[0] +
+                                         (col[1] * weight - color_accum[1] * r1ma) * gi[1] +
+                                         (col[2] * weight - color_accum[2] * r1ma) * gi[2];
+                        color_accum[0] += col[0] * aw;
+                        color_accum[1] += col[1] * aw;
+                        color_accum[2] += col[2] * aw;
+                        w = norm_prob * ga;
+                    }
+                }
+            }
+            // a lane contributes iff it passed the alpha test; aw > 0 there (alpha >= 1/255, weight > 0)
+            const float awz = contrib ? aw : 0.0f;
+            const unsigned long long cmask = ballot(awz != 0.0f);
+            GS_STAT(3, ballot(st_in) != 0);
+            GS_STAT(4, cmask != 0);
+            GS_STAT(5, __popcll(cmask));
+            GS_HALF_VISIT(ballot(st_in));
+            if (cmask == 0) continue;   // every reaching lane skipped the splat
+            float val[9];
+            const float wz = contrib ? w : 0.0f;
+            const float awy = awz * Y[0];
+            val[0] = awy * gi[0]; val[1] = awy * gi[1]; val[2] = awy * gi[2];   // (reduced, never flushed)
+            val[3] = wz; val[4] = wz * du; val[5] = wz * dv;
+            // (mh and duv of a lane that stayed outside are whatever an earlier visit left: 0 * x = 0 for every x)
+            {
+#pragma clang fp contract(fast)
+                val[6] = mul_zero_wins((dv2 - g1.z * mh), wz);
+                val[7] = mul_zero_wins((g1.y * mh - duv), wz);
+                val[8] = mul_zero_wins((du2 - g1.x * mh), wz);
+            }
+            int slot_i = i * SV;   // (kept scalar: the compiler otherwise folds it into a 64-bit vector multiply-add)
+            asm volatile("" : "+s"(slot_i));
+            reduce9_to_slot(val, slot_stores, s_acc, slot_lane_base + slot_i);
+            hit |= 1ull << bit;
+            // column nb of the batch's B: this splat's aw at the wave's 64 pixels (0 where it does not contribute)
+            s_B[(wave * MB + nb) * BROW + lane] = awz;
+            if (lane == 0) s_bidx[wave * MB + nb] = s_idx[i];
+            if (++nb == MB) {
+                mma_flush(MB);
+                nb = 0;
+            }
+          }
+          if (lane == 0) s_hit[wave][word] = hit;
+        }
+        if (nb > 0) {
+            mma_flush(nb);
+            nb = 0;
+        }
+        GS_PHASE(2);
+        GS_HALF_CHUNK(12);
+        __syncthreads();
+        GS_PHASE(3);
+        // the flush: one global atomic per value per (splat, tile), the six geometric columns only (the colour
+        // coefficients went out with the batches)
+        // Phase 1, thread = splat: add the slots of the waves that wrote this splat, in wave order
+        // (deterministic per tile), apply the per-splat factors, and park the row in wave 0's slot of the
+        // same splat (each thread only ever touches its own splat's slots: no barrier needed before).
+        if (tid < cnt) {
+            float a[SV];
+#pragma unroll
+            for (int j = 0; j < SV; j++) a[j] = 0;
+#pragma unroll
+            for (int w4 = 0; w4 < 4; w4++) {
+                if ((s_hit[w4][tid >> 6] >> (tid & 63)) & 1ull) {
+                    const float* sl = s_acc + (w4 * RCHUNK + tid) * SV;
+#pragma unroll
+                    for (int j = 0; j < SV; j++) a[j] += sl[j];
+                }
+            }
+            // sums of (w, w du, w dv) and of the per-pixel conic terms -> gradients (see the loop)
+            const float* rec = s_geom + tid * GS_PACKED_WIDTH;
+            const float ca = rec[4], cb = rec[5], cc = rec[6];
+            const float k = -0.5f * rec[3] * rec[8];
+            const float Mu = a[4], Mv = a[5];
+            a[4] = -2.0f * k * (cc * Mu - cb * Mv);
+            a[5] = -2.0f * k * (ca * Mv - cb * Mu);
+            a[6] *= k;
+            a[7] *= k;
+            a[8] *= k;
+            float* row = s_acc + tid * SV;
+#pragma unroll
+            for (int j = 0; j < SV; j++) row[j] = a[j];
+        }
+        __syncthreads();
+        // Phase 2, nine lanes = one row: seven rows per wave instruction, consecutive addresses (see k_render_bwd)
+        const int sub = lane / SV, col = lane - sub * SV;   // lane 63: idle
+        for (int r0 = wave * 7; r0 < cnt; r0 += 28) {
+            const int r = r0 + sub;
+            const bool in = lane < 63 && r < cnt && col >= 3;
+            const float v = in ? s_acc[r * SV + col] : 0.0f;
+            const unsigned long long nz = ballot(v != 0.0f);
+            const bool any = in && ((nz >> (sub * SV)) & 0x1ffull) != 0;   // rows of zeros stay untouched
+            GS_STAT(11, __popcll(ballot(any && col == 3)));   // flushed rows (col 3: the colour columns are not sent here)
+            if (any) {
+                const int g = s_idx[r];
+                float* dst;
+                if (col == 3) dst = g_opa + g;
                 else if (col < 6) dst = g_uv + (size_t)g * 2 + (col - 4);
                 else dst = g_conic + (size_t)g * 3 + (col - 6);
                 global_add(dst, v);
@@ -2292,14 +2537,30 @@ static int launch_render_bwd(const void* packed_or_uvs, const void* opacity, con
     const int nt = (tile_row1 - tile_row0) * ntx;
     if (nt == 0) return GS_OK;
     const int grid = render_grid(nt);
-    if (dtype == GS_F32) {
-        using T = float;
-        DISPATCH_SH(n_sh, (k_render_bwd<T, N_SH><<<grid, RB, 0, s>>>(
-                              (const T*)packed_or_uvs, (const T*)rgb, (const T*)view_dir_by_pixel, tile_ranges,
-                              sorted_gaussians, (const T*)background_rgb, num_splats_per_pixel,
-                              (const T*)final_weight_per_pixel, (const T*)grad_image, W, H, ntx, tile_row0 * ntx, nt,
-                              (T*)grad_rgb, (T*)grad_opacity, (T*)grad_uv, (T*)grad_conic, 0, exact, nullptr,
-                              (const T*)opacity, (const T*)conic, SEG_NONE, nullptr, nullptr, nullptr, nullptr)));
+    if (dtype == GS_F32 && n_sh == 1) {
+        // one coefficient: the fused renderer's kernel on separate arrays or packed records, whole lists, grid order
+        k_render_bwd<float, 1><<<grid, RB, 0, s>>>(
+            (const float*)packed_or_uvs, (const float*)rgb, (const float*)view_dir_by_pixel, tile_ranges,
+            sorted_gaussians, (const float*)background_rgb, num_splats_per_pixel,
+            (const float*)final_weight_per_pixel, (const float*)grad_image, W, H, ntx, tile_row0 * ntx, nt,
+            (float*)grad_rgb, (float*)grad_opacity, (float*)grad_uv, (float*)grad_conic, 0, exact, nullptr,
+            (const float*)opacity, (const float*)conic, SEG_NONE, nullptr, nullptr, nullptr, nullptr);
+    } else if (dtype == GS_F32) {
+        decltype(&k_render_bwd_sh<4>) kernel = nullptr;
+        switch (n_sh) {
+            case 4: kernel = k_render_bwd_sh<4>; break;
+            case 9: kernel = k_render_bwd_sh<9>; break;
+            case 16: kernel = k_render_bwd_sh<16>; break;
+            default:
+                gs::set_error("Unsupported number of SH coefficients: %d", n_sh);
+                return GS_EINVAL;
+        }
+        kernel<<<grid, RB, 0, s>>>(
+            (const float*)packed_or_uvs, (const float*)rgb, (const float*)view_dir_by_pixel, tile_ranges,
+            sorted_gaussians, (const float*)background_rgb, num_splats_per_pixel,
+            (const float*)final_weight_per_pixel, (const float*)grad_image, W, H, ntx, tile_row0 * ntx, nt,
+            (float*)grad_rgb, (float*)grad_opacity, (float*)grad_uv, (float*)grad_conic, exact,
+            (const float*)opacity, (const float*)conic);
     } else if (dtype == GS_F64) {
         using T = double;
         DISPATCH_SH(n_sh, (k_render_bwd_ref<N_SH><<<grid, RB, 0, s>>>(

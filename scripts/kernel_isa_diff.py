@@ -9,7 +9,14 @@ Per kernel: the function body (its label to .Lfunc_end), the .amdhsa_kernel desc
 counts (.set <kernel>.num_vgpr ...), with only the
 function index of local labels (.LBB<n>_, .Lfunc_end<n>) normalised -- it shifts when a kernel is added to or
 removed from the file.  Prints one line per kernel (instruction count and "identical", "only in ..." or the
-unified diff) and exits 1 if a kernel present in both files differs."""
+unified diff) and exits 1 if a kernel present in both files differs.
+
+    scripts/kernel_isa_diff.py --mnemonics before.s after.s
+
+For a kernel whose registers moved but whose instruction stream should not have: compares opcode names only (operands,
+register numbers, labels and directives dropped).  Per kernel that differs, instead of the unified diff: the stretches
+where the two mnemonic sequences differ, the common tail (from which instruction on each side they are equal to the
+end) and the position of the first s_flbit_i32_b64 on each side (the render backward's visit loop opens with it)."""
 import difflib
 import re
 import subprocess
@@ -29,8 +36,22 @@ def kernels(path):
         d1 = lines.index("\t.end_amdhsa_kernel", d0)
         sets = [l for l in lines[d1:] if l.startswith("\t.set " + name + ".")]   # the resource counts
         text = [LABEL.sub(r".\1N", l) for l in lines[start:end + 1] + lines[d0:d1 + 1] + sets]
-        n_instr = sum(1 for l in lines[start:end] if l.startswith("\t") and not l.lstrip().startswith((".", ";")))
-        out[name] = (text, n_instr)
+        mnem = [l.split()[0] for l in lines[start:end] if l.startswith("\t") and not l.lstrip().startswith((".", ";"))]
+        out[name] = (text, len(mnem), mnem)
+    return out
+
+
+def mnemonic_report(a, b):
+    """Lines describing where two mnemonic sequences differ (0-based instruction positions)."""
+    first = [seq.index("s_flbit_i32_b64") if "s_flbit_i32_b64" in seq else None for seq in (a, b)]
+    out = [f"    first s_flbit_i32_b64: before {first[0]}, after {first[1]}"]
+    tail = 0
+    while tail < min(len(a), len(b)) and a[-1 - tail] == b[-1 - tail]:
+        tail += 1
+    out.append(f"    equal from before {len(a) - tail} / after {len(b) - tail} to the end ({tail} mnemonics)")
+    for tag, i0, i1, j0, j1 in difflib.SequenceMatcher(None, a, b, autojunk=False).get_opcodes():
+        if tag != "equal":
+            out.append(f"    {tag:8s} before [{i0}, {i1}) {' '.join(a[i0:i1])}  |  after [{j0}, {j1}) {' '.join(b[j0:j1])}")
     return out
 
 
@@ -44,21 +65,26 @@ def demangle(names):
 
 
 def main():
-    before, after = kernels(sys.argv[1]), kernels(sys.argv[2])
+    mnemonics = "--mnemonics" in sys.argv
+    paths = [a for a in sys.argv[1:] if a != "--mnemonics"]
+    before, after = kernels(paths[0]), kernels(paths[1])
     names = list(before) + [n for n in after if n not in before]
     pretty = demangle(names)
     differ = 0
     for n in names:
         if n not in after:
-            print(f"{pretty[n]:44s} {before[n][1]:6d} instructions   only in {sys.argv[1]}")
+            print(f"{pretty[n]:44s} {before[n][1]:6d} instructions   only in {paths[0]}")
         elif n not in before:
-            print(f"{pretty[n]:44s} {after[n][1]:6d} instructions   only in {sys.argv[2]}")
+            print(f"{pretty[n]:44s} {after[n][1]:6d} instructions   only in {paths[1]}")
         elif before[n][0] == after[n][0]:
             print(f"{pretty[n]:44s} {after[n][1]:6d} instructions   identical")
         else:
             differ += 1
             print(f"{pretty[n]:44s} {before[n][1]:6d} -> {after[n][1]:6d} instructions   DIFFERENT")
-            print("\n".join(difflib.unified_diff(before[n][0], after[n][0], "before", "after", lineterm="", n=2)))
+            if mnemonics:
+                print("\n".join(mnemonic_report(before[n][2], after[n][2])))
+            else:
+                print("\n".join(difflib.unified_diff(before[n][0], after[n][0], "before", "after", lineterm="", n=2)))
     return 1 if differ else 0
 
 

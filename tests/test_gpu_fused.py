@@ -867,3 +867,69 @@ def test_general_forward_staging_forms_and_bands(dtype, n_sh):
         assert int(nsp_a.max()) > 0 and bool(img_a.any())
         for got in ((nsp_b, fw_b, img_b), (nsp_c, fw_c, img_c)):
             assert torch.equal(nsp_a, got[0]) and torch.equal(fw_a, got[1]) and torch.equal(img_a, got[2]), name
+
+
+@pytest.mark.parametrize("mode", ["compat", "exact"])
+@pytest.mark.parametrize("n_sh", [4, 16])
+def test_per_pixel_sh_backward_staging_forms_and_bands(n_sh, mode):
+    """k_render_bwd_sh (fp32 with per-pixel SH) run three ways after one gs_render_tiles forward, each into freshly
+    zeroed gradient arrays: gs_render_tiles_backward on the separate arrays (record formed while staging),
+    gs_render_tiles_backward_packed on records of gs_pack_splats, and the latter in two calls over the tile rows [0, 1)
+    and [1, nty) into one set of arrays.  The same kernel on the same record values under another order of atomics:
+    the four gradients within scaled_err < 2e-6 of the first form (the bound of
+    test_packed_render_entry_points_equal_the_reference_signature_ones), rows of Gaussians that are in no list exactly
+    zero, every gradient tensor with a non-zero entry.  faint_300: one tile, 300 faint splats every pixel walks to the
+    end -- five 64-entry chunks with a partial last one, batches of 16 that close in mid-chunk.  partial_48x40: 3 x 3
+    tiles, partial right and bottom tiles, empty tiles and single-entry lists.  The first form is the yardstick of the
+    other two; of its own values this test checks only the non-zero entry and the zero rows, and their correctness
+    rests on tests/test_gpu_render_ref64.py (the first form against the fp64 reference on these scenes)."""
+    import ctypes
+
+    from gaussian_splatting_amd import _hip
+
+    from . import render_ref64 as R
+    p = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
+    stream = _hip.current_stream()
+    gs_mode = _hip.GS_BACKWARD_EXACT if mode == "exact" else _hip.GS_BACKWARD_COMPAT
+    for name in ("faint_300", "partial_48x40"):
+        sc = R.render_scenes()[name]
+        W, H, V, nty = sc.W, sc.H, sc.V, (sc.H + 15) // 16
+        uv, opa, coeff, conic, bg, rays, gi, ranges, sorted_g = (
+            x.contiguous().to(DEV) for x in (sc.uv, sc.opacity, R.scene_coeff(sc, n_sh), sc.conic, sc.bg, sc.rays,
+                                             sc.grad_image, sc.ranges, sc.sorted_g))
+        nsp = torch.zeros(H, W, dtype=torch.int32, device=DEV)
+        fw, img = torch.zeros(H, W, device=DEV), torch.zeros(H, W, 3, device=DEV)
+        _hip.call("gs_render_tiles", p(uv), p(opa), p(coeff), p(conic), p(rays), p(ranges), p(sorted_g), p(bg), p(nsp),
+                  p(fw), p(img), W, H, n_sh, 0, nty, _hip.GS_F32, stream)
+        if name == "faint_300":
+            assert bool((nsp == 300).all())   # the last, partial chunk is reached by every pixel
+        packed = torch.empty(V, 12, device=DEV)
+        _hip.call("gs_pack_splats", p(uv), p(opa), p(conic), None, V, p(packed), _hip.GS_F32, stream)
+
+        def grads():
+            return [torch.zeros_like(x) for x in (coeff, opa, uv, conic)]
+
+        def backward_packed(g, row0, row1):
+            _hip.call("gs_render_tiles_backward_packed", p(packed), p(coeff), p(rays), p(ranges), p(sorted_g), p(bg),
+                      p(nsp), p(fw), p(gi), W, H, n_sh, row0, row1, p(g[0]), p(g[1]), p(g[2]), p(g[3]), _hip.GS_F32,
+                      gs_mode, stream)
+
+        ga, gb, gc = grads(), grads(), grads()
+        _hip.call("gs_render_tiles_backward", p(uv), p(opa), p(coeff), p(conic), p(rays), p(ranges), p(sorted_g), p(bg),
+                  p(nsp), p(fw), p(gi), p(ga[0]), p(ga[1]), p(ga[2]), p(ga[3]), W, H, n_sh, 0, nty, _hip.GS_F32, gs_mode,
+                  stream)
+        backward_packed(gb, 0, nty)
+        backward_packed(gc, 0, 1)
+        backward_packed(gc, 1, nty)
+
+        listed = torch.zeros(V, dtype=torch.bool, device=DEV)
+        listed[sorted_g[:int(ranges[-1])].long()] = True
+        for form, got in (("separate", ga), ("packed", gb), ("packed_bands", gc)):
+            for key, a, b in zip(R.GRAD_KEYS, ga, got):
+                assert bool(b.any()), (name, form, key)
+                assert not bool(b[~listed].any()), (name, form, key)
+                if got is not ga:
+                    err = scaled_err(b, a)
+                    report("per_pixel_sh_backward_forms", scene=name, n_sh=n_sh, mode=mode, form=form, grad=key,
+                           scaled_err=err)
+                    assert err < 2e-6, (name, form, key, err)

@@ -6,8 +6,8 @@ float64 kernels (k_render_fwd_general<double> and k_render_bwd_ref): num_splats 
 within the scaled_err bound of the CPU test (1.8e-12); exact mode everywhere, compat mode where the lists fit the
 reference's first chunk.
 
-float32 kernels (k_render_fwd<float, 1> with one coefficient, k_render_fwd_general<float> with 4 / 9 / 16; k_render_bwd<float>),
-non-fragile pixels only: num_splats equal; image and final weight
+float32 kernels (k_render_fwd<float, 1> and k_render_bwd<float, 1> with one coefficient, k_render_fwd_general<float> and
+k_render_bwd_sh with 4 / 9 / 16), non-fragile pixels only: num_splats equal; image and final weight
 through ref64.r_measure with env = |fp32 oracle - reference| (bound 8, tests/test_gpu_general_cameras.py); gradients
 through |got - ref| / abs_sum with the reference's own abs sums, where the kernel may exceed the fp32 oracle's value of
 the same measure by 2e-5 (tests/test_gpu_scale.py's noise_normalised bound) and no more.  Two runs per case:
