@@ -1,5 +1,5 @@
 // per_gaussian.hip -- one-thread-per-Gaussian kernels behind the eight projection entry points,
-// the two SH-precompute entry points and gs_pack_splats.  HBM-bound streaming kernels: 256-thread
+// the two SH-precompute entry points, gs_pack_splats and gs_z_backward.  HBM-bound streaming kernels: 256-thread
 // workgroups, no LDS, no host synchronisation, launched on the caller's stream.
 //
 // Forward kernels keep the operation order and operand precisions of the reference so that their
@@ -222,6 +222,23 @@ __global__ __launch_bounds__(PG_BLOCK) void k_pack(const T* __restrict__ uvs,
     for (int k = 0; k < GS_PACKED_WIDTH; k++) packed[(size_t)i * GS_PACKED_WIDTH + k] = p[k];
 }
 
+// The z term of the depth map's gradient (gs_z_backward): z = camera_T_world[2, 0:3] . xyz + camera_T_world[2, 3] of a
+// visible Gaussian, so dL/dxyz += dL/dz * camera_T_world[2, 0:3].  grad_z is indexed by the Gaussian's visible index
+// rank[i] - v_base; culled rows (rank < 0) are left as they are.  One fused multiply-add per element.
+__global__ __launch_bounds__(PG_BLOCK) void k_z_bwd(const int* __restrict__ rank, const float* __restrict__ grad_z,
+                                                    const float* __restrict__ camera_T_world, int v_base, int N,
+                                                    float* __restrict__ grad_xyz) {
+    const int i = blockIdx.x * PG_BLOCK + threadIdx.x;
+    if (i >= N) return;
+    const int r = rank[i];
+    if (r < 0) return;
+    const float gz = grad_z[r - v_base];
+    float* g = grad_xyz + (size_t)i * 3;
+    g[0] = __builtin_fmaf(gz, camera_T_world[8], g[0]);
+    g[1] = __builtin_fmaf(gz, camera_T_world[9], g[1]);
+    g[2] = __builtin_fmaf(gz, camera_T_world[10], g[2]);
+}
+
 template <typename F>
 inline int launch1d(int N, const char* what, F f) {
     if (N <= 0) return GS_OK;
@@ -368,6 +385,16 @@ int gs_pack_splats(const void* uvs, const void* opacity, const void* conic, cons
                    k_pack<T><<<g, b, 0, s>>>((const T*)uvs, (const T*)opacity, (const T*)conic,
                                              (const T*)rgb, V, (T*)packed);
                }));
+}
+
+int gs_z_backward(const int32_t* rank, const void* grad_z, const void* camera_T_world, int v_base, int N,
+                  void* grad_xyz, void* stream) {
+    GS_REQUIRE(N <= 0 || (rank != nullptr && grad_z != nullptr && camera_T_world != nullptr && grad_xyz != nullptr),
+               "z_backward: rank, grad_z, camera_T_world or grad_xyz is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    return launch1d(N, "z_backward", [&](dim3 g, dim3 b) {
+        k_z_bwd<<<g, b, 0, s>>>(rank, (const float*)grad_z, (const float*)camera_T_world, v_base, N, (float*)grad_xyz);
+    });
 }
 
 }  // extern "C"

@@ -2249,6 +2249,259 @@ __global__ __launch_bounds__(RB) void k_render_depth(const float* __restrict__ p
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// differentiable depth and accumulated opacity (no reference counterpart), fp32, one colour coefficient
+// ---------------------------------------------------------------------------------------------------
+// For pixel p and the entries k < num_splats_per_pixel[p] the colour forward walked, with alpha_k and the
+// contribute decision formed by render_tile_fwd_fused's own expressions (zalpha_alpha below):
+//   T_k = prod_{j < k, contributing} (1 - alpha_j)      w_k = alpha_k T_k
+//   depth[p] = sum w_k z_k  (z = xyz_camera_frame[:, 2])      alpha[p] = sum w_k      T_end = the product over all
+// No background, no normalisation.  The kernels stand BESIDE the colour kernels (whose ISA is left alone): plain walks
+// of the touch masks, one record read per visit, no flags, costs, segments or handed-over masks.  They read
+// num_splats_per_pixel and never look beyond it, so they need no saturation test and are correct on prefix-sorted
+// lists (a tile is ordered as far as any of its pixels walked).  The staged record's first colour word (word 9, which
+// nobody here reads as a colour) carries z.
+//
+// alpha of one (pixel, staged record) pair and whether it contributes -- the forward's decisions, bit for bit: the
+// cutoff radius, the IEEE quotient from the stored reciprocal, exp_neg_half, zero unless mh > 0, alpha >= 1/255.
+struct ZalphaVisit {
+    float du, dv, mh, norm_prob, alpha;
+    bool contrib;
+};
+__device__ __forceinline__ ZalphaVisit zalpha_alpha(const Vec4<float>& g0, const Vec4<float>& g1, float rdet, float pu,
+                                                    float pv, bool reach) {
+    ZalphaVisit o;
+    o.du = pu - g0.x;
+    o.dv = pv - g0.y;
+    o.mh = 0.0f; o.norm_prob = 0.0f; o.alpha = 0.0f;
+    o.contrib = false;
+    if (reach && !(o.du * o.du + o.dv * o.dv > g0.z)) {
+        const float tb = g1.y + g1.y;
+        o.mh = div_by_reciprocal(g1.z * o.du * o.du - tb * o.du * o.dv + g1.x * o.dv * o.dv, g1.w, rdet);
+        o.norm_prob = exp_neg_half(o.mh);
+        o.alpha = g0.w * o.norm_prob;
+        o.contrib = (o.mh > 0.0f) & !(o.alpha < Thr<float>::alpha_min());
+    }
+    return o;
+}
+
+// the deepest entry any pixel of the workgroup / of this wave walked (0 outside the image); barrier inside
+__device__ __forceinline__ void zalpha_reach(int nsp, int n_tile, int tid, int* s_max, int& n_used, int& wave_used) {
+    int m = nsp;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) m = max(m, __shfl_xor(m, d));
+    if ((tid & 63) == 0) s_max[tid >> 6] = m;
+    __syncthreads();
+    n_used = min(n_tile, max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3])));
+    wave_used = __builtin_amdgcn_readfirstlane(m);
+}
+
+// One workgroup per tile.  Writes depth, alpha and T_end [H, W] of the tile's pixels inside the image.  T_end is
+// stored itself: at alpha = 0.99999 the difference 1 - alpha formed in fp32 is good to about 1 %.
+__global__ __launch_bounds__(RB) void k_render_zalpha_fwd(
+    const float* __restrict__ packed, const float* __restrict__ xyz_cam, const int* __restrict__ ranges,
+    const int* __restrict__ sorted, const int* __restrict__ nsp_in, int W, int H, int ntx, int tile0, int nt,
+    float* __restrict__ depth, float* __restrict__ alpha_out, float* __restrict__ t_out) {
+    constexpr int RCHUNK = 256;
+    constexpr int NW = RCHUNK / 64;
+    __shared__ alignas(16) float s_geom[RCHUNK * GS_PACKED_WIDTH];
+    __shared__ unsigned long long s_mask[4][NW];
+    __shared__ int s_max[4];
+    const int t_local = tile_of_block(blockIdx.x, nt);
+    if (t_local >= nt) return;
+    const int tile = tile0 + t_local;
+    const int tid = threadIdx.x, wave = tid >> 6;
+    const PixelMap px = pixel_of_thread(tile % ntx, tile / ntx, tid);
+    const bool valid = px.u < W && px.v < H;
+    const size_t p = (size_t)px.v * W + px.u;
+    const int s0 = ranges[tile];
+    const int n_tile = ranges[tile + 1] - s0;
+    const int nsp = valid ? nsp_in[p] : 0;
+    int n_used, wave_used;
+    zalpha_reach(nsp, n_tile, tid, s_max, n_used, wave_used);
+    const float pu = float(px.u), pv = float(px.v);
+    float T = 1.0f, D = 0.0f, A = 0.0f;
+    for (int base = 0; base < n_used; base += RCHUNK) {
+        const int cnt = min(RCHUNK, n_used - base);
+        if (base > 0) __syncthreads();   // the previous chunk's readers are done
+        stage_chunk<float, 1>(packed, nullptr, sorted, s0 + base, cnt, tid, s_geom, nullptr, nullptr);
+        if (tid < cnt) s_geom[tid * GS_PACKED_WIDTH + 9] = xyz_cam[(size_t)sorted[s0 + base + tid] * 3 + 2];
+        // (no barrier in between: thread t tests the record thread t staged)
+        build_touch_masks<float, RCHUNK>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
+        __syncthreads();
+        for (int word = 0; word < NW && word * 64 < cnt; word++) {
+            if (base + word * 64 >= wave_used) break;   // wave-uniform: no pixel of the patch walked this far
+            unsigned long long m = wave_uniform(s_mask[wave][word]);
+            while (m) {
+                const int i = word * 64 + __builtin_ctzll(m);
+                m &= m - 1;
+                const int k = base + i;
+                if (k >= wave_used) break;
+                const float* rec = s_geom + i * GS_PACKED_WIDTH;
+                const Vec4<float> g0 = *reinterpret_cast<const Vec4<float>*>(rec);       // u v r2 opacity
+                const Vec4<float> g1 = *reinterpret_cast<const Vec4<float>*>(rec + 4);   // a b c det
+                const Vec4<float> g2 = *reinterpret_cast<const Vec4<float>*>(rec + 8);   // 1/det, z
+                const ZalphaVisit v = zalpha_alpha(g0, g1, g2.x, pu, pv, k < nsp);
+                if (v.contrib) {
+                    const float w = v.alpha * T;
+                    D = __builtin_fmaf(w, g2.y, D);
+                    A += w;
+                    T = __builtin_fmaf(-v.alpha, T, T);   // T (1 - alpha), one rounding
+                }
+            }
+        }
+    }
+    if (valid) {
+        depth[p] = D;
+        alpha_out[p] = A;
+        t_out[p] = T;
+    }
+}
+
+// The true derivative of the two maps (the contribute / stop decisions held constant), back to front from T_end with
+// c_k = g_depth z_k + g_alpha:
+//   T_k = T / (1 - alpha_k)      dL/dalpha_k = T_k c_k - S / (1 - alpha_k)      S += alpha_k T_k c_k      dL/dz_k = g_depth w_k
+// and alpha -> opacity, u, v, conic as k_render_bwd chains them (the per-splat factor -0.5 opacity / det in the flush).
+// No walk quirk is replicated: this output has no reference to be compatible with.  alpha above 0.9999
+// enters the derivative as 0.9999, as in k_render_bwd (Q4).  Seven sums per (wave, entry) -- z | opacity | w du, w dv |
+// conic 3 -- through reduce9_to_slot with two zero inputs into the wave's own LDS slot, the four waves' slots added
+// per chunk, one global atomic per value per (entry, tile): grad_z[g] and columns 3..8 of the [V, 9] slab (columns
+// 0..2 are not touched).  Chunks of 64 entries, from the tile's deepest num_splats_per_pixel to the front, tiles in
+// grid order.
+__global__ __launch_bounds__(RB) void k_render_zalpha_bwd(
+    const float* __restrict__ packed, const float* __restrict__ xyz_cam, const int* __restrict__ ranges,
+    const int* __restrict__ sorted, const int* __restrict__ nsp_in, const float* __restrict__ t_in,
+    const float* __restrict__ g_depth, const float* __restrict__ g_alpha, int W, int H, int ntx, int tile0, int nt,
+    float* __restrict__ slab, float* __restrict__ grad_z) {
+    constexpr int SV = 9;        // width of a slot: z, 0, 0 | w, w du, w dv | conic terms 3
+    constexpr int RCHUNK = 64;
+    __shared__ alignas(16) float s_geom[RCHUNK * GS_PACKED_WIDTH];
+    __shared__ int s_idx[RCHUNK];
+    __shared__ float s_acc[4 * RCHUNK * SV];   // [wave][splat][9]
+    __shared__ int s_max[4];
+    __shared__ unsigned long long s_mask[4][1];
+    __shared__ unsigned long long s_hit[4];    // slots written by each wave
+    const int t_local = tile_of_block(blockIdx.x, nt);
+    if (t_local >= nt) return;
+    const int tile = tile0 + t_local;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const PixelMap px = pixel_of_thread(tile % ntx, tile / ntx, tid);
+    const bool valid = px.u < W && px.v < H;
+    const int s0 = ranges[tile];
+    const int n_tile = ranges[tile + 1] - s0;
+    if (n_tile <= 0) return;
+    int nsp = 0;
+    float T = 1.0f, gd = 0.0f, ga = 0.0f;
+    if (valid) {
+        const size_t p = (size_t)px.v * W + px.u;
+        nsp = nsp_in[p];
+        T = t_in[p];
+        if (g_depth != nullptr) gd = g_depth[p];
+        if (g_alpha != nullptr) ga = g_alpha[p];
+    }
+    int n_used, wave_used;
+    zalpha_reach(nsp, n_tile, tid, s_max, n_used, wave_used);
+    if (n_used <= 0) return;
+    const float pu = float(px.u), pv = float(px.v);
+    const int slot_off = slot_lane_offset(lane);
+    const bool slot_stores = slot_off >= 0;
+    const int slot_lane_base = wave * RCHUNK * SV + (slot_stores ? slot_off : 0);
+    float S = 0.0f;   // sum of alpha_j T_j c_j over the contributors behind the current entry
+    for (int chunk = (n_used - 1) / RCHUNK; chunk >= 0; chunk--) {
+        const int base = chunk * RCHUNK;
+        const int cnt = min(RCHUNK, n_used - base);
+        __syncthreads();   // previous chunk fully flushed
+        stage_chunk<float, 1>(packed, nullptr, sorted, s0 + base, cnt, tid, s_geom, nullptr, s_idx);
+        if (tid < cnt) s_geom[tid * GS_PACKED_WIDTH + 9] = xyz_cam[(size_t)s_idx[tid] * 3 + 2];
+        // (no barrier in between: thread t tests the record thread t staged)
+        build_touch_masks<float, RCHUNK>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
+        __syncthreads();
+        unsigned long long m = wave_uniform(s_mask[wave][0]);
+        unsigned long long hit = 0;   // the entries of this chunk whose slot the wave wrote
+        while (m) {
+            const int i = 63 - __builtin_clzll(m);
+            m &= ~(1ull << i);
+            const int k = base + i;
+            if (k >= wave_used) continue;   // wave-uniform: no pixel of the patch walked this far
+            const float* rec = s_geom + i * GS_PACKED_WIDTH;
+            const Vec4<float> g0 = *reinterpret_cast<const Vec4<float>*>(rec);       // u v r2 opacity
+            const Vec4<float> g1 = *reinterpret_cast<const Vec4<float>*>(rec + 4);   // a b c det
+            const Vec4<float> g2 = *reinterpret_cast<const Vec4<float>*>(rec + 8);   // 1/det, z
+            const ZalphaVisit v = zalpha_alpha(g0, g1, g2.x, pu, pv, k < nsp);
+            if (ballot(v.contrib) == 0) continue;   // every reaching lane skipped the entry
+            float gz = 0.0f, w = 0.0f;
+            if (v.contrib) {
+                float alpha = v.alpha;
+                if (alpha > Thr<float>::sat_gt()) alpha = Thr<float>::alpha_cap();   // min(0.9999, .)
+                const float r1ma = fast_rcp(1.0f - alpha);
+                const float c = __builtin_fmaf(gd, g2.y, ga);
+                T = T * r1ma;                        // T_k: the transmittance in front of the entry
+                const float aT = alpha * T;          // w_k
+                const float dalpha = T * c - S * r1ma;
+                S = __builtin_fmaf(aT, c, S);
+                gz = gd * aT;
+                w = v.norm_prob * dalpha;
+            }
+            float val[9];
+            const float du2 = v.du * v.du, dv2 = v.dv * v.dv, duv = v.du * v.dv;
+            val[0] = gz; val[1] = 0.0f; val[2] = 0.0f;
+            val[3] = w; val[4] = w * v.du; val[5] = w * v.dv;
+            val[6] = (dv2 - g1.z * v.mh) * w;
+            val[7] = (g1.y * v.mh - duv) * w;
+            val[8] = (du2 - g1.x * v.mh) * w;
+            int slot_i = i * SV;
+            asm volatile("" : "+s"(slot_i));
+            reduce9_to_slot(val, slot_stores, s_acc, slot_lane_base + slot_i);
+            hit |= 1ull << i;
+        }
+        if (lane == 0) s_hit[wave] = hit;
+        __syncthreads();
+        // the flush, as k_render_bwd's.  Phase 1, thread = entry: add the slots of the waves that wrote it, in wave
+        // order, apply the per-splat factors and park the row in wave 0's slot of the same entry
+        if (tid < cnt) {
+            float a[SV];
+#pragma unroll
+            for (int j = 0; j < SV; j++) a[j] = 0;
+#pragma unroll
+            for (int w4 = 0; w4 < 4; w4++) {
+                if ((s_hit[w4] >> tid) & 1ull) {
+                    const float* sl = s_acc + (w4 * RCHUNK + tid) * SV;
+#pragma unroll
+                    for (int j = 0; j < SV; j++) a[j] += sl[j];
+                }
+            }
+            const float* rec = s_geom + tid * GS_PACKED_WIDTH;
+            const float ca = rec[4], cb = rec[5], cc = rec[6];
+            const float kf = -0.5f * rec[3] * rec[8];
+            const float Mu = a[4], Mv = a[5];
+            a[4] = -2.0f * kf * (cc * Mu - cb * Mv);
+            a[5] = -2.0f * kf * (ca * Mv - cb * Mu);
+            a[6] *= kf;
+            a[7] *= kf;
+            a[8] *= kf;
+            float* row = s_acc + tid * SV;
+#pragma unroll
+            for (int j = 0; j < SV; j++) row[j] = a[j];
+        }
+        __syncthreads();
+        // Phase 2, nine lanes = one row (seven rows per wave instruction); rows of zeros stay untouched, and so do
+        // the slab's colour columns
+        const int sub = lane / SV, col = lane - sub * SV;   // lane 63: idle
+        for (int r0 = wave * 7; r0 < cnt; r0 += 28) {
+            const int r = r0 + sub;
+            const bool in = lane < 63 && r < cnt;
+            const float v = in ? s_acc[r * SV + col] : 0.0f;
+            const unsigned long long nz = ballot(v != 0.0f);
+            const bool any = in && ((nz >> (sub * SV)) & 0x1ffull) != 0;
+            if (any) {
+                const int g = s_idx[r];
+                if (col == 0) global_add(grad_z + g, v);
+                else if (col >= 3) global_add(slab + (size_t)g * SV + col, v);
+            }
+        }
+    }
+}
+
 }  // namespace gs
 
 using namespace gs;
@@ -2711,6 +2964,45 @@ int gs_render_depth(const void* packed, const void* xyz_camera_frame, const int3
                                        tile_ranges, sorted_gaussians, W, H, ntx, nt,
                                        alpha_threshold, (float*)depth_image);
     return check_launch("render_depth");
+}
+
+int gs_render_zalpha(const void* packed, const void* xyz_camera_frame, const int32_t* tile_ranges,
+                     const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel, int W, int H,
+                     int tile_row0, int tile_row1, void* depth, void* alpha, void* transmittance, void* stream) {
+    GS_REQUIRE(W > 0 && H > 0, "image must be non-empty");
+    GS_REQUIRE(tile_ranges != nullptr && num_splats_per_pixel != nullptr,
+               "render_zalpha: tile_ranges or num_splats_per_pixel is NULL");
+    GS_REQUIRE(depth != nullptr && alpha != nullptr && transmittance != nullptr, "render_zalpha: an output is NULL");
+    GS_REQUIRE(((uintptr_t)packed & 15) == 0, "render_zalpha: packed must be 16-byte aligned");
+    if (int e = check_rows(H, tile_row0, tile_row1)) return e;
+    const int ntx = (W + 15) / 16;
+    const int nt = (tile_row1 - tile_row0) * ntx;
+    if (nt == 0) return GS_OK;
+    // (packed, xyz_camera_frame and sorted_gaussians are only read where a list has entries: V == 0 passes anything)
+    k_render_zalpha_fwd<<<render_grid(nt), RB, 0, (hipStream_t)stream>>>(
+        (const float*)packed, (const float*)xyz_camera_frame, tile_ranges, sorted_gaussians, num_splats_per_pixel, W, H,
+        ntx, tile_row0 * ntx, nt, (float*)depth, (float*)alpha, (float*)transmittance);
+    return check_launch("render_zalpha");
+}
+
+int gs_render_zalpha_backward(const void* packed, const void* xyz_camera_frame, const int32_t* tile_ranges,
+                              const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel,
+                              const void* transmittance, const void* grad_depth, const void* grad_alpha, int W, int H,
+                              int tile_row0, int tile_row1, void* grad_slab, void* grad_z, void* stream) {
+    GS_REQUIRE(W > 0 && H > 0, "image must be non-empty");
+    GS_REQUIRE(tile_ranges != nullptr && num_splats_per_pixel != nullptr && transmittance != nullptr,
+               "render_zalpha_backward: tile_ranges, num_splats_per_pixel or transmittance is NULL");
+    GS_REQUIRE(((uintptr_t)packed & 15) == 0, "render_zalpha_backward: packed must be 16-byte aligned");
+    if (int e = check_rows(H, tile_row0, tile_row1)) return e;
+    const int ntx = (W + 15) / 16;
+    const int nt = (tile_row1 - tile_row0) * ntx;
+    if (nt == 0 || (grad_depth == nullptr && grad_alpha == nullptr)) return GS_OK;   // nothing to add
+    GS_REQUIRE(grad_slab != nullptr && grad_z != nullptr, "render_zalpha_backward: grad_slab or grad_z is NULL");
+    k_render_zalpha_bwd<<<render_grid(nt), RB, 0, (hipStream_t)stream>>>(
+        (const float*)packed, (const float*)xyz_camera_frame, tile_ranges, sorted_gaussians, num_splats_per_pixel,
+        (const float*)transmittance, (const float*)grad_depth, (const float*)grad_alpha, W, H, ntx, tile_row0 * ntx, nt,
+        (float*)grad_slab, (float*)grad_z);
+    return check_launch("render_zalpha_backward");
 }
 
 }  // extern "C"

@@ -17,6 +17,10 @@ to the reference-shaped path in splat_py.rasterize (still HIP kernels, never a C
 
 The four stages are plain functions (preprocess_forward, render_forward, render_backward,
 preprocess_backward) that gaussian_splatting_amd.sharded composes differently for multi-GPU frames.
+
+rasterize_rgbd is the same frame with two more differentiable outputs, depth and accumulated opacity [H, W]
+(_RenderRGBD: gs_render_zalpha / gs_render_zalpha_backward next to the colour kernels, gs_z_backward behind the
+per-Gaussian backward).
 """
 import os
 from types import SimpleNamespace
@@ -101,6 +105,7 @@ def last_flags(clear=False):
 # it -- inside the native module when that is loaded (its backward runs without the interpreter), else _last_slab
 _keep_slab = False
 _last_slab = None
+_last_grad_z = None   # rasterize_rgbd frames: dL/dz [V] of the visible Gaussians, kept with the slab
 _slab_slot = None   # the native module holding the slot, fixed by keep_last_slab(True)
 
 
@@ -109,8 +114,8 @@ def keep_last_slab(on):
     latest per-Gaussian backward.  The render backward's summation order differs from run to run, so a gradient
     derived from the slab (camera_T_world's) can only be checked against the slab it was computed from.  Every call
     drops what was kept."""
-    global _keep_slab, _last_slab, _slab_slot
-    _keep_slab, _last_slab = bool(on), None
+    global _keep_slab, _last_slab, _slab_slot, _last_grad_z
+    _keep_slab, _last_slab, _last_grad_z = bool(on), None, None
     if _native_mod is not None:
         _native_mod.keep_last_slab(False)
     _slab_slot = native() if on else None
@@ -122,6 +127,12 @@ def last_slab():
     """the [V, 9] slab (rgb 3 | opacity 1 | uv 2 | conic 3) of the latest per-Gaussian backward since
     keep_last_slab(True), whichever orchestration ran it; None if there was none"""
     return _slab_slot.last_slab() if _slab_slot is not None else _last_slab
+
+
+def last_grad_z():
+    """dL/dz [V] (z = xyz_camera_frame[:, 2]) that the latest rasterize_rgbd backward since keep_last_slab(True) handed
+    to the per-Gaussian node next to the slab; None if that frame's depth went unused or there was none"""
+    return _last_grad_z
 
 
 def _note_slab(slab, V):
@@ -578,32 +589,58 @@ def render_forward(packed, rgb, ranges, sorted_g, keys, background_rgb, height, 
 
 
 def render_backward(packed, rgb, ranges, sorted_g, background_rgb, nsp, fw, grad_image, height, width, tile_rows,
-                    V, tile_cost=None, backward_mode=None, seg_state=None, cut=None):
+                    V, tile_cost=None, backward_mode=None, seg_state=None, cut=None, tail=0):
     """-> the slab [V, 9] of accumulated render gradients (rgb 3 | opacity 1 | uv 2 | conic 3).
+    tail > 0 (rasterize_rgbd): -> (slab, float[tail]); the tail lies behind the slab's rows in the same allocation and
+    is cleared by the same prologue launch.  grad_image None: the slab is cleared and no colour backward runs.
     tile_cost: render_forward's fourth output (the tiles are then started longest-first).
     seg_state: render_forward's fifth output; non-empty -> one workgroup per (tile, depth segment).
     backward_mode: _hip.GS_BACKWARD_COMPAT / _EXACT, per call (ABI 5); None = the process default at the call"""
     nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
     row0, row1 = tile_rows if tile_rows is not None else (0, nty)
     # (cleared by the call itself, in the launch that also orders the tiles: zero_slab_rows)
-    slab = torch.empty(max(V, 1), SLAB_WIDTH, dtype=torch.float32, device=packed.device)
+    rows = max(V, 1)
+    slab = torch.empty(rows + (tail + SLAB_WIDTH - 1) // SLAB_WIDTH, SLAB_WIDTH, dtype=torch.float32, device=packed.device)
     cost = order = None
     seg_on = seg_state is not None and seg_state.numel() > 0
     # longest-first only pays where a workgroup lives long enough for the kernel's tail to matter: lists of a
     # few hundred entries per tile (workload B, 52 per tile: the order kernel's 6 us are not won back)
-    if (not seg_on and tile_cost is not None and tile_cost.numel() > 0
+    if (grad_image is not None and not seg_on and tile_cost is not None and tile_cost.numel() > 0
             and sorted_g.shape[0] >= LPT_MIN_MEAN_LIST * tile_cost.numel()):
         cost = tile_cost
         order = torch.empty(tile_cost.numel() + 8, dtype=torch.int32, device=packed.device)
     # one prologue launch (clear the slab + order the tiles), then the render kernel alone in its entry
     _hip.call("gs_render_backward_prologue", _p(slab), slab.shape[0], _p(cost), _p(order), width, height, row0, row1,
               _stream())
-    _hip.call("gs_render_tiles_backward_slab", _p(packed), _p(rgb), _p(ranges), _p(sorted_g), _p(background_rgb),
-              _p(nsp), _p(fw), _p(grad_image), width, height, row0, row1, _p(slab), 0, None, _p(order),
-              _p(seg_state) if seg_on else None, _p(cut.flags) if cut is not None else None,
-              _p(cut.full_ranges) if cut is not None else None, _p(cut.overflow_sorted) if cut is not None else None,
-              _hip.GS_BACKWARD_DEFAULT if backward_mode is None else int(backward_mode), _stream())
+    if grad_image is not None:
+        _hip.call("gs_render_tiles_backward_slab", _p(packed), _p(rgb), _p(ranges), _p(sorted_g), _p(background_rgb),
+                  _p(nsp), _p(fw), _p(grad_image), width, height, row0, row1, _p(slab), 0, None, _p(order),
+                  _p(seg_state) if seg_on else None, _p(cut.flags) if cut is not None else None,
+                  _p(cut.full_ranges) if cut is not None else None, _p(cut.overflow_sorted) if cut is not None else None,
+                  _hip.GS_BACKWARD_DEFAULT if backward_mode is None else int(backward_mode), _stream())
+    if tail:
+        return slab[:V], slab.view(-1)[rows * SLAB_WIDTH:rows * SLAB_WIDTH + tail]
     return slab[:V]
+
+
+def zalpha_forward(packed, xyz_cam, ranges, sorted_g, nsp, height, width):
+    """-> depth, alpha, T_end, each [H, W] (gs_render_zalpha): the differentiable depth and accumulated opacity of the
+    frame whose colour forward left nsp; one allocation"""
+    nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
+    buf = torch.empty(3, height, width, dtype=torch.float32, device=packed.device)
+    _hip.call("gs_render_zalpha", _p(packed), _p(xyz_cam), _p(ranges), _p(sorted_g), _p(nsp), width, height, 0, nty,
+              _p(buf[0]), _p(buf[1]), _p(buf[2]), _stream())
+    return buf[0], buf[1], buf[2]
+
+
+def zalpha_backward(packed, xyz_cam, ranges, sorted_g, nsp, t_end, grad_depth, grad_alpha, height, width, slab, grad_z):
+    """adds the depth / alpha maps' gradients to columns 3..8 of the (cleared or colour-filled) slab and to grad_z
+    (gs_render_zalpha_backward); either grad may be None"""
+    nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
+    gd = grad_depth.contiguous() if grad_depth is not None else None
+    ga = grad_alpha.contiguous() if grad_alpha is not None else None
+    _hip.call("gs_render_zalpha_backward", _p(packed), _p(xyz_cam), _p(ranges), _p(sorted_g), _p(nsp), _p(t_end),
+              _p(gd), _p(ga), width, height, 0, nty, _p(slab), _p(grad_z), _stream())
 
 
 def _as_slab(g_uv, g_conic, g_opa, g_rgb, V, dev):
@@ -629,12 +666,14 @@ class _Preprocess(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, width, height, near_thresh,
                 far_thresh, cull_mask_padding, mh_dist, tile_rows, sort_prefix=0, background_rgb=None, cut_box=None,
-                adam_plan=None, pose_grad=False):
+                adam_plan=None, pose_grad=False, z_out=False):
         # cut_box: a list; when the frame takes the depth cut its record (what _Render's two passes need) is left in it
         # adam_plan: train_ops.FusedRasterAdam's plan -> the backward steps quaternion, scale, opacity, rgb and sh
         # itself (preprocess_backward_adam) and returns a gradient for xyz only
         # pose_grad: the frame gives camera_T_world its gradient when it requires one (pose_backward); False keeps
         # the pose a constant (multi-GPU frames: the sum would need an all-reduce; per-pixel SH: its rays depend on it)
+        # z_out (rasterize_rgbd only): one more output BEHIND everything else, z = xyz_camera_frame[:V, 2] as a
+        # differentiable tensor -- the handle through which the depth map's dL/dz comes back to this node
         ntx = (width + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
         nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
         row0, row1 = tile_rows if tile_rows is not None else (0, nty)
@@ -670,27 +709,42 @@ class _Preprocess(torch.autograd.Function):
         ctx.set_materialize_grads(False)   # no zero tensors for the auxiliary outputs in backward
         ctx.adam_plan = adam_plan
         ctx.pose_grad = pose_grad
-        ctx.f = SimpleNamespace(N=f.N, V=V, n_sh=f.n_sh, center=f.center, rank=f.rank, opacity_act=f.opacity_act)
+        ctx.z_out = z_out
+        ctx.f = SimpleNamespace(N=f.N, V=V, n_sh=f.n_sh, center=f.center, rank=f.rank, opacity_act=f.opacity_act,
+                                vis_idx=f.vis_idx[:V])
         uv_v, conic_v, opa_v, rgb_v = f.uv[:V], f.conic[:V], f.opacity_act[:V], f.rgb_render[:V]
         aux = (f.packed, f.xyz_cam[:V], f.culling_mask, f.ranges, f.sorted_g, f.vis_idx[:V], f.keys) + tuple(pre)
         ctx.mark_non_differentiable(*aux)
+        if z_out:
+            return (uv_v, conic_v, opa_v, rgb_v) + aux + (f.xyz_cam[:V, 2].contiguous(),)
         return (uv_v, conic_v, opa_v, rgb_v) + aux
 
     @staticmethod
     def backward(ctx, g_uv, g_conic, g_opa, g_rgb, *unused):
         xyz, quaternion, scale, camera_T_world, K = ctx.saved_tensors
         slab = _as_slab(g_uv, g_conic, g_opa, g_rgb, ctx.f.V, xyz.device)
+        g_z = unused[-1].contiguous() if (ctx.z_out and unused[-1] is not None and ctx.f.V > 0) else None
         if _keep_slab:
+            global _last_grad_z
             _note_slab(slab, ctx.f.V)
+            _last_grad_z = g_z
         # (before the fused optimizer step, which overwrites the quaternion and scale the pose terms read)
         g_pose = None
         if ctx.pose_grad and ctx.needs_input_grad[6]:
             g_pose = pose_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab)
+            if g_z is not None:
+                # the direct term of z = T[2, 0:3] . xyz + T[2, 3] (the slab's terms above already hold the depth map's
+                # uv / conic columns): plumbing on the visible rows, not a hot path
+                gz64 = g_z.double()   # (float64 sums: V terms of mixed sign)
+                g_pose[2, :3] += (gz64 @ xyz.index_select(0, ctx.f.vis_idx.long()).double()).float()
+                g_pose[2, 3] += gz64.sum().float()
         if ctx.adam_plan is not None:
             grads = (preprocess_backward_adam(xyz, camera_T_world, K, ctx.f, slab, ctx.adam_plan),) + (None,) * 5
         else:
             grads = preprocess_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab)
-        return grads + (g_pose,) + (None,) * 13
+        if g_z is not None:
+            _hip.call("gs_z_backward", _p(ctx.f.rank), _p(g_z), _p(camera_T_world), 0, ctx.f.N, _p(grads[0]), _stream())
+        return grads + (g_pose,) + (None,) * 14
 
 
 class _Render(torch.autograd.Function):
@@ -722,6 +776,41 @@ class _Render(torch.autograd.Function):
             ctx.slab_sync(slab.view(-1))   # multi-GPU: sum the partial gradients of all bands in place
         # the four gradients are views of the one slab; _Preprocess.backward recognises that
         return (slab[:, SLAB_UV], slab[:, SLAB_CONIC], slab[:, SLAB_OPACITY], slab[:, SLAB_RGB]) + (None,) * 12
+
+
+class _RenderRGBD(torch.autograd.Function):
+    """_Render with two more outputs, depth and alpha [H, W] (gs_render_zalpha on the lists and the splat counts the
+    colour forward left).  One backward for the three: the prologue clears the slab and the dL/dz tail, the colour
+    backward runs if the image has a gradient, gs_render_zalpha_backward if depth or alpha has one, and _Preprocess
+    gets the one slab plus dL/dz.  An unused output costs no launch."""
+
+    @staticmethod
+    def forward(ctx, uv, conic, opacity, rgb, z, packed, xyz_cam, ranges, sorted_g, background_rgb, height, width,
+                keys=None, sort_prefix=0, rendered=None):
+        image, nsp, fw, cost, seg = rendered if rendered else render_forward(
+            packed, rgb, ranges, sorted_g, keys, background_rgb, height, width, None, sort_prefix)
+        depth, alpha, t_end = zalpha_forward(packed, xyz_cam, ranges, sorted_g, nsp, height, width)
+        ctx.save_for_backward(packed, rgb, xyz_cam, ranges, sorted_g, background_rgb, nsp, fw, cost, seg, t_end)
+        ctx.set_materialize_grads(False)
+        ctx.dims = (height, width, uv.shape[0])
+        ctx.backward_mode = _hip.get_backward_mode()   # the frame's mode is the default at its forward
+        return image, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_image, grad_depth, grad_alpha):
+        packed, rgb, xyz_cam, ranges, sorted_g, background_rgb, nsp, fw, cost, seg, t_end = ctx.saved_tensors
+        height, width, V = ctx.dims
+        if grad_image is None and grad_depth is None and grad_alpha is None:
+            return (None,) * 15
+        geometric = grad_depth is not None or grad_alpha is not None
+        slab, g_z = render_backward(packed, rgb, ranges, sorted_g, background_rgb, nsp, fw,
+                                    grad_image.contiguous() if grad_image is not None else None, height, width, None,
+                                    V, cost, ctx.backward_mode, seg, tail=max(V, 1))
+        if geometric and V > 0:   # (nothing visible: nothing to add, and an empty slab has no address)
+            zalpha_backward(packed, xyz_cam, ranges, sorted_g, nsp, t_end, grad_depth, grad_alpha, height, width,
+                            slab, g_z)
+        return (slab[:, SLAB_UV], slab[:, SLAB_CONIC], slab[:, SLAB_OPACITY], slab[:, SLAB_RGB],
+                g_z[:V] if grad_depth is not None else None) + (None,) * 10   # (alpha alone leaves dL/dz zero)
 
 
 class _GatherRows(torch.autograd.Function):
@@ -914,3 +1003,44 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
                                              xyz_camera_frame=xyz_cam, tile_ranges=ranges,
                                              sorted_gaussians=sorted_g, vis_idx=vis_idx)
     return image, culling_mask, uv
+
+
+def rasterize_rgbd(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+                   use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None, slab_sync=None,
+                   frame_hook=None, adam_plan=None):
+    """rasterize() with a differentiable depth map and accumulated opacity:
+
+        image, depth, alpha, culling_mask, uv = rasterize_rgbd(...)
+
+    image, culling_mask and uv are those of rasterize() on the same inputs, bit for bit.  depth [H, W] = sum_k w_k z_k
+    with z the camera-frame z of the Gaussian and w_k = alpha_k T_k the compositing weights of the entries the colour
+    forward walked; alpha [H, W] = sum_k w_k.  No background term, depth is not normalised (callers form
+    depth / alpha).  All three carry gradients to the Gaussians' parameters and, when it requires one, to
+    camera_T_world; the backward of depth and alpha is their true derivative (DESIGN.md "Depth and alpha maps").
+    Whole single-GPU fp32 frames in the SH-precompute colour mode, Python orchestration, depth cut off: anything
+    else raises RuntimeError (the trailing keyword arguments exist only to say so)."""
+    g = gaussians
+    _require(tile_rows is None and not (return_aux or grad_sync or slab_sync or frame_hook),
+             "rasterize_rgbd serves whole single-GPU frames: tile_rows, return_aux, grad_sync, slab_sync and "
+             "frame_hook are not supported")
+    _require(adam_plan is None, "rasterize_rgbd does not take the fused optimizer step (adam_plan)")
+    _require(g.sh is None or use_sh_precompute,
+             "rasterize_rgbd needs the SH-precompute colour mode: per-pixel SH (use_sh_precompute=False) is not supported")
+    tensors = [t for t in (g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
+                           background_rgb) if t is not None]
+    _require(all(t.is_cuda and t.dtype == torch.float32 for t in tensors),
+             "rasterize_rgbd needs float32 tensors on the GPU (no fp64, no CPU path)")
+    validate(g, camera_T_world, camera, background_rgb)
+    sh = g.sh.contiguous() if g.sh is not None else None
+    sort_prefix = _hip.GS_SORT_PREFIX if SORT_PREFIX else 0
+    height, width = int(camera.height), int(camera.width)
+    # (no cut_box: the depth cut stays off -- a cut frame's flagged tiles keep their lists elsewhere)
+    out = _Preprocess.apply(
+        g.xyz.contiguous(), g.quaternion.contiguous(), g.scale.contiguous(), g.opacity.contiguous(),
+        g.rgb.contiguous(), sh, camera_T_world.contiguous(), camera.K.contiguous(), width, height, near_thresh,
+        far_thresh, cull_mask_padding, mh_dist, None, sort_prefix, background_rgb.contiguous(), None, None, True, True)
+    uv, conic, opacity, rgb, packed, xyz_cam, culling_mask, ranges, sorted_g, _vis_idx, keys = out[:11]
+    image, depth, alpha = _RenderRGBD.apply(uv, conic, opacity, rgb, out[-1], packed, xyz_cam, ranges, sorted_g,
+                                            background_rgb.contiguous(), height, width, keys, sort_prefix,
+                                            tuple(out[11:-1]))
+    return image, depth, alpha, culling_mask, uv

@@ -450,6 +450,43 @@ int gs_render_depth(const void* packed, const void* xyz_camera_frame, const int3
                     const int32_t* sorted_gaussians, int W, int H, float alpha_threshold,
                     void* depth_image, void* stream);
 
+/* Differentiable depth and accumulated opacity of a rendered frame (ABI 11; no reference counterpart), fp32, for the
+ * packed records of gs_pack_splats / gs_preprocess_forward.  For pixel p and the list entries
+ * k < num_splats_per_pixel[p] (what the colour forward walked, in its order), with alpha_k and the contribute decision
+ * formed exactly as gs_render_tiles_packed forms them (cutoff radius, alpha >= 1/255):
+ *   T_k = prod_{j < k, contributing} (1 - alpha_j),  w_k = alpha_k T_k,
+ *   depth[p] = sum w_k z_k  with z = xyz_camera_frame[:, 2] (camera-frame z, NOT the range gs_render_depth writes),
+ *   alpha[p] = sum w_k,  transmittance[p] = T behind the last contributor (= 1 - alpha[p], stored itself because the
+ *   difference loses its digits as alpha approaches 1).
+ * No background term and no normalisation (callers form depth / alpha).  Nothing beyond num_splats_per_pixel is
+ * read, so the lists may be prefix-sorted (gs_render_tiles_prefix orders a tile as far as any of its pixels walked).
+ *   inputs    packed[V,12], xyz_camera_frame[V,3], tile_ranges, sorted_gaussians, num_splats_per_pixel[H,W] as
+ *             gs_render_tiles_packed takes / writes them
+ *   outputs   depth[H,W], alpha[H,W], transmittance[H,W]: written for every pixel of the tile rows
+ *             [tile_row0, tile_row1), untouched elsewhere.  Empty lists (V == 0) give 0, 0, 1. */
+int gs_render_zalpha(const void* packed, const void* xyz_camera_frame, const int32_t* tile_ranges,
+                     const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel, int W, int H,
+                     int tile_row0, int tile_row1, void* depth, void* alpha, void* transmittance, void* stream);
+/* Backward of the above: the TRUE derivative of the two maps, the contribute / stop decisions held constant (no
+ * walk quirk of render_backward.cu is replicated; alpha above 0.9999 enters as 0.9999, Q4).
+ *   grad_depth, grad_alpha   [H,W]; either may be NULL = all zeros (both NULL: nothing is launched)
+ *   transmittance            what gs_render_zalpha wrote
+ *   grad_slab                [V,9] (rgb 3 | opacity 1 | uv 2 | conic 3, the layout gs_preprocess_backward reads):
+ *                            columns 3..8 accumulated, columns 0..2 untouched
+ *   grad_z                   float[V], accumulated: dL/dz of each visible Gaussian (gs_z_backward takes it on)
+ * Both are added into (one atomic per value per (list entry, tile)); the caller zeroes them, e.g. with
+ * gs_render_backward_prologue.  Rows of Gaussians no pixel uses are not touched. */
+int gs_render_zalpha_backward(const void* packed, const void* xyz_camera_frame, const int32_t* tile_ranges,
+                              const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel,
+                              const void* transmittance, const void* grad_depth, const void* grad_alpha, int W, int H,
+                              int tile_row0, int tile_row1, void* grad_slab, void* grad_z, void* stream);
+/* z = camera_T_world[2,0:3] . xyz + camera_T_world[2,3] back to the positions: for every Gaussian i of the N with
+ * rank[i] >= 0, grad_xyz[i,:] += grad_z[rank[i] - v_base] * camera_T_world[2,0:3] (one fused multiply-add per
+ * element; culled rows untouched).  rank, v_base and slices as in gs_preprocess_backward, after which it runs on the
+ * same grad_xyz[N,3].  One thread per Gaussian, no atomics.  N == 0 launches nothing. */
+int gs_z_backward(const int32_t* rank, const void* grad_z, const void* camera_T_world, int v_base, int N,
+                  void* grad_xyz, void* stream);
+
 /* Cost-balanced bands (multi-GPU; no reference counterpart): the band images of unequal bands are all-gathered as
  * equal chunks of chunk_rows = 16 x (tallest band) + 1 pixel rows, each starting at its rank's band; the last row of
  * a chunk carries the per-tile-row costs of that band (floats; 0 outside the band).
