@@ -2502,6 +2502,413 @@ __global__ __launch_bounds__(RB) void k_render_zalpha_bwd(
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// per-Gaussian feature vectors composited with the frame's weights (no reference counterpart), fp32
+// ---------------------------------------------------------------------------------------------------
+// The depth / alpha walks above with the one channel z generalised to C <= 32 caller-supplied channels:
+//   feature_map[p, c] = sum w_k features[g_k, c]      alpha[p] = sum w_k      T_end
+// with alpha_k, the contribute decision and w_k = alpha_k T_k from zalpha_alpha and the same update order, so alpha and
+// T_end are bit-equal to k_render_zalpha_fwd's and a channel holding z gives its depth.  The kernels are templated on
+// a padded channel count CP and instantiated for CP = 4, 8, 16, 32 (the next one at or above n_channels runs): a
+// feature row is staged into LDS beside the geometry records with a pitch of CP floats (16-byte aligned, read as
+// ds_read_b128 broadcasts), the channels from n_channels to CP - 1 staged as zeros.  Nothing beyond column
+// n_channels - 1 of features, feature_map, grad_feature_map or grad_features is read or written.
+template <int CP>
+__device__ __forceinline__ void stage_features(const float* __restrict__ features, int C, const int* __restrict__ sorted,
+                                               int first, int cnt, int tid, float* s_feat) {
+    // by the whole workgroup: CP consecutive threads read the consecutive words of a row (as stage_chunk's coefficient
+    // rows), RB / CP rows per step -- a thread keeps its channel and moves down the rows, four rows' loads in flight
+    // before the first is stored (one row at a time was two dependent global latencies per step: 16 steps for 64
+    // entries of 32 channels)
+    constexpr int RPS = RB / CP;   // rows per step
+    constexpr int U = 4;
+    const int c = tid % CP, r0 = tid / CP;
+    for (int rb = r0; rb < cnt; rb += U * RPS) {
+        float v[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int r = rb + u * RPS;
+            v[u] = (r < cnt && c < C) ? features[(size_t)sorted[first + r] * C + c] : 0.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int r = rb + u * RPS;
+            if (r < cnt) s_feat[r * CP + c] = v[u];
+        }
+    }
+}
+
+// One workgroup per tile, a wave per 8 x 8 patch.  Writes feature_map [H, W, C], alpha and T_end [H, W] of the tile's
+// pixels inside the image.  LDS: 12 KB of records + CP KB of feature rows.
+template <int CP>
+__global__ __launch_bounds__(RB) void k_render_features_fwd(
+    const float* __restrict__ packed, const float* __restrict__ features, int C, const int* __restrict__ ranges,
+    const int* __restrict__ sorted, const int* __restrict__ nsp_in, int W, int H, int ntx, int tile0, int nt,
+    float* __restrict__ fmap, float* __restrict__ alpha_out, float* __restrict__ t_out) {
+    static_assert(CP % 4 == 0 && CP >= 4 && CP <= 32, "padded channel count");
+    constexpr int RCHUNK = 256;
+    constexpr int NW = RCHUNK / 64;
+    __shared__ alignas(16) float s_geom[RCHUNK * GS_PACKED_WIDTH];
+    __shared__ alignas(16) float s_feat[RCHUNK * CP];
+    __shared__ unsigned long long s_mask[4][NW];
+    __shared__ int s_max[4];
+    const int t_local = tile_of_block(blockIdx.x, nt);
+    if (t_local >= nt) return;
+    const int tile = tile0 + t_local;
+    const int tid = threadIdx.x, wave = tid >> 6;
+    const PixelMap px = pixel_of_thread(tile % ntx, tile / ntx, tid);
+    const bool valid = px.u < W && px.v < H;
+    const size_t p = (size_t)px.v * W + px.u;
+    const int s0 = ranges[tile];
+    const int n_tile = ranges[tile + 1] - s0;
+    const int nsp = valid ? nsp_in[p] : 0;
+    int n_used, wave_used;
+    zalpha_reach(nsp, n_tile, tid, s_max, n_used, wave_used);
+    const float pu = float(px.u), pv = float(px.v);
+    float T = 1.0f, A = 0.0f;
+    float F[CP];
+#pragma unroll
+    for (int c = 0; c < CP; c++) F[c] = 0.0f;
+    for (int base = 0; base < n_used; base += RCHUNK) {
+        const int cnt = min(RCHUNK, n_used - base);
+        if (base > 0) __syncthreads();   // the previous chunk's readers are done
+        stage_chunk<float, 1>(packed, nullptr, sorted, s0 + base, cnt, tid, s_geom, nullptr, nullptr);
+        stage_features<CP>(features, C, sorted, s0 + base, cnt, tid, s_feat);
+        // (no barrier in between: thread t tests the record thread t staged)
+        build_touch_masks<float, RCHUNK>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
+        __syncthreads();
+        for (int word = 0; word < NW && word * 64 < cnt; word++) {
+            if (base + word * 64 >= wave_used) break;   // wave-uniform: no pixel of the patch walked this far
+            unsigned long long m = wave_uniform(s_mask[wave][word]);
+            while (m) {
+                const int i = word * 64 + __builtin_ctzll(m);
+                m &= m - 1;
+                const int k = base + i;
+                if (k >= wave_used) break;
+                const float* rec = s_geom + i * GS_PACKED_WIDTH;
+                const Vec4<float> g0 = *reinterpret_cast<const Vec4<float>*>(rec);       // u v r2 opacity
+                const Vec4<float> g1 = *reinterpret_cast<const Vec4<float>*>(rec + 4);   // a b c det
+                const ZalphaVisit v = zalpha_alpha(g0, g1, rec[8], pu, pv, k < nsp);
+                if (v.contrib) {
+                    const float w = v.alpha * T;
+                    const Vec4<float>* f4 = reinterpret_cast<const Vec4<float>*>(s_feat + i * CP);
+#pragma unroll
+                    for (int c4 = 0; c4 < CP / 4; c4++) {
+                        const Vec4<float> f = f4[c4];
+                        F[4 * c4 + 0] = __builtin_fmaf(w, f.x, F[4 * c4 + 0]);
+                        F[4 * c4 + 1] = __builtin_fmaf(w, f.y, F[4 * c4 + 1]);
+                        F[4 * c4 + 2] = __builtin_fmaf(w, f.z, F[4 * c4 + 2]);
+                        F[4 * c4 + 3] = __builtin_fmaf(w, f.w, F[4 * c4 + 3]);
+                    }
+                    A += w;
+                    T = __builtin_fmaf(-v.alpha, T, T);   // T (1 - alpha), one rounding
+                }
+            }
+        }
+    }
+    if (valid) {
+        float* row = fmap + p * C;
+        if ((C & 3) == 0 && ((uintptr_t)fmap & 15) == 0) {
+            // rows of whole 16-byte words (workgroup-uniform): a quarter of the store instructions; at 32 channels the
+            // map is 128 bytes per pixel and the forward of a short-list frame is bound by writing it
+#pragma unroll
+            for (int c4 = 0; c4 < CP / 4; c4++) {
+                if (4 * c4 < C) {
+                    Vec4<float> v4;
+                    v4.x = F[4 * c4 + 0]; v4.y = F[4 * c4 + 1]; v4.z = F[4 * c4 + 2]; v4.w = F[4 * c4 + 3];
+                    reinterpret_cast<Vec4<float>*>(row)[c4] = v4;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < CP; c++)
+                if (c < C) row[c] = F[c];
+        }
+        alpha_out[p] = A;
+        t_out[p] = T;
+    }
+}
+
+// The true derivative of the two maps (decisions held constant), k_render_zalpha_bwd's walk with
+//   c_k = g_alpha + sum_c g[c] f_k[c]   (a fused multiply-add chain from g_alpha, channels ascending)
+//   T_k = T / (1 - alpha_k)      dL/dalpha_k = T_k c_k - S / (1 - alpha_k)      S += alpha_k T_k c_k
+// The six geometry sums go through reduce9_to_slot (three zero inputs) and the two-phase flush into columns 3..8 of
+// the slab.  The feature gradient dL/df[k, c] = sum_pixels w_k(p) g[p, c] does not: per wave it is the contraction
+// [channels x 64 pixels] x [64 pixels x 16 entries], done with v_mfma_f32_16x16x4_f32 (exact fp32) on batches of 16
+// contributing entries as k_render_bwd_sh contracts its coefficient gradients -- the pixel-side operand g[pixel][channel]
+// stays in registers for the whole walk (y_op, one set of 16 per block of 16 channels), the entries' w_k go to the
+// wave's LDS batch, two accumulator chains per channel block, and the results are added straight to grad_features
+// rows, consecutive lanes on consecutive words of a row.  A batch stays open across chunks (it keeps the Gaussian
+// indices itself) and the partial one is flushed at the end of the walk.  grad_features == nullptr: none of it runs.
+// LDS: 3 KB records + CP / 4 KB feature rows + 9 KB slots + 17 KB batches.
+template <int CP>
+__global__ __launch_bounds__(RB) void k_render_features_bwd(
+    const float* __restrict__ packed, const float* __restrict__ features, int C, const int* __restrict__ ranges,
+    const int* __restrict__ sorted, const int* __restrict__ nsp_in, const float* __restrict__ t_in,
+    const float* __restrict__ g_map, const float* __restrict__ g_alpha, int W, int H, int ntx, int tile0, int nt,
+    float* __restrict__ slab, float* __restrict__ grad_features) {
+    static_assert(CP % 4 == 0 && CP >= 4 && CP <= 32, "padded channel count");
+    constexpr int SV = 9;        // width of a slot: 0, 0, 0 | w, w du, w dv | conic terms 3
+    constexpr int RCHUNK = 64;
+    constexpr int MB = 16;               // entries per MFMA batch (the N of 16x16x4)
+    constexpr int BROW = 64 + 4;         // floats per row of the batch's weight matrix [slot][pixel]
+    constexpr int NBLK = (CP + 15) / 16; // blocks of 16 channels (the M of 16x16x4)
+    constexpr int OW = 16 * NBLK;        // floats per slot of the batch's result [slot][channel]
+    static_assert(64 * 17 <= MB * BROW && MB * OW <= MB * BROW, "scratch uses of the wave's batch rows");
+    __shared__ alignas(16) float s_geom[RCHUNK * GS_PACKED_WIDTH];
+    __shared__ alignas(16) float s_feat[RCHUNK * CP];
+    __shared__ int s_idx[RCHUNK];
+    __shared__ float s_acc[4 * RCHUNK * SV];          // [wave][splat][9]
+    __shared__ alignas(16) float s_B[4 * MB * BROW];  // [wave][slot][pixel] w of the open batch
+    __shared__ int s_bidx[4 * MB];                    // [wave][slot] Gaussian index of the entry
+    __shared__ int s_max[4];
+    __shared__ unsigned long long s_mask[4][1];
+    __shared__ unsigned long long s_hit[4];           // slots written by each wave
+    const int t_local = tile_of_block(blockIdx.x, nt);
+    if (t_local >= nt) return;
+    const int tile = tile0 + t_local;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const PixelMap px = pixel_of_thread(tile % ntx, tile / ntx, tid);
+    const bool valid = px.u < W && px.v < H;
+    const int s0 = ranges[tile];
+    const int n_tile = ranges[tile + 1] - s0;
+    if (n_tile <= 0) return;
+    int nsp = 0;
+    float T = 1.0f, ga = 0.0f;
+    float g[CP];
+#pragma unroll
+    for (int c = 0; c < CP; c++) g[c] = 0.0f;
+    if (valid) {
+        const size_t p = (size_t)px.v * W + px.u;
+        nsp = nsp_in[p];
+        T = t_in[p];
+        if (g_map != nullptr) {
+            if ((C & 3) == 0 && ((uintptr_t)g_map & 15) == 0) {   // rows of whole 16-byte words (workgroup-uniform)
+#pragma unroll
+                for (int c4 = 0; c4 < CP / 4; c4++) {
+                    if (4 * c4 < C) {
+                        const Vec4<float> v4 = reinterpret_cast<const Vec4<float>*>(g_map + p * C)[c4];
+                        g[4 * c4 + 0] = v4.x; g[4 * c4 + 1] = v4.y; g[4 * c4 + 2] = v4.z; g[4 * c4 + 3] = v4.w;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < CP; c++)
+                    if (c < C) g[c] = g_map[p * C + c];
+            }
+        }
+        if (g_alpha != nullptr) ga = g_alpha[p];
+    }
+    int n_used, wave_used;
+    zalpha_reach(nsp, n_tile, tid, s_max, n_used, wave_used);
+    if (n_used <= 0) return;
+    const float pu = float(px.u), pv = float(px.v);
+    const int slot_off = slot_lane_offset(lane);
+    const bool slot_stores = slot_off >= 0;
+    const int slot_lane_base = wave * RCHUNK * SV + (slot_stores ? slot_off : 0);
+    const bool want_f = grad_features != nullptr;   // workgroup-uniform
+
+    // The batch GEMM per block of 16 channels  D[c][j] = sum_k A[c][k] B[k][j]  with  A[c][k] = g[pixel k][channel c]
+    // (constant over the walk) and B[k][j] = w of batch slot j at pixel k.  As in k_render_bwd_sh the contraction index
+    // of MFMA step t, sub-index q (= lane >> 4) is pixel 16 q + t of the wave, so that lane 16 q + j finds its sixteen
+    // B values (slot j, pixels 16 q .. 16 q + 15) contiguous in LDS:  y_op[blk][t] = g[pixel 16 q + t][16 blk + (lane & 15)]
+    float y_op[NBLK][16];
+    float* mine = s_B + wave * MB * BROW;
+    int nb = 0;   // filled slots of the wave's open batch (wave-uniform)
+#pragma unroll
+    for (int blk = 0; blk < NBLK; blk++) {
+#pragma unroll
+        for (int t = 0; t < 16; t++) y_op[blk][t] = 0.0f;
+    }
+    if (want_f) {
+#pragma unroll
+        for (int blk = 0; blk < NBLK; blk++) {
+            // the wave's batch rows as [pixel][17] for the transposition
+#pragma unroll
+            for (int s2 = 0; s2 < 16; s2++)
+                mine[lane * 17 + s2] = (16 * blk + s2 < CP) ? g[(16 * blk + s2 < CP) ? 16 * blk + s2 : 0] : 0.0f;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+            for (int t = 0; t < 16; t++) y_op[blk][t] = mine[(16 * (lane >> 4) + t) * 17 + (lane & 15)];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    // The GEMM of the open batch; its results are the wave's complete sums for (tile patch, entry) and go straight to
+    // the global gradient rows
+    auto mma_flush = [&](int n_filled) {
+        typedef float f32x4 __attribute__((ext_vector_type(4)));
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const int j = lane & 15, q = lane >> 4;
+        const Vec4<float>* brow = reinterpret_cast<const Vec4<float>*>(mine + j * BROW + 16 * q);
+        float b[16];
+#pragma unroll
+        for (int m4 = 0; m4 < 4; m4++) {
+            const Vec4<float> v4 = brow[m4];
+            b[4 * m4 + 0] = v4.x; b[4 * m4 + 1] = v4.y; b[4 * m4 + 2] = v4.z; b[4 * m4 + 3] = v4.w;
+        }
+        f32x4 acc[NBLK];
+#pragma unroll
+        for (int blk = 0; blk < NBLK; blk++) {
+            f32x4 even = {0, 0, 0, 0}, odd = {0, 0, 0, 0};   // two chains: the dependent-issue latency is 40 cycles
+#pragma unroll
+            for (int t = 0; t < 16; t += 2) {
+                even = __builtin_amdgcn_mfma_f32_16x16x4f32(y_op[blk][t], b[t], even, 0, 0, 0);
+                odd = __builtin_amdgcn_mfma_f32_16x16x4f32(y_op[blk][t + 1], b[t + 1], odd, 0, 0, 0);
+            }
+            acc[blk] = even + odd;
+        }
+        // D: column j = lane & 15 (the batch slot), rows c = 4 q + r  ->  the wave's scratch as [slot][OW]
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();   // every lane has read its B values
+#pragma unroll
+        for (int blk = 0; blk < NBLK; blk++) {
+            Vec4<float> v4;
+            v4.x = acc[blk][0]; v4.y = acc[blk][1]; v4.z = acc[blk][2]; v4.w = acc[blk][3];
+            *reinterpret_cast<Vec4<float>*>(mine + j * OW + blk * 16 + 4 * q) = v4;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // consecutive lanes, consecutive words of a gradient row
+        for (int k = lane; k < n_filled * CP; k += 64) {
+            const int row = k / CP, c = k - row * CP;
+            if (c < C) global_add(grad_features + (size_t)s_bidx[wave * MB + row] * C + c, mine[row * OW + c]);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+
+    float S = 0.0f;   // sum of alpha_j T_j c_j over the contributors behind the current entry
+    for (int chunk = (n_used - 1) / RCHUNK; chunk >= 0; chunk--) {
+        const int base = chunk * RCHUNK;
+        const int cnt = min(RCHUNK, n_used - base);
+        __syncthreads();   // previous chunk fully flushed
+        stage_chunk<float, 1>(packed, nullptr, sorted, s0 + base, cnt, tid, s_geom, nullptr, s_idx);
+        stage_features<CP>(features, C, sorted, s0 + base, cnt, tid, s_feat);
+        // (no barrier in between: thread t tests the record thread t staged)
+        build_touch_masks<float, RCHUNK>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
+        __syncthreads();
+        unsigned long long m = wave_uniform(s_mask[wave][0]);
+        unsigned long long hit = 0;   // the entries of this chunk whose slot the wave wrote
+        while (m) {
+            const int i = 63 - __builtin_clzll(m);
+            m &= ~(1ull << i);
+            const int k = base + i;
+            if (k >= wave_used) continue;   // wave-uniform: no pixel of the patch walked this far
+            const float* rec = s_geom + i * GS_PACKED_WIDTH;
+            const Vec4<float> g0 = *reinterpret_cast<const Vec4<float>*>(rec);       // u v r2 opacity
+            const Vec4<float> g1 = *reinterpret_cast<const Vec4<float>*>(rec + 4);   // a b c det
+            const ZalphaVisit v = zalpha_alpha(g0, g1, rec[8], pu, pv, k < nsp);
+            if (ballot(v.contrib) == 0) continue;   // every reaching lane skipped the entry
+            float w = 0.0f, aT = 0.0f;
+            if (v.contrib) {
+                float alpha = v.alpha;
+                if (alpha > Thr<float>::sat_gt()) alpha = Thr<float>::alpha_cap();   // min(0.9999, .)
+                const float r1ma = fast_rcp(1.0f - alpha);
+                float c = ga;
+                const Vec4<float>* f4 = reinterpret_cast<const Vec4<float>*>(s_feat + i * CP);
+#pragma unroll
+                for (int c4 = 0; c4 < CP / 4; c4++) {
+                    const Vec4<float> f = f4[c4];
+                    c = __builtin_fmaf(g[4 * c4 + 0], f.x, c);
+                    c = __builtin_fmaf(g[4 * c4 + 1], f.y, c);
+                    c = __builtin_fmaf(g[4 * c4 + 2], f.z, c);
+                    c = __builtin_fmaf(g[4 * c4 + 3], f.w, c);
+                }
+                T = T * r1ma;                        // T_k: the transmittance in front of the entry
+                aT = alpha * T;                      // w_k
+                const float dalpha = T * c - S * r1ma;
+                S = __builtin_fmaf(aT, c, S);
+                w = v.norm_prob * dalpha;
+            }
+            float val[9];
+            const float du2 = v.du * v.du, dv2 = v.dv * v.dv, duv = v.du * v.dv;
+            val[0] = 0.0f; val[1] = 0.0f; val[2] = 0.0f;
+            val[3] = w; val[4] = w * v.du; val[5] = w * v.dv;
+            val[6] = (dv2 - g1.z * v.mh) * w;
+            val[7] = (g1.y * v.mh - duv) * w;
+            val[8] = (du2 - g1.x * v.mh) * w;
+            int slot_i = i * SV;
+            asm volatile("" : "+s"(slot_i));
+            reduce9_to_slot(val, slot_stores, s_acc, slot_lane_base + slot_i);
+            hit |= 1ull << i;
+            if (want_f) {
+                // column nb of the batch's B: this entry's w at the wave's 64 pixels (0 where it does not contribute)
+                mine[nb * BROW + lane] = aT;
+                if (lane == 0) s_bidx[wave * MB + nb] = s_idx[i];
+                if (++nb == MB) {
+                    mma_flush(MB);
+                    nb = 0;
+                }
+            }
+        }
+        if (lane == 0) s_hit[wave] = hit;
+        __syncthreads();
+        // the flush, as k_render_zalpha_bwd's.  Phase 1, thread = entry: add the slots of the waves that wrote it, in
+        // wave order, apply the per-splat factors and park the row in wave 0's slot of the same entry
+        if (tid < cnt) {
+            float a[SV];
+#pragma unroll
+            for (int j = 0; j < SV; j++) a[j] = 0;
+#pragma unroll
+            for (int w4 = 0; w4 < 4; w4++) {
+                if ((s_hit[w4] >> tid) & 1ull) {
+                    const float* sl = s_acc + (w4 * RCHUNK + tid) * SV;
+#pragma unroll
+                    for (int j = 0; j < SV; j++) a[j] += sl[j];
+                }
+            }
+            const float* rec = s_geom + tid * GS_PACKED_WIDTH;
+            const float ca = rec[4], cb = rec[5], cc = rec[6];
+            const float kf = -0.5f * rec[3] * rec[8];
+            const float Mu = a[4], Mv = a[5];
+            a[4] = -2.0f * kf * (cc * Mu - cb * Mv);
+            a[5] = -2.0f * kf * (ca * Mv - cb * Mu);
+            a[6] *= kf;
+            a[7] *= kf;
+            a[8] *= kf;
+            float* row = s_acc + tid * SV;
+#pragma unroll
+            for (int j = 0; j < SV; j++) row[j] = a[j];
+        }
+        __syncthreads();
+        // Phase 2, nine lanes = one row (seven rows per wave instruction); rows of zeros stay untouched, and so do
+        // the slab's colour columns
+        const int sub = lane / SV, col = lane - sub * SV;   // lane 63: idle
+        for (int r0 = wave * 7; r0 < cnt; r0 += 28) {
+            const int r = r0 + sub;
+            const bool in = lane < 63 && r < cnt;
+            const float v = in ? s_acc[r * SV + col] : 0.0f;
+            const unsigned long long nz = ballot(v != 0.0f);
+            const bool any = in && ((nz >> (sub * SV)) & 0x1ffull) != 0;
+            if (any && col >= 3) global_add(slab + (size_t)s_idx[r] * SV + col, v);
+        }
+    }
+    if (nb > 0) mma_flush(nb);   // the partial batch
+}
+
+// the instantiation at or above n_channels: 4, 8, 16, 32
+template <int CP>
+static void launch_features_fwd(int nt, hipStream_t st, const float* packed, const float* features, int C,
+                                const int32_t* ranges, const int32_t* sorted, const int32_t* nsp, int W, int H, int ntx,
+                                int tile0, float* fmap, float* alpha, float* t_out) {
+    k_render_features_fwd<CP><<<render_grid(nt), RB, 0, st>>>(packed, features, C, ranges, sorted, nsp, W, H, ntx, tile0,
+                                                              nt, fmap, alpha, t_out);
+}
+template <int CP>
+static void launch_features_bwd(int nt, hipStream_t st, const float* packed, const float* features, int C,
+                                const int32_t* ranges, const int32_t* sorted, const int32_t* nsp, const float* t_in,
+                                const float* g_map, const float* g_alpha, int W, int H, int ntx, int tile0, float* slab,
+                                float* grad_features) {
+    k_render_features_bwd<CP><<<render_grid(nt), RB, 0, st>>>(packed, features, C, ranges, sorted, nsp, t_in, g_map,
+                                                              g_alpha, W, H, ntx, tile0, nt, slab, grad_features);
+}
+
 }  // namespace gs
 
 using namespace gs;
@@ -3003,6 +3410,52 @@ int gs_render_zalpha_backward(const void* packed, const void* xyz_camera_frame, 
         (const float*)transmittance, (const float*)grad_depth, (const float*)grad_alpha, W, H, ntx, tile_row0 * ntx, nt,
         (float*)grad_slab, (float*)grad_z);
     return check_launch("render_zalpha_backward");
+}
+
+int gs_render_features(const void* packed, const void* features, int n_channels, const int32_t* tile_ranges,
+                       const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel, int W, int H,
+                       int tile_row0, int tile_row1, void* feature_map, void* alpha, void* transmittance,
+                       void* stream) {
+    GS_REQUIRE(W > 0 && H > 0, "image must be non-empty");
+    GS_REQUIRE(n_channels >= 1 && n_channels <= 32, "render_features: n_channels must be in 1..32");
+    GS_REQUIRE(tile_ranges != nullptr && num_splats_per_pixel != nullptr,
+               "render_features: tile_ranges or num_splats_per_pixel is NULL");
+    GS_REQUIRE(feature_map != nullptr && alpha != nullptr && transmittance != nullptr,
+               "render_features: an output is NULL");
+    GS_REQUIRE(((uintptr_t)packed & 15) == 0, "render_features: packed must be 16-byte aligned");
+    if (int e = check_rows(H, tile_row0, tile_row1)) return e;
+    const int ntx = (W + 15) / 16;
+    const int nt = (tile_row1 - tile_row0) * ntx;
+    if (nt == 0) return GS_OK;
+    // (packed, features and sorted_gaussians are only read where a list has entries: V == 0 passes anything)
+    auto go = n_channels <= 4 ? launch_features_fwd<4> : n_channels <= 8 ? launch_features_fwd<8>
+              : n_channels <= 16 ? launch_features_fwd<16> : launch_features_fwd<32>;
+    go(nt, (hipStream_t)stream, (const float*)packed, (const float*)features, n_channels, tile_ranges, sorted_gaussians,
+       num_splats_per_pixel, W, H, ntx, tile_row0 * ntx, (float*)feature_map, (float*)alpha, (float*)transmittance);
+    return check_launch("render_features");
+}
+
+int gs_render_features_backward(const void* packed, const void* features, int n_channels, const int32_t* tile_ranges,
+                                const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel,
+                                const void* transmittance, const void* grad_feature_map, const void* grad_alpha, int W,
+                                int H, int tile_row0, int tile_row1, void* grad_slab, void* grad_features,
+                                void* stream) {
+    GS_REQUIRE(W > 0 && H > 0, "image must be non-empty");
+    GS_REQUIRE(n_channels >= 1 && n_channels <= 32, "render_features_backward: n_channels must be in 1..32");
+    GS_REQUIRE(tile_ranges != nullptr && num_splats_per_pixel != nullptr && transmittance != nullptr,
+               "render_features_backward: tile_ranges, num_splats_per_pixel or transmittance is NULL");
+    GS_REQUIRE(((uintptr_t)packed & 15) == 0, "render_features_backward: packed must be 16-byte aligned");
+    if (int e = check_rows(H, tile_row0, tile_row1)) return e;
+    const int ntx = (W + 15) / 16;
+    const int nt = (tile_row1 - tile_row0) * ntx;
+    if (nt == 0 || (grad_feature_map == nullptr && grad_alpha == nullptr)) return GS_OK;   // nothing to add
+    GS_REQUIRE(grad_slab != nullptr, "render_features_backward: grad_slab is NULL");
+    auto go = n_channels <= 4 ? launch_features_bwd<4> : n_channels <= 8 ? launch_features_bwd<8>
+              : n_channels <= 16 ? launch_features_bwd<16> : launch_features_bwd<32>;
+    go(nt, (hipStream_t)stream, (const float*)packed, (const float*)features, n_channels, tile_ranges, sorted_gaussians,
+       num_splats_per_pixel, (const float*)transmittance, (const float*)grad_feature_map, (const float*)grad_alpha, W, H,
+       ntx, tile_row0 * ntx, (float*)grad_slab, (float*)grad_features);
+    return check_launch("render_features_backward");
 }
 
 }  // extern "C"

@@ -21,6 +21,10 @@ preprocess_backward) that gaussian_splatting_amd.sharded composes differently fo
 rasterize_rgbd is the same frame with two more differentiable outputs, depth and accumulated opacity [H, W]
 (_RenderRGBD: gs_render_zalpha / gs_render_zalpha_backward next to the colour kernels, gs_z_backward behind the
 per-Gaussian backward).
+
+rasterize_features composites caller-supplied per-Gaussian feature vectors [N, C <= 32] with the frame's weights into a
+differentiable [H, W, C] map next to the image and the accumulated opacity (_RenderFeatures: gs_render_features /
+gs_render_features_backward).
 """
 import os
 from types import SimpleNamespace
@@ -643,6 +647,29 @@ def zalpha_backward(packed, xyz_cam, ranges, sorted_g, nsp, t_end, grad_depth, g
               _p(gd), _p(ga), width, height, 0, nty, _p(slab), _p(grad_z), _stream())
 
 
+def features_forward(packed, feat, ranges, sorted_g, nsp, height, width):
+    """-> feature_map [H, W, C], alpha, T_end [H, W] (gs_render_features) for the visible Gaussians' feature rows
+    feat [V, C] on the lists of the frame whose colour forward left nsp; one allocation"""
+    nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
+    C, P = int(feat.shape[1]), height * width
+    buf = torch.empty((C + 2) * P, dtype=torch.float32, device=packed.device)
+    fmap, alpha, t_end = buf[:C * P].view(height, width, C), buf[C * P:(C + 1) * P].view(height, width), \
+        buf[(C + 1) * P:].view(height, width)
+    _hip.call("gs_render_features", _p(packed), _p(feat), C, _p(ranges), _p(sorted_g), _p(nsp), width, height, 0, nty,
+              _p(fmap), _p(alpha), _p(t_end), _stream())
+    return fmap, alpha, t_end
+
+
+def features_backward(packed, feat, ranges, sorted_g, nsp, t_end, grad_map, grad_alpha, height, width, slab, grad_feat):
+    """adds the feature / alpha maps' gradients to columns 3..8 of the (cleared or colour-filled) slab and, unless it
+    is None, to grad_feat [V, C] (gs_render_features_backward); either map gradient may be None"""
+    nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
+    gm = grad_map.contiguous() if grad_map is not None else None
+    ga = grad_alpha.contiguous() if grad_alpha is not None else None
+    _hip.call("gs_render_features_backward", _p(packed), _p(feat), int(feat.shape[1]), _p(ranges), _p(sorted_g), _p(nsp),
+              _p(t_end), _p(gm), _p(ga), width, height, 0, nty, _p(slab), _p(grad_feat), _stream())
+
+
 def _as_slab(g_uv, g_conic, g_opa, g_rgb, V, dev):
     """the four render gradients as one [V, 9] slab: the slab they are views of when they come
     straight from _Render.backward, a packed copy otherwise (outputs nobody consumed count as 0)"""
@@ -811,6 +838,43 @@ class _RenderRGBD(torch.autograd.Function):
                             slab, g_z)
         return (slab[:, SLAB_UV], slab[:, SLAB_CONIC], slab[:, SLAB_OPACITY], slab[:, SLAB_RGB],
                 g_z[:V] if grad_depth is not None else None) + (None,) * 10   # (alpha alone leaves dL/dz zero)
+
+
+class _RenderFeatures(torch.autograd.Function):
+    """_Render with two more outputs, feature_map [H, W, C] and alpha [H, W] (gs_render_features on the lists and the
+    splat counts the colour forward left, feat [V, C] the visible Gaussians' rows).  One backward for the three, as
+    _RenderRGBD's: the prologue clears the slab, the colour backward runs if the image has a gradient,
+    gs_render_features_backward if feature_map or alpha has one (grad_features NULL unless feat requires a gradient
+    and feature_map has one).  An unused output costs no launch."""
+
+    @staticmethod
+    def forward(ctx, uv, conic, opacity, rgb, feat, packed, ranges, sorted_g, background_rgb, height, width,
+                keys=None, sort_prefix=0, rendered=None):
+        image, nsp, fw, cost, seg = rendered if rendered else render_forward(
+            packed, rgb, ranges, sorted_g, keys, background_rgb, height, width, None, sort_prefix)
+        fmap, alpha, t_end = features_forward(packed, feat, ranges, sorted_g, nsp, height, width)
+        ctx.save_for_backward(packed, rgb, feat, ranges, sorted_g, background_rgb, nsp, fw, cost, seg, t_end)
+        ctx.set_materialize_grads(False)
+        ctx.dims = (height, width, uv.shape[0])
+        ctx.backward_mode = _hip.get_backward_mode()   # the frame's mode is the default at its forward
+        return image, fmap, alpha
+
+    @staticmethod
+    def backward(ctx, grad_image, grad_map, grad_alpha):
+        packed, rgb, feat, ranges, sorted_g, background_rgb, nsp, fw, cost, seg, t_end = ctx.saved_tensors
+        height, width, V = ctx.dims
+        if grad_image is None and grad_map is None and grad_alpha is None:
+            return (None,) * 14
+        slab = render_backward(packed, rgb, ranges, sorted_g, background_rgb, nsp, fw,
+                               grad_image.contiguous() if grad_image is not None else None, height, width, None,
+                               V, cost, ctx.backward_mode, seg)
+        g_feat = None
+        if grad_map is not None and ctx.needs_input_grad[4]:
+            g_feat = torch.zeros_like(feat)
+        if (grad_map is not None or grad_alpha is not None) and V > 0:   # (nothing visible: nothing to add)
+            features_backward(packed, feat, ranges, sorted_g, nsp, t_end, grad_map, grad_alpha, height, width, slab,
+                              g_feat)
+        return (slab[:, SLAB_UV], slab[:, SLAB_CONIC], slab[:, SLAB_OPACITY], slab[:, SLAB_RGB], g_feat) + (None,) * 9
 
 
 class _GatherRows(torch.autograd.Function):
@@ -1044,3 +1108,54 @@ def rasterize_rgbd(gaussians, camera_T_world, camera, near_thresh, far_thresh, c
                                             background_rgb.contiguous(), height, width, keys, sort_prefix,
                                             tuple(out[11:-1]))
     return image, depth, alpha, culling_mask, uv
+
+
+def rasterize_features(gaussians, features, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+                       use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None,
+                       slab_sync=None, frame_hook=None, adam_plan=None):
+    """rasterize() with a map of caller-supplied per-Gaussian feature vectors and the accumulated opacity:
+
+        image, feature_map, alpha, culling_mask, uv = rasterize_features(gaussians, features, ...)
+
+    features is [N, C] float32 on the Gaussians' device, 1 <= C <= 32, one row per Gaussian (dense: culled rows
+    included; callers with more channels split them).  image, culling_mask and uv are those of rasterize() on the same
+    inputs, bit for bit.  feature_map [H, W, C] = sum_k w_k features[k] with w_k = alpha_k T_k the compositing weights
+    of the entries the colour forward walked; alpha [H, W] = sum_k w_k, bit-equal to rasterize_rgbd's.  No background
+    term, no normalisation.  feature_map and alpha carry gradients to features (culled rows: exactly zero), to the
+    Gaussians' parameters and, when it requires one, to camera_T_world (through the slab; features have no direct
+    pose term); their backward is the true derivative (DESIGN.md "Feature maps").  Whole single-GPU fp32 frames in the
+    SH-precompute colour mode, Python orchestration, depth cut off: anything else raises RuntimeError (the trailing
+    keyword arguments exist only to say so)."""
+    g = gaussians
+    _require(tile_rows is None and not (return_aux or grad_sync or slab_sync or frame_hook),
+             "rasterize_features serves whole single-GPU frames: tile_rows, return_aux, grad_sync, slab_sync and "
+             "frame_hook are not supported")
+    _require(adam_plan is None, "rasterize_features does not take the fused optimizer step (adam_plan)")
+    _require(g.sh is None or use_sh_precompute,
+             "rasterize_features needs the SH-precompute colour mode: per-pixel SH (use_sh_precompute=False) is not "
+             "supported")
+    tensors = [t for t in (g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
+                           background_rgb) if t is not None]
+    _require(all(t.is_cuda and t.dtype == torch.float32 for t in tensors),
+             "rasterize_features needs float32 tensors on the GPU (no fp64, no CPU path)")
+    _require(torch.is_tensor(features) and features.dim() == 2 and features.shape[0] == g.xyz.shape[0],
+             "rasterize_features: features must be [N, C], one row per Gaussian")
+    _require(1 <= features.shape[1] <= 32,
+             "rasterize_features: features must have 1 to 32 columns (callers with more split the channels)")
+    _require(features.dtype == torch.float32 and features.device == g.xyz.device,
+             "rasterize_features: features must be float32 on the Gaussians' device (no fp64, no CPU path)")
+    validate(g, camera_T_world, camera, background_rgb)
+    sh = g.sh.contiguous() if g.sh is not None else None
+    sort_prefix = _hip.GS_SORT_PREFIX if SORT_PREFIX else 0
+    height, width = int(camera.height), int(camera.width)
+    # (no cut_box: the depth cut stays off -- a cut frame's flagged tiles keep their lists elsewhere)
+    out = _Preprocess.apply(
+        g.xyz.contiguous(), g.quaternion.contiguous(), g.scale.contiguous(), g.opacity.contiguous(),
+        g.rgb.contiguous(), sh, camera_T_world.contiguous(), camera.K.contiguous(), width, height, near_thresh,
+        far_thresh, cull_mask_padding, mh_dist, None, sort_prefix, background_rgb.contiguous(), None, None, True)
+    uv, conic, opacity, rgb, packed, _xyz_cam, culling_mask, ranges, sorted_g, vis_idx, keys = out[:11]
+    feat = _GatherRows.apply(features, vis_idx.long()).contiguous()
+    image, feature_map, alpha = _RenderFeatures.apply(uv, conic, opacity, rgb, feat, packed, ranges, sorted_g,
+                                                      background_rgb.contiguous(), height, width, keys, sort_prefix,
+                                                      tuple(out[11:]))
+    return image, feature_map, alpha, culling_mask, uv

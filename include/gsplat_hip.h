@@ -487,6 +487,38 @@ int gs_render_zalpha_backward(const void* packed, const void* xyz_camera_frame, 
 int gs_z_backward(const int32_t* rank, const void* grad_z, const void* camera_T_world, int v_base, int N,
                   void* grad_xyz, void* stream);
 
+/* Per-Gaussian feature vectors composited with the frame's weights (ABI 12; no reference counterpart), fp32.  With
+ * alpha_k, the contribute decision, T_k and w_k = alpha_k T_k exactly as gs_render_zalpha forms them (the same code),
+ * for pixel p and the list entries k < num_splats_per_pixel[p]:
+ *   feature_map[p, c] = sum w_k features[g_k, c]  (c < n_channels),  alpha[p] = sum w_k,  transmittance[p] = T_end,
+ * per contributing visit  F[c] = fma(w, f[c], F[c]) for every channel, A += w, T = fma(-alpha, T, T): alpha and
+ * transmittance are bit-equal to gs_render_zalpha's, and one channel holding z gives its depth bit for bit.  No
+ * background term and no normalisation.
+ *   features    [V, n_channels], rows in the index space of sorted_gaussians (visible rows, as xyz_camera_frame)
+ *   n_channels  1 .. 32, anything else is GS_EINVAL (callers with more split the channels).  The kernels are
+ *               instantiated for 4, 8, 16 and 32 channels; a count in between runs the next one with the channels
+ *               beyond n_channels staged as zeros, and nothing beyond column n_channels - 1 is read or written
+ *   outputs     feature_map[H,W,n_channels], alpha[H,W], transmittance[H,W]: written for every pixel of the tile rows
+ *               [tile_row0, tile_row1), untouched elsewhere.  Empty lists (V == 0) give 0, 0, 1. */
+int gs_render_features(const void* packed, const void* features, int n_channels, const int32_t* tile_ranges,
+                       const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel, int W, int H,
+                       int tile_row0, int tile_row1, void* feature_map, void* alpha, void* transmittance,
+                       void* stream);
+/* Backward of the above: the TRUE derivative, decisions held constant, as gs_render_zalpha_backward (no walk quirk;
+ * alpha above 0.9999 enters as 0.9999), with c_k = grad_alpha + sum_c grad_feature_map[c] f_k[c] formed as a fused
+ * multiply-add chain from grad_alpha over the channels ascending.
+ *   grad_feature_map [H,W,n_channels], grad_alpha [H,W]   either may be NULL = all zeros (both NULL: nothing is launched)
+ *   grad_slab        [V,9]: columns 3..8 accumulated, columns 0..2 untouched
+ *   grad_features    [V,n_channels], accumulated: dL/df[k, c] = sum_pixels w_k g[c]; NULL skips it altogether
+ * Both are added into (the slab: one atomic per value per (list entry, tile); grad_features: one per value per
+ * (list entry, 8 x 8 patch), from v_mfma_f32_16x16x4_f32 contractions over the patch's pixels); the caller zeroes
+ * them.  Rows of Gaussians no pixel uses are not touched. */
+int gs_render_features_backward(const void* packed, const void* features, int n_channels, const int32_t* tile_ranges,
+                                const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel,
+                                const void* transmittance, const void* grad_feature_map, const void* grad_alpha, int W,
+                                int H, int tile_row0, int tile_row1, void* grad_slab, void* grad_features,
+                                void* stream);
+
 /* Cost-balanced bands (multi-GPU; no reference counterpart): the band images of unequal bands are all-gathered as
  * equal chunks of chunk_rows = 16 x (tallest band) + 1 pixel rows, each starting at its rank's band; the last row of
  * a chunk carries the per-tile-row costs of that band (floats; 0 outside the band).
