@@ -267,6 +267,23 @@ def test_tile_lists_with_screen_filling_gaussians(hip_backend, N, W, H):
     assert torch.equal(got_r.cpu(), ref_r) and torch.equal(got_s.cpu(), ref_s)
 
 
+def test_tile_lists_one_lane_per_gaussian(hip_backend):
+    """more than 262144 visible Gaussians on a grid with too few of them per tile for the LDS histogram (binning.hip:
+    for_subgroup_of, use_private): the atomic-counter kernels k_tile_count<1> / k_tile_emit<1>, one lane per Gaussian"""
+    orc = oracle()
+    W, H = 1920, 1080
+    ntx, nty = (W + 15) // 16, (H + 15) // 16
+    d = cpu_stage_inputs(300000, W, H, 0, 14)
+    V = d["uv"].shape[0]
+    assert V > (1 << 18) and V * 8 <= 1024 * ntx * nty
+    ref_sorted, ref_ranges = orc.get_sorted_gaussian_list(1024, d["uv"], d["xyz_c"], d["conic"], ntx, nty, 3.0)
+    got_sorted, got_ranges = hip_backend.get_sorted_gaussian_list(
+        1024, d["uv"].to(DEV), d["xyz_c"].to(DEV), d["conic"].to(DEV), ntx, nty, 3.0)
+    assert torch.equal(got_ranges.cpu(), ref_ranges)
+    assert torch.equal(got_sorted.cpu(), ref_sorted)
+    assert ref_sorted.numel() > V
+
+
 def _needs_tile_rows_extension(mod):
     if mod.__file__.endswith(".so"):
         pytest.skip("tile_rows= is an extension of the ctypes shim (multi-GPU hooks), not part of the "

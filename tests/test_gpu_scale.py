@@ -296,6 +296,49 @@ def test_prefix_sort_selects_the_nearest_entries():
             assert torch.equal(got[s0:s0 + n], before[s0:s0 + n]), (t, n)
 
 
+def test_prefix_sort_repair_of_a_small_frame():
+    """a frame of 1024 < S <= 4096 instances with one flagged tile of more than 1024 entries: the repair pass takes
+    k_tile_sort_flagged<4096> (binning.hip: launch_sort_flagged), the smaller LDS allocation"""
+    import ctypes
+    from gaussian_splatting_amd import _hip
+    orc = oracle()
+    gen = torch.Generator().manual_seed(13)
+    chunks, sizes = [], (3000, 40, 1)
+    for tile_x, n in enumerate(sizes):
+        uvs = torch.rand(n, 2, generator=gen) * 10 + 3
+        uvs[:, 0] += 16 * tile_x
+        chunks.append(uvs)
+    uv = torch.cat(chunks).contiguous()
+    V = uv.shape[0]
+    conic = torch.tensor([[0.5, 0.0, 0.5]]).repeat(V, 1).contiguous()
+    z = 1 + 10 * torch.rand(V, 1, generator=gen)
+    z[::7] = 3.0   # ties
+    xyz_c = torch.cat([torch.zeros(V, 2), z], dim=1).contiguous()
+    ntx = len(sizes)
+    ref_sorted, ref_ranges = orc.get_sorted_gaussian_list(1024, uv, xyz_c, conic, ntx, 1, 3.0)
+    assert (ref_ranges[1:] - ref_ranges[:-1]).tolist() == list(sizes)
+    p = lambda x: ctypes.c_void_p(x.data_ptr())
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    uv_d, xyz_d, conic_d = uv.to(DEV), xyz_c.to(DEV), conic.to(DEV)
+    ws = torch.empty(_hip.lib().gs_tile_workspace_ints(ntx), dtype=torch.int32, device=DEV)
+    ranges = torch.empty(ntx + 1, dtype=torch.int32, device=DEV)
+    _hip.call("gs_tile_count", p(uv_d), p(conic_d), V, None, None, None, ntx, 1, ctypes.c_float(3.0), 0, 1, p(ws),
+              p(ranges), None, stream)
+    assert torch.equal(ranges.cpu(), ref_ranges)
+    S = int(ranges[-1])
+    assert 1024 < S <= 4096
+    keys = torch.empty(S, dtype=torch.int64, device=DEV)
+    got_d = torch.full((S,), -1, dtype=torch.int32, device=DEV)
+    _hip.call("gs_tile_emit_sort", p(uv_d), p(xyz_d), p(conic_d), V, None, None, None, ntx, 1, ctypes.c_float(3.0),
+              0, 1, p(ranges), p(ws), p(keys), ctypes.c_int64(S), p(got_d), _hip.GS_SORT_PREFIX, stream)
+    got = got_d.cpu()
+    assert torch.equal(got[:1024], ref_sorted[:1024]) and torch.equal(got[3000:], ref_sorted[3000:])
+    assert not torch.equal(got[:3000], ref_sorted[:3000])   # the prefix tile is not sorted beyond its prefix yet
+    flags = torch.tensor([1, 0, 0], dtype=torch.int32, device=DEV)
+    _hip.call("gs_tile_sort_flagged", p(ranges), p(keys), ctypes.c_int64(S), p(flags), ntx, 0, 1, p(got_d), stream)
+    assert torch.equal(got_d.cpu(), ref_sorted)
+
+
 def run_both_sort_modes(make, grad_image):
     out = {}
     for mode in (False, True):
