@@ -4,6 +4,8 @@
 //                             (splat_py/optimizer_manager.py:15-42 builds the optimizer, trainer.py:376
 //                             steps it): one launch for all groups instead of ~10 elementwise kernels
 //                             per group
+//   gs_adam_step_rows         the same step restricted to the rows (Gaussians) a frame saw: a culled row's
+//                             parameters and moments are neither read nor written
 //   gs_accumulate_grad_stats  the densification statistics of trainer.py:378-385: |uv.grad| scaled by
 //                             the focal lengths and scattered to the visible Gaussians, |xyz.grad|,
 //                             and the view counter -- without the boolean-mask index_put (which costs
@@ -97,6 +99,91 @@ __global__ __launch_bounds__(256) void k_adam(AdamGroups G, float w1, float beta
     }
 }
 
+// ---- the selective step: only the rows a frame saw ----------------------------------------------------------
+// Tensor k is [n_rows, row_width[k]]; skip[r] != 0 leaves row r of every tensor alone.  The walk is k_adam's (the
+// float4 chunks of all tensors, two in flight per thread); a chunk whose elements are all skipped costs its lane the
+// mask bytes and nothing else.
+struct AdamRowGroups {
+    AdamGroups g;
+    long long row_width[GS_ADAM_MAX_GROUPS];
+    int idx32[GS_ADAM_MAX_GROUPS];   // numel < 2^31: the row index is a 32-bit division
+};
+
+// the elements of a chunk (bit e: element i + e) that lie in rows to be stepped.  One division for the first
+// element's row, the others advance by increment-and-compare; the mask byte is read again only where the row changes.
+template <typename I>
+__device__ inline unsigned adam_visible(const unsigned char* __restrict__ skip, I i, I w, int count) {
+    I r = i / w, rem = i - r * w;
+    bool s = skip[r] != 0;
+    unsigned vis = s ? 0u : 1u;
+#pragma unroll
+    for (int e = 1; e < 4; e++) {
+        if (e < count) {
+            if (++rem == w) {
+                rem = 0;
+                s = skip[++r] != 0;
+            }
+            vis |= s ? 0u : 1u << e;
+        }
+    }
+    return vis;
+}
+
+__device__ inline unsigned adam_rows_locate(const AdamRowGroups& R, const unsigned char* __restrict__ skip,
+                                            long long c, AdamChunk& ch) {
+    adam_locate(R.g, c, ch);
+    const long long left = R.g.numel[ch.k] - ch.i;   // >= 1
+    const int count = left < 4 ? (int)left : 4;
+    return R.idx32[ch.k] ? adam_visible<unsigned>(skip, (unsigned)ch.i, (unsigned)R.row_width[ch.k], count)
+                         : adam_visible<unsigned long long>(skip, (unsigned long long)ch.i,
+                                                            (unsigned long long)R.row_width[ch.k], count);
+}
+
+__device__ inline void adam_rows_finish(const AdamGroups& G, AdamChunk& ch, unsigned vis, float w1, float beta2,
+                                        float w2, float eps) {
+    if (vis == 0) return;
+    const int k = ch.k;
+    const float neg_step = G.neg_step_size[k], bc2 = G.bc2_sqrt[k];
+    if (ch.vec) {
+        // skipped elements of a chunk that is stepped in part go back as they were loaded
+        if (vis & 1) adam_update(ch.p.x, ch.g.x, ch.m.x, ch.v.x, w1, beta2, w2, bc2, eps, neg_step);
+        if (vis & 2) adam_update(ch.p.y, ch.g.y, ch.m.y, ch.v.y, w1, beta2, w2, bc2, eps, neg_step);
+        if (vis & 4) adam_update(ch.p.z, ch.g.z, ch.m.z, ch.v.z, w1, beta2, w2, bc2, eps, neg_step);
+        if (vis & 8) adam_update(ch.p.w, ch.g.w, ch.m.w, ch.v.w, w1, beta2, w2, bc2, eps, neg_step);
+        nt_store4(G.p[k] + ch.i, ch.p);
+        nt_store4(G.m[k] + ch.i, ch.m);
+        nt_store4(G.v[k] + ch.i, ch.v);
+    } else {
+        for (int e = 0; e < 4; e++) {   // bits of vis exist only for elements below numel
+            if (!(vis >> e & 1)) continue;
+            const long long j = ch.i + e;
+            float p = G.p[k][j], m = G.m[k][j], v = G.v[k][j];
+            adam_update(p, G.g[k][j], m, v, w1, beta2, w2, bc2, eps, neg_step);
+            G.p[k][j] = p;
+            G.m[k][j] = m;
+            G.v[k][j] = v;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_adam_rows(AdamRowGroups R, const unsigned char* __restrict__ skip,
+                                                   float w1, float beta2, float w2, float eps) {
+    const AdamGroups& G = R.g;
+    const long long total = G.chunk_end[G.n - 1];
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < total;
+         c += 2 * stride) {
+        AdamChunk a, b;
+        const bool two = c + stride < total;
+        const unsigned va = adam_rows_locate(R, skip, c, a);
+        const unsigned vb = two ? adam_rows_locate(R, skip, c + stride, b) : 0u;
+        if (va) adam_load(G, a);
+        if (vb) adam_load(G, b);
+        adam_rows_finish(G, a, va, w1, beta2, w2, eps);
+        adam_rows_finish(G, b, vb, w1, beta2, w2, eps);
+    }
+}
+
 // trainer.py:378-385.  One thread per Gaussian index i:
 //   uv_grad_accum[i]  += |uv_grad[rank[i]] * (fx, fy)|    if i is visible (rank[i] >= 0)
 //   xyz_grad_accum[i] += |xyz_grad[i]|
@@ -175,6 +262,51 @@ int gs_adam_step(int n_groups, void* const* params, const void* const* grads, vo
     const AdamShared sh = adam_shared(beta1, beta2, eps);
     k_adam<<<grid, 256, 0, (hipStream_t)stream>>>(G, sh.w1, sh.beta2, sh.w2, sh.eps);
     return check_launch("adam_step");
+}
+
+int gs_adam_step_rows(int n_groups, void* const* params, const void* const* grads, void* const* exp_avg,
+                      void* const* exp_avg_sq, const int64_t* numel, const int64_t* row_width,
+                      const void* skip_row, int64_t n_rows, const double* lr, const int64_t* step, double beta1,
+                      double beta2, double eps, void* stream) {
+    GS_REQUIRE(n_groups >= 1 && n_groups <= GS_ADAM_MAX_GROUPS, "adam_step_rows: 1 <= n_groups <= %d",
+               GS_ADAM_MAX_GROUPS);
+    GS_REQUIRE(n_rows >= 0, "adam_step_rows: n_rows must be >= 0");
+    AdamRowGroups R;
+    AdamGroups& G = R.g;
+    long long chunks = 0;
+    for (int k = 0; k < n_groups; k++) {
+        GS_REQUIRE(row_width[k] >= 1, "adam_step_rows: row_width of group %d must be >= 1", k);
+        GS_REQUIRE(numel[k] / row_width[k] == n_rows && numel[k] % row_width[k] == 0,
+                   "adam_step_rows: numel of group %d is not n_rows * row_width", k);
+        GS_REQUIRE(step[k] >= 1, "adam_step_rows: bad step of group %d", k);
+        G.p[k] = (float*)params[k];
+        G.g[k] = (const float*)grads[k];
+        G.m[k] = (float*)exp_avg[k];
+        G.v[k] = (float*)exp_avg_sq[k];
+        G.numel[k] = numel[k];
+        chunks += (numel[k] + 3) / 4;
+        G.chunk_end[k] = chunks;
+        R.row_width[k] = row_width[k];
+        R.idx32[k] = numel[k] <= 0x7fffffffLL;
+        adam_scalars(lr[k], step[k], beta1, beta2, &G.neg_step_size[k], &G.bc2_sqrt[k]);
+        const uintptr_t bits = (uintptr_t)params[k] | (uintptr_t)grads[k] | (uintptr_t)exp_avg[k] |
+                               (uintptr_t)exp_avg_sq[k];
+        G.vec_ok[k] = (bits & 15) == 0;
+    }
+    for (int k = n_groups; k < GS_ADAM_MAX_GROUPS; k++) {
+        G.p[k] = nullptr; G.g[k] = nullptr; G.m[k] = nullptr; G.v[k] = nullptr;
+        G.numel[k] = 0; G.chunk_end[k] = chunks; G.neg_step_size[k] = 0; G.bc2_sqrt[k] = 1;
+        G.vec_ok[k] = 0; R.row_width[k] = 1; R.idx32[k] = 1;
+    }
+    G.n = n_groups;
+    if (n_rows == 0) return GS_OK;
+    GS_REQUIRE(skip_row != nullptr, "adam_step_rows: skip_row is NULL with n_rows > 0");
+    const long long want = (chunks + 255) / 256;
+    const int grid = (int)(want < 8192 ? want : 8192);
+    const AdamShared sh = adam_shared(beta1, beta2, eps);
+    k_adam_rows<<<grid, 256, 0, (hipStream_t)stream>>>(R, (const unsigned char*)skip_row, sh.w1, sh.beta2, sh.w2,
+                                                       sh.eps);
+    return check_launch("adam_step_rows");
 }
 
 int gs_stream_copy(void* dst, const void* src, size_t bytes, int blocks, void* stream) {

@@ -10,6 +10,9 @@
                               update where the gradients are in registers: they are never written out and
                               read back); step() then steps xyz.  Opt-in; falls back to fused.rasterize +
                               Adam.step whenever a condition of the fused step does not hold
+    SelectiveAdam             Adam whose step(culling_mask=...) steps only the Gaussians the frame saw (the
+                              `sparse_adam` / SelectiveAdam of other trainers): a culled row's parameters and
+                              moments are neither read nor written; one HIP launch (gs_adam_step_rows)
     accumulate_grad_stats     trainer.py:378-385 (densification statistics) in one launch, without
                               the boolean-mask index_put and its host sync
 
@@ -19,6 +22,7 @@ non-fp32 / non-device tensors) is handed to torch.optim.Adam.step itself.
 import ctypes
 
 import torch
+from torch.optim.adam import adam as _torch_adam   # the functional form (torch.optim.adam itself is not an attribute)
 
 from . import _hip
 
@@ -80,6 +84,123 @@ class Adam(torch.optim.Adam):
         # the kernel wrote through raw pointers: bump the version counters like an in-place torch op would,
         # so that autograd's saved-tensor check still catches a backward over stale parameters
         for p, _, m, v, *_ in work:
+            torch.autograd.graph.increment_version(p)
+            torch.autograd.graph.increment_version(m)
+            torch.autograd.graph.increment_version(v)
+        return loss
+
+
+class SelectiveAdam(Adam):
+    """train_ops.Adam (same constructor, param_groups and state layout, so a DensityController's parameter surgery
+    works on it unchanged) whose step can leave alone the Gaussians a frame did not see:
+
+        opt = SelectiveAdam(param_groups)
+        image, culling_mask, uv = fused.rasterize(...)
+        loss.backward()
+        opt.step(culling_mask=culling_mask)        # keyword only; None -> Adam.step
+
+    culling_mask: [N] bool, True = skip, as rasterize returns it; every parameter with a gradient has shape[0] == N.
+
+      rows with culling_mask[r] == False   p[r], exp_avg[r], exp_avg_sq[r] take exactly the update Adam.step applies in
+                                           the same step (bias correction from the tensor's own state["step"] after its
+                                           increment): bit for bit a dense step restricted to those rows
+      rows with culling_mask[r] == True    every bit of p[r], exp_avg[r], exp_avg_sq[r] stays (no moment decay, no drift
+                                           on stale momentum; NaN payloads and infinities included); the gradient is
+                                           not read there and need not be zero
+      state["step"]                        advances by one for every parameter that has a .grad, whatever the mask
+                                           says (an all-True mask included): the count is global, not per row
+
+    step(culling_mask=None) is Adam.step, with its results.  With a mask, amsgrad / weight decay / maximize /
+    capturable / differentiable in any group raise RuntimeError; a mask that is not a 1-D bool tensor on the
+    parameters' device, or a parameter whose shape[0] differs from the mask's, raises ValueError before any state
+    is touched.  fp32 contiguous device tensors go through one gs_adam_step_rows launch per run of at most 8 tensors
+    that share (betas, eps); anything else (CPU, other dtypes, non-contiguous) through torch's functional Adam on the
+    gathered visible rows, which are scattered back -- culled rows are not written at all.
+
+    A caller that accumulates gradients over several frames before one step passes the AND of their culling masks
+    (a row is skipped only if no frame saw it).  On an owner-sliced multi-GPU job, where a rank steps only its own
+    rows, the caller passes the slice of the mask that matches those rows."""
+
+    @torch.no_grad()
+    def step(self, closure=None, *, culling_mask=None):
+        if culling_mask is None:
+            return super().step(closure)
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        mask = culling_mask
+        if not (torch.is_tensor(mask) and mask.dtype == torch.bool and mask.dim() == 1):
+            what = f"{tuple(mask.shape)} {mask.dtype}" if torch.is_tensor(mask) else type(mask).__name__
+            raise ValueError(f"SelectiveAdam: culling_mask must be a 1-D bool tensor, got {what}")
+        for gi, group in enumerate(self.param_groups):
+            for pi, p in enumerate(group["params"]):
+                if p.grad is None:
+                    continue
+                if p.device != mask.device:
+                    raise ValueError(f"SelectiveAdam: culling_mask is on {mask.device}, parameter {pi} of group {gi} "
+                                     f"on {p.device}")
+                if p.dim() == 0 or p.shape[0] != mask.shape[0]:
+                    raise ValueError(f"SelectiveAdam: parameter {pi} of group {gi} has shape {tuple(p.shape)}, "
+                                     f"culling_mask {mask.shape[0]} rows")
+        for gi, group in enumerate(self.param_groups):
+            for name in ("amsgrad", "weight_decay", "maximize", "capturable", "differentiable"):
+                if group.get(name, False):
+                    raise RuntimeError(f"SelectiveAdam: {name} in param group {gi} is not supported with a culling_mask")
+        N = mask.shape[0]
+        mask = mask.contiguous()
+        visible = None   # row indices for the torch path, made on first use
+        work = []
+        for group in self.param_groups:
+            beta1, beta2 = group["betas"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                state = self.state[p]
+                if len(state) == 0:   # torch/optim/adam.py _init_group
+                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                state["step"] += 1
+                if p.numel() == 0:
+                    continue
+                m, v = state["exp_avg"], state["exp_avg_sq"]
+                if (p.is_cuda and not p.grad.is_sparse
+                        and all(t.dtype == torch.float32 and t.is_contiguous() for t in (p, m, v))
+                        and p.grad.dtype == torch.float32):
+                    grad = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                    work.append((p, grad, m, v, float(group["lr"]), int(state["step"]), beta1, beta2, group["eps"]))
+                    continue
+                if visible is None:
+                    visible = (~mask).nonzero().squeeze(1)
+                if visible.numel() == 0:
+                    continue
+                grad = p.grad.to_dense() if p.grad.is_sparse else p.grad
+                rows = [t.index_select(0, visible) for t in (p, grad, m, v)]
+                # _single_tensor_adam increments the step it is given
+                _torch_adam([rows[0]], [rows[1]], [rows[2]], [rows[3]], [], [state["step"] - 1], foreach=False,
+                            amsgrad=False, beta1=beta1, beta2=beta2, lr=group["lr"], weight_decay=0, eps=group["eps"],
+                            maximize=False)
+                p.index_copy_(0, visible, rows[0])
+                m.index_copy_(0, visible, rows[2])
+                v.index_copy_(0, visible, rows[3])
+        if work:
+            stream = _hip.current_stream()
+        i = 0
+        while i < len(work):
+            j = i
+            while j < len(work) and j - i < _MAX_TENSORS and work[j][6:] == work[i][6:]:
+                j += 1
+            chunk = work[i:j]
+            n = len(chunk)
+            ptrs = lambda k: (ctypes.c_void_p * n)(*[t[k].data_ptr() for t in chunk])
+            _hip.call("gs_adam_step_rows", n, ptrs(0), ptrs(1), ptrs(2), ptrs(3),
+                      (ctypes.c_int64 * n)(*[t[0].numel() for t in chunk]),
+                      (ctypes.c_int64 * n)(*[t[0].numel() // N for t in chunk]), mask.data_ptr(), N,
+                      (ctypes.c_double * n)(*[t[4] for t in chunk]), (ctypes.c_int64 * n)(*[t[5] for t in chunk]),
+                      chunk[0][6], chunk[0][7], chunk[0][8], stream)
+            i = j
+        for p, _, m, v, *_ in work:   # as Adam.step: the kernel wrote through raw pointers
             torch.autograd.graph.increment_version(p)
             torch.autograd.graph.increment_version(m)
             torch.autograd.graph.increment_version(v)

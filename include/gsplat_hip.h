@@ -672,6 +672,21 @@ int gs_preprocess_backward_gathered(const void* xyz, const void* quaternion, con
 int gs_adam_step(int n_groups, void* const* params, const void* const* grads, void* const* exp_avg,
                  void* const* exp_avg_sq, const int64_t* numel, const double* lr,
                  const int64_t* step, double beta1, double beta2, double eps, void* stream);
+/* gs_adam_step restricted to the rows a frame saw (ABI 13; the `sparse_adam` / SelectiveAdam of other trainers).
+ * Tensor k is [n_rows, row_width[k]] (numel[k] == n_rows * row_width[k], row_width[k] >= 1); skip_row: n_rows bytes on
+ * the device, nonzero = leave the row alone (a bool culling mask as the rasterizer returns it).
+ *   rows with skip_row[r] == 0   params / exp_avg / exp_avg_sq take exactly gs_adam_step's update with the same lr[k],
+ *                                step[k], betas and eps: bit-identical to a dense step restricted to those rows
+ *   rows with skip_row[r] != 0   every bit of params / exp_avg / exp_avg_sq is unchanged (NaN payloads and infinities
+ *                                included: no arithmetic touches them); grads is not read there
+ * step[k] is the global count (it advances whether or not a row was seen).  One launch for up to 8 tensors; a float4
+ * chunk without a visible element is neither loaded nor stored, so the traffic follows the visible rows where they
+ * are contiguous or wide (28 B per visible element plus n_rows mask bytes per tensor).  n_rows == 0 returns GS_OK
+ * without a launch; skip_row may be NULL only then. */
+int gs_adam_step_rows(int n_groups, void* const* params, const void* const* grads, void* const* exp_avg,
+                      void* const* exp_avg_sq, const int64_t* numel, const int64_t* row_width,
+                      const void* skip_row, int64_t n_rows, const double* lr, const int64_t* step, double beta1,
+                      double beta2, double eps, void* stream);
 /* Measurement aid (ABI 7; bench.py `roofline.hbm_copy_gbs_measured`): a float4 grid-stride stream copy of `bytes` bytes
  * (multiple of 16, as are both pointers) with `blocks` workgroups of 256 lanes, non-temporal loads and stores.
  * No reference counterpart. */

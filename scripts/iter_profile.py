@@ -1,8 +1,10 @@
 """Where does one training iteration go?  Host time to enqueue and GPU time (sync after each stage) of
 rasterize / loss+backward / Adam / statistics at a given Gaussian count.
-usage: python scripts/iter_profile.py [N] [--fused-adam]
+usage: python scripts/iter_profile.py [N] [--fused-adam | --selective-adam]
 --fused-adam: the same iteration with train_ops.FusedRasterAdam (five of the six tensors are stepped inside the
-backward, "adam" is then the step of xyz alone)"""
+backward, "adam" is then the step of xyz alone)
+--selective-adam: the same iteration with train_ops.SelectiveAdam stepping with the frame's own culling mask; also
+prints the frames' mean V / N (the visible share of the Gaussians)"""
 import os
 import sys
 import time
@@ -14,10 +16,13 @@ import bench  # noqa: E402
 from gaussian_splatting_amd import fused  # noqa: E402
 from gaussian_splatting_amd.densify import DensifyConfig, DensityController  # noqa: E402
 from gaussian_splatting_amd.synthetic import DEFAULTS, make_scene  # noqa: E402
-from gaussian_splatting_amd.train_ops import Adam, FusedRasterAdam, ssim_l1_loss  # noqa: E402
+from gaussian_splatting_amd.train_ops import Adam, FusedRasterAdam, SelectiveAdam, ssim_l1_loss  # noqa: E402
 
 FUSED_ADAM = "--fused-adam" in sys.argv
-argv = [a for a in sys.argv[1:] if a != "--fused-adam"]
+SELECTIVE_ADAM = "--selective-adam" in sys.argv
+if FUSED_ADAM and SELECTIVE_ADAM:
+    sys.exit("--fused-adam and --selective-adam exclude each other")
+argv = [a for a in sys.argv[1:] if a not in ("--fused-adam", "--selective-adam")]
 N = int(argv[0]) if argv else 700_000
 dev = torch.device("cuda", 0)
 W, H = 1297, 840
@@ -25,11 +30,12 @@ g, cam, T = make_scene(N, W, H, 3, seed=5, device=dev)
 names = ("xyz", "quaternion", "scale", "opacity", "rgb", "sh")
 for k in names:
     getattr(g, k).requires_grad_(True)
-opt = (FusedRasterAdam if FUSED_ADAM else Adam)([{"params": getattr(g, k), "lr": 1e-3} for k in names])
+opt = (FusedRasterAdam if FUSED_ADAM else SelectiveAdam if SELECTIVE_ADAM else Adam)([{"params": getattr(g, k), "lr": 1e-3} for k in names])
 ctrl = DensityController(g, opt, DensifyConfig())
 poses = bench.camera_poses(24, 4321, dev, moving=True)
 target = torch.rand(H, W, 3, device=dev)
 stages = {}
+visible = torch.zeros((), dtype=torch.int64, device=dev)   # summed on the device: no sync in the iteration
 
 
 def mark(name, t0, sync):
@@ -54,10 +60,14 @@ def iteration(i, sync):
     t = mark("loss", t, sync)
     loss.backward()
     t = mark("backward", t, sync)
-    opt.step()
+    if SELECTIVE_ADAM:
+        opt.step(culling_mask=culled)
+    else:
+        opt.step()
     t = mark("adam", t, sync)
     ctrl.accumulate(uv.grad, culled, cam)
     t = mark("statistics", t, sync)
+    visible.add_((~culled).sum())   # outside the timed stages
 
 
 for i in range(20):
@@ -73,5 +83,6 @@ host = {k: v[0] * 10 for k, v in stages.items()}
 stages.clear()
 for i in range(100):
     iteration(i, True)
-print(f"N={N}{' (fused optimizer step)' if FUSED_ADAM else ''}: {free:.3f} ms/iteration free-running; host enqueue ms: " + ", ".join(f"{k} {v:.3f}" for k, v in host.items()))
+mode = " (fused optimizer step)" if FUSED_ADAM else " (selective optimizer step)" if SELECTIVE_ADAM else ""
+print(f"N={N}{mode}: V / N = {int(visible) / (220 * N):.4f} (mean of the frames); {free:.3f} ms/iteration free-running; host enqueue ms: " + ", ".join(f"{k} {v:.3f}" for k, v in host.items()))
 print("with a sync after every stage (host + GPU) ms: " + ", ".join(f"{k} {v[1] * 10:.3f}" for k, v in stages.items()))
