@@ -38,9 +38,11 @@
 //   k_render_bwd<float, 1>, fp32 with one colour coefficient -- the fused renderer's, and what gs_render_tiles_backward /
 //   _packed run for float32 with n_sh == 1: sums nine per-splat values over the wave with a transposing DPP /
 //   permlane-swap reduction into a wave-private LDS slot (plain store, no LDS atomics); the flush adds the four waves'
-//   slots and issues the global atomics nine lanes per 36-byte row (of the [V, 9] slab, or of the separate gradient
-//   arrays).  It alone carries the fused frame's depth segments, depth-cut overflow lists, handed-over touch masks and
-//   the longest-first tile order (durations the forward measured; k_bwd_prologue: tile_order_body).
+//   slots (flush_sum_slots' text, written out here; the routine itself in the other fp32 backwards) and issues the
+//   global atomics nine lanes per 36-byte row (of the [V, 9] slab, or of the separate gradient arrays).  It alone
+//   carries the fused frame's depth
+//   segments, depth-cut overflow lists, handed-over touch masks and the longest-first tile order (durations the forward
+//   measured; k_bwd_prologue: tile_order_body).
 //   k_render_bwd_sh<N_SH>, fp32 with per-pixel SH (4 / 9 / 16 coefficients): the same slots for the six geometric sums,
 //   whole lists, separate gradient arrays; the colour is evaluated at the pixel's view direction and the
 //   colour-coefficient gradients are a matrix-core contraction over the wave's 64 pixels per batch of 16 contributing
@@ -48,6 +50,11 @@
 //   k_render_bwd_ref<N_SH>, fp64 (gradcheck and the fp64 parity tests): one shared LDS row of 3 N_SH + 6 sums per
 //   staged splat, shuffle wave sums + one LDS atomic per value per visit, one global atomic per value per
 //   (splat, tile) -- the reference issues eight (one per warp), unconditionally.
+//
+// Maps (no reference counterpart): depth / alpha (k_render_zalpha_fwd / _bwd) and per-Gaussian feature vectors
+// (k_render_features_fwd / _bwd<CP>) composited with the weights of the entries the colour forward walked.  One
+// forward walk and one backward walk with its flush, render_map_fwd / render_map_bwd, templated on a channel policy
+// that holds what a family has of its own: where the channel values come from and where their sums and gradients go.
 //
 // Numerics.  The fp32 forward is bit-identical to the CPU restatement: same operation order and
 // operand precisions as render.cu (including its double-literal promotions), the IEEE quotient (formed
@@ -1293,6 +1300,43 @@ __device__ __forceinline__ void reduce9_to_slot(const float* val, bool stores, f
     if (stores) slots[lane_slot] = total;
 }
 
+// Phase 1 of the flush of k_render_bwd_sh and of the map walk (k_render_bwd has the same text written out, see there;
+// one global atomic per value per (splat, tile)), thread = staged splat: add the slots of the waves that wrote this
+// splat (s_hit [wave][RCHUNK / 64 words]), in wave order (deterministic per tile), apply the per-splat factors -- the
+// sums of (w, w du, w dv) and of the per-pixel conic terms become gradients with k = -0.5 opacity / det -- and park
+// the row in wave 0's slot of the same splat.  Each thread only ever touches its own splat's slots: no barrier needed
+// before; the caller puts one behind, in front of its Phase 2.
+template <int RCHUNK, int SV>
+__device__ __forceinline__ void flush_sum_slots(float* s_acc, const float* s_geom,
+                                                const unsigned long long (*s_hit)[RCHUNK / 64 > 0 ? RCHUNK / 64 : 1],
+                                                int tid, int cnt) {
+    if (tid < cnt) {
+        float a[SV];
+#pragma unroll
+        for (int j = 0; j < SV; j++) a[j] = 0;
+#pragma unroll
+        for (int w4 = 0; w4 < 4; w4++) {
+            if ((s_hit[w4][tid >> 6] >> (tid & 63)) & 1ull) {
+                const float* sl = s_acc + (w4 * RCHUNK + tid) * SV;
+#pragma unroll
+                for (int j = 0; j < SV; j++) a[j] += sl[j];
+            }
+        }
+        const float* rec = s_geom + tid * GS_PACKED_WIDTH;
+        const float ca = rec[4], cb = rec[5], cc = rec[6];
+        const float k = -0.5f * rec[3] * rec[8];
+        const float Mu = a[4], Mv = a[5];
+        a[4] = -2.0f * k * (cc * Mu - cb * Mv);
+        a[5] = -2.0f * k * (ca * Mv - cb * Mu);
+        a[6] *= k;
+        a[7] *= k;
+        a[8] *= k;
+        float* row = s_acc + tid * SV;
+#pragma unroll
+        for (int j = 0; j < SV; j++) row[j] = a[j];
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------------------------------
@@ -1585,9 +1629,9 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
         __syncthreads();
         GS_PHASE(3);
         // the flush: one global atomic per value per (splat, tile)
-        // Phase 1, thread = splat: add the slots of the waves that wrote this splat, in wave order
-        // (deterministic per tile), apply the per-splat factors, and park the row in wave 0's slot of the
-        // same splat (each thread only ever touches its own splat's slots: no barrier needed before).
+        // Phase 1, thread = splat: flush_sum_slots' text, written out -- called as the routine, the same instructions
+        // come out with a lane-mask merge of the visit loop scheduled four places later, and this kernel's visit loop
+        // is not to move for a tidier flush.  A change to either is a change to both.
         if (tid < cnt) {
             float a[SV];
 #pragma unroll
@@ -1946,36 +1990,8 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd_sh(
         __syncthreads();
         GS_PHASE(3);
         // the flush: one global atomic per value per (splat, tile), the six geometric columns only (the colour
-        // coefficients went out with the batches)
-        // Phase 1, thread = splat: add the slots of the waves that wrote this splat, in wave order
-        // (deterministic per tile), apply the per-splat factors, and park the row in wave 0's slot of the
-        // same splat (each thread only ever touches its own splat's slots: no barrier needed before).
-        if (tid < cnt) {
-            float a[SV];
-#pragma unroll
-            for (int j = 0; j < SV; j++) a[j] = 0;
-#pragma unroll
-            for (int w4 = 0; w4 < 4; w4++) {
-                if ((s_hit[w4][tid >> 6] >> (tid & 63)) & 1ull) {
-                    const float* sl = s_acc + (w4 * RCHUNK + tid) * SV;
-#pragma unroll
-                    for (int j = 0; j < SV; j++) a[j] += sl[j];
-                }
-            }
-            // sums of (w, w du, w dv) and of the per-pixel conic terms -> gradients (see the loop)
-            const float* rec = s_geom + tid * GS_PACKED_WIDTH;
-            const float ca = rec[4], cb = rec[5], cc = rec[6];
-            const float k = -0.5f * rec[3] * rec[8];
-            const float Mu = a[4], Mv = a[5];
-            a[4] = -2.0f * k * (cc * Mu - cb * Mv);
-            a[5] = -2.0f * k * (ca * Mv - cb * Mu);
-            a[6] *= k;
-            a[7] *= k;
-            a[8] *= k;
-            float* row = s_acc + tid * SV;
-#pragma unroll
-            for (int j = 0; j < SV; j++) row[j] = a[j];
-        }
+        // coefficients went out with the batches).  Phase 1: flush_sum_slots
+        flush_sum_slots<RCHUNK, SV>(s_acc, s_geom, s_hit, tid, cnt);
         __syncthreads();
         // Phase 2, nine lanes = one row: seven rows per wave instruction, consecutive addresses (see k_render_bwd)
         const int sub = lane / SV, col = lane - sub * SV;   // lane 63: idle
@@ -2259,8 +2275,9 @@ __global__ __launch_bounds__(RB) void k_render_depth(const float* __restrict__ p
 // No background, no normalisation.  The kernels stand BESIDE the colour kernels (whose ISA is left alone): plain walks
 // of the touch masks, one record read per visit, no flags, costs, segments or handed-over masks.  They read
 // num_splats_per_pixel and never look beyond it, so they need no saturation test and are correct on prefix-sorted
-// lists (a tile is ordered as far as any of its pixels walked).  The staged record's first colour word (word 9, which
-// nobody here reads as a colour) carries z.
+// lists (a tile is ordered as far as any of its pixels walked).
+// The walks are render_map_fwd and render_map_bwd below, shared with the feature maps further down: everything about
+// alpha, T, the order of the sums and the slab is there, once; z enters through the depth policies (DepthFwd, DepthBwd).
 //
 // alpha of one (pixel, staged record) pair and whether it contributes -- the forward's decisions, bit for bit: the
 // cutoff radius, the IEEE quotient from the stored reciprocal, exp_neg_half, zero unless mh > 0, alpha >= 1/255.
@@ -2296,17 +2313,25 @@ __device__ __forceinline__ void zalpha_reach(int nsp, int n_tile, int tid, int* 
     wave_used = __builtin_amdgcn_readfirstlane(m);
 }
 
-// One workgroup per tile.  Writes depth, alpha and T_end [H, W] of the tile's pixels inside the image.  T_end is
-// stored itself: at alpha = 0.99999 the difference 1 - alpha formed in fp32 is good to about 1 %.
-__global__ __launch_bounds__(RB) void k_render_zalpha_fwd(
-    const float* __restrict__ packed, const float* __restrict__ xyz_cam, const int* __restrict__ ranges,
-    const int* __restrict__ sorted, const int* __restrict__ nsp_in, int W, int H, int ntx, int tile0, int nt,
-    float* __restrict__ depth, float* __restrict__ alpha_out, float* __restrict__ t_out) {
-    constexpr int RCHUNK = 256;
+constexpr int MAP_FWD_CHUNK = 256;   // entries staged per chunk of the forward walk
+constexpr int MAP_BWD_CHUNK = 64;    // of the backward walk: one mask word, one slot of nine sums per (wave, entry)
+
+// The forward walk of one tile (one workgroup, a wave per 8 x 8 patch): alpha and T_end [H, W] of the tile's pixels
+// inside the image, and the channel policy's map.  T_end is stored itself: at alpha = 0.99999 the difference
+// 1 - alpha formed in fp32 is good to about 1 %.  The pixel's N channel sums M are locals of the walk, beside T and A
+// (as members of the policy object they cost k_render_features_fwd<4> about 0.6 %).  Ch supplies
+//   N                                               the number of channel sums per pixel
+//   stage(sorted, first, cnt, tid, s_geom, s_idx)   the chunk's channel values into LDS, beside the records (s_idx: the
+//                                                   Gaussian indices stage_chunk kept, nullptr in the forward)
+//   add(M, w, rec, i)                               staged entry i (rec: its record) enters the sums with weight w
+//   store(M, p)                                     the sums to the map
+template <class Ch>
+__device__ __forceinline__ void render_map_fwd(
+    const Ch ch, const float* __restrict__ packed, const int* __restrict__ ranges, const int* __restrict__ sorted,
+    const int* __restrict__ nsp_in, int W, int H, int ntx, int tile0, int nt, float* __restrict__ alpha_out,
+    float* __restrict__ t_out, float* s_geom, unsigned long long (*s_mask)[MAP_FWD_CHUNK / 64], int* s_max) {
+    constexpr int RCHUNK = MAP_FWD_CHUNK;
     constexpr int NW = RCHUNK / 64;
-    __shared__ alignas(16) float s_geom[RCHUNK * GS_PACKED_WIDTH];
-    __shared__ unsigned long long s_mask[4][NW];
-    __shared__ int s_max[4];
     const int t_local = tile_of_block(blockIdx.x, nt);
     if (t_local >= nt) return;
     const int tile = tile0 + t_local;
@@ -2320,12 +2345,15 @@ __global__ __launch_bounds__(RB) void k_render_zalpha_fwd(
     int n_used, wave_used;
     zalpha_reach(nsp, n_tile, tid, s_max, n_used, wave_used);
     const float pu = float(px.u), pv = float(px.v);
-    float T = 1.0f, D = 0.0f, A = 0.0f;
+    float T = 1.0f, A = 0.0f;
+    float M[Ch::N];   // the pixel's sums of the map's channels
+#pragma unroll
+    for (int c = 0; c < Ch::N; c++) M[c] = 0.0f;
     for (int base = 0; base < n_used; base += RCHUNK) {
         const int cnt = min(RCHUNK, n_used - base);
         if (base > 0) __syncthreads();   // the previous chunk's readers are done
         stage_chunk<float, 1>(packed, nullptr, sorted, s0 + base, cnt, tid, s_geom, nullptr, nullptr);
-        if (tid < cnt) s_geom[tid * GS_PACKED_WIDTH + 9] = xyz_cam[(size_t)sorted[s0 + base + tid] * 3 + 2];
+        ch.stage(sorted, s0 + base, cnt, tid, s_geom, nullptr);
         // (no barrier in between: thread t tests the record thread t staged)
         build_touch_masks<float, RCHUNK>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
         __syncthreads();
@@ -2340,11 +2368,10 @@ __global__ __launch_bounds__(RB) void k_render_zalpha_fwd(
                 const float* rec = s_geom + i * GS_PACKED_WIDTH;
                 const Vec4<float> g0 = *reinterpret_cast<const Vec4<float>*>(rec);       // u v r2 opacity
                 const Vec4<float> g1 = *reinterpret_cast<const Vec4<float>*>(rec + 4);   // a b c det
-                const Vec4<float> g2 = *reinterpret_cast<const Vec4<float>*>(rec + 8);   // 1/det, z
-                const ZalphaVisit v = zalpha_alpha(g0, g1, g2.x, pu, pv, k < nsp);
+                const ZalphaVisit v = zalpha_alpha(g0, g1, rec[8], pu, pv, k < nsp);
                 if (v.contrib) {
                     const float w = v.alpha * T;
-                    D = __builtin_fmaf(w, g2.y, D);
+                    ch.add(M, w, rec, i);
                     A += w;
                     T = __builtin_fmaf(-v.alpha, T, T);   // T (1 - alpha), one rounding
                 }
@@ -2352,35 +2379,40 @@ __global__ __launch_bounds__(RB) void k_render_zalpha_fwd(
         }
     }
     if (valid) {
-        depth[p] = D;
+        ch.store(M, p);
         alpha_out[p] = A;
         t_out[p] = T;
     }
 }
 
-// The true derivative of the two maps (the contribute / stop decisions held constant), back to front from T_end with
-// c_k = g_depth z_k + g_alpha:
-//   T_k = T / (1 - alpha_k)      dL/dalpha_k = T_k c_k - S / (1 - alpha_k)      S += alpha_k T_k c_k      dL/dz_k = g_depth w_k
-// and alpha -> opacity, u, v, conic as k_render_bwd chains them (the per-splat factor -0.5 opacity / det in the flush).
-// No walk quirk is replicated: this output has no reference to be compatible with.  alpha above 0.9999
-// enters the derivative as 0.9999, as in k_render_bwd (Q4).  Seven sums per (wave, entry) -- z | opacity | w du, w dv |
-// conic 3 -- through reduce9_to_slot with two zero inputs into the wave's own LDS slot, the four waves' slots added
-// per chunk, one global atomic per value per (entry, tile): grad_z[g] and columns 3..8 of the [V, 9] slab (columns
-// 0..2 are not touched).  Chunks of 64 entries, from the tile's deepest num_splats_per_pixel to the front, tiles in
-// grid order.
-__global__ __launch_bounds__(RB) void k_render_zalpha_bwd(
-    const float* __restrict__ packed, const float* __restrict__ xyz_cam, const int* __restrict__ ranges,
-    const int* __restrict__ sorted, const int* __restrict__ nsp_in, const float* __restrict__ t_in,
-    const float* __restrict__ g_depth, const float* __restrict__ g_alpha, int W, int H, int ntx, int tile0, int nt,
-    float* __restrict__ slab, float* __restrict__ grad_z) {
-    constexpr int SV = 9;        // width of a slot: z, 0, 0 | w, w du, w dv | conic terms 3
-    constexpr int RCHUNK = 64;
-    __shared__ alignas(16) float s_geom[RCHUNK * GS_PACKED_WIDTH];
-    __shared__ int s_idx[RCHUNK];
-    __shared__ float s_acc[4 * RCHUNK * SV];   // [wave][splat][9]
-    __shared__ int s_max[4];
-    __shared__ unsigned long long s_mask[4][1];
-    __shared__ unsigned long long s_hit[4];    // slots written by each wave
+// The true derivative of a map and of alpha (the contribute / stop decisions held constant), back to front from T_end
+// with c_k = g_alpha + <g_map, channels of entry k>:
+//   T_k = T / (1 - alpha_k)      dL/dalpha_k = T_k c_k - S / (1 - alpha_k)      S += alpha_k T_k c_k
+// and alpha -> opacity, u, v, conic as k_render_bwd chains them (the per-splat factor -0.5 opacity / det in
+// flush_sum_slots).  No walk quirk is replicated: this output has no reference to be compatible with.
+// alpha above 0.9999 enters the derivative as 0.9999, as in k_render_bwd (Q4).  Nine sums per (wave, entry) -- the
+// policy's column 0, two zeros | opacity | w du, w dv | conic 3 -- through reduce9_to_slot into the wave's own LDS
+// slot, the four waves' slots added per chunk (flush_sum_slots), then nine lanes per row, one global atomic per value
+// per (entry, tile): columns 3..8 of the [V, 9] slab, columns 0..2 wherever the policy sends them (the slab's colour
+// columns are not touched); rows of zeros stay untouched.  Chunks of 64 entries, from the tile's deepest
+// num_splats_per_pixel to the front, tiles in grid order.  Ch supplies
+//   stage(sorted, first, cnt, tid, s_geom, s_idx)   as the forward's
+//   load(p)                                         the pixel's incoming map gradient (pixels outside the image: zeros)
+//   begin(lane, wave)                               once the tile is known to have work
+//   c(ga, g2, i)                                    c_k of staged entry i (g2: words 8..11 of its record)
+//   column0(aT)                                     the contributing lane's input to sum 0, from w_k = alpha_k T_k
+//   visited(aT, g)                                  after the slot of an entry (Gaussian g) is written; aT = 0 in lanes
+//                                                   that did not contribute
+//   send(g, col, x)                                 the sum x of column col < 3 of Gaussian g's row, to where it belongs
+//   finish()                                        after the last chunk
+template <class Ch>
+__device__ __forceinline__ void render_map_bwd(
+    Ch& ch, const float* __restrict__ packed, const int* __restrict__ ranges, const int* __restrict__ sorted,
+    const int* __restrict__ nsp_in, const float* __restrict__ t_in, const float* __restrict__ g_alpha, int W, int H,
+    int ntx, int tile0, int nt, float* __restrict__ slab, float* s_geom, int* s_idx, float* s_acc, int* s_max,
+    unsigned long long (*s_mask)[1], unsigned long long (*s_hit)[1]) {
+    constexpr int SV = 9;
+    constexpr int RCHUNK = MAP_BWD_CHUNK;
     const int t_local = tile_of_block(blockIdx.x, nt);
     if (t_local >= nt) return;
     const int tile = tile0 + t_local;
@@ -2391,12 +2423,12 @@ __global__ __launch_bounds__(RB) void k_render_zalpha_bwd(
     const int n_tile = ranges[tile + 1] - s0;
     if (n_tile <= 0) return;
     int nsp = 0;
-    float T = 1.0f, gd = 0.0f, ga = 0.0f;
+    float T = 1.0f, ga = 0.0f;
     if (valid) {
         const size_t p = (size_t)px.v * W + px.u;
         nsp = nsp_in[p];
         T = t_in[p];
-        if (g_depth != nullptr) gd = g_depth[p];
+        ch.load(p);
         if (g_alpha != nullptr) ga = g_alpha[p];
     }
     int n_used, wave_used;
@@ -2406,13 +2438,14 @@ __global__ __launch_bounds__(RB) void k_render_zalpha_bwd(
     const int slot_off = slot_lane_offset(lane);
     const bool slot_stores = slot_off >= 0;
     const int slot_lane_base = wave * RCHUNK * SV + (slot_stores ? slot_off : 0);
+    ch.begin(lane, wave);
     float S = 0.0f;   // sum of alpha_j T_j c_j over the contributors behind the current entry
     for (int chunk = (n_used - 1) / RCHUNK; chunk >= 0; chunk--) {
         const int base = chunk * RCHUNK;
         const int cnt = min(RCHUNK, n_used - base);
         __syncthreads();   // previous chunk fully flushed
         stage_chunk<float, 1>(packed, nullptr, sorted, s0 + base, cnt, tid, s_geom, nullptr, s_idx);
-        if (tid < cnt) s_geom[tid * GS_PACKED_WIDTH + 9] = xyz_cam[(size_t)s_idx[tid] * 3 + 2];
+        ch.stage(sorted, s0 + base, cnt, tid, s_geom, s_idx);
         // (no barrier in between: thread t tests the record thread t staged)
         build_touch_masks<float, RCHUNK>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
         __syncthreads();
@@ -2426,25 +2459,25 @@ __global__ __launch_bounds__(RB) void k_render_zalpha_bwd(
             const float* rec = s_geom + i * GS_PACKED_WIDTH;
             const Vec4<float> g0 = *reinterpret_cast<const Vec4<float>*>(rec);       // u v r2 opacity
             const Vec4<float> g1 = *reinterpret_cast<const Vec4<float>*>(rec + 4);   // a b c det
-            const Vec4<float> g2 = *reinterpret_cast<const Vec4<float>*>(rec + 8);   // 1/det, z
+            const Vec4<float> g2 = *reinterpret_cast<const Vec4<float>*>(rec + 8);   // 1/det, z (depth)
             const ZalphaVisit v = zalpha_alpha(g0, g1, g2.x, pu, pv, k < nsp);
             if (ballot(v.contrib) == 0) continue;   // every reaching lane skipped the entry
-            float gz = 0.0f, w = 0.0f;
+            float v0 = 0.0f, w = 0.0f, aT = 0.0f;
             if (v.contrib) {
                 float alpha = v.alpha;
                 if (alpha > Thr<float>::sat_gt()) alpha = Thr<float>::alpha_cap();   // min(0.9999, .)
                 const float r1ma = fast_rcp(1.0f - alpha);
-                const float c = __builtin_fmaf(gd, g2.y, ga);
+                const float c = ch.c(ga, g2, i);
                 T = T * r1ma;                        // T_k: the transmittance in front of the entry
-                const float aT = alpha * T;          // w_k
+                aT = alpha * T;                      // w_k
                 const float dalpha = T * c - S * r1ma;
                 S = __builtin_fmaf(aT, c, S);
-                gz = gd * aT;
+                v0 = ch.column0(aT);
                 w = v.norm_prob * dalpha;
             }
             float val[9];
             const float du2 = v.du * v.du, dv2 = v.dv * v.dv, duv = v.du * v.dv;
-            val[0] = gz; val[1] = 0.0f; val[2] = 0.0f;
+            val[0] = v0; val[1] = 0.0f; val[2] = 0.0f;
             val[3] = w; val[4] = w * v.du; val[5] = w * v.dv;
             val[6] = (dv2 - g1.z * v.mh) * w;
             val[7] = (g1.y * v.mh - duv) * w;
@@ -2453,66 +2486,111 @@ __global__ __launch_bounds__(RB) void k_render_zalpha_bwd(
             asm volatile("" : "+s"(slot_i));
             reduce9_to_slot(val, slot_stores, s_acc, slot_lane_base + slot_i);
             hit |= 1ull << i;
+            ch.visited(aT, s_idx[i]);
         }
-        if (lane == 0) s_hit[wave] = hit;
+        if (lane == 0) s_hit[wave][0] = hit;
         __syncthreads();
-        // the flush, as k_render_bwd's.  Phase 1, thread = entry: add the slots of the waves that wrote it, in wave
-        // order, apply the per-splat factors and park the row in wave 0's slot of the same entry
-        if (tid < cnt) {
-            float a[SV];
-#pragma unroll
-            for (int j = 0; j < SV; j++) a[j] = 0;
-#pragma unroll
-            for (int w4 = 0; w4 < 4; w4++) {
-                if ((s_hit[w4] >> tid) & 1ull) {
-                    const float* sl = s_acc + (w4 * RCHUNK + tid) * SV;
-#pragma unroll
-                    for (int j = 0; j < SV; j++) a[j] += sl[j];
-                }
-            }
-            const float* rec = s_geom + tid * GS_PACKED_WIDTH;
-            const float ca = rec[4], cb = rec[5], cc = rec[6];
-            const float kf = -0.5f * rec[3] * rec[8];
-            const float Mu = a[4], Mv = a[5];
-            a[4] = -2.0f * kf * (cc * Mu - cb * Mv);
-            a[5] = -2.0f * kf * (ca * Mv - cb * Mu);
-            a[6] *= kf;
-            a[7] *= kf;
-            a[8] *= kf;
-            float* row = s_acc + tid * SV;
-#pragma unroll
-            for (int j = 0; j < SV; j++) row[j] = a[j];
-        }
+        // (the thread index of the flush is formed here, inside the chunk loop, as slot_i above: left to the compiler, the
+        // twelve slot addresses of flush_sum_slots are hoisted over the whole walk and k_render_features_bwd<4> takes 120
+        // VGPRs where its own body took 104; profiles/r12/map_walk_isa.txt)
+        int row_tid = tid;
+        asm volatile("" : "+v"(row_tid));
+        flush_sum_slots<RCHUNK, SV>(s_acc, s_geom, s_hit, row_tid, cnt);
         __syncthreads();
-        // Phase 2, nine lanes = one row (seven rows per wave instruction); rows of zeros stay untouched, and so do
-        // the slab's colour columns
+        // nine lanes = one row (seven rows per wave instruction, see k_render_bwd)
         const int sub = lane / SV, col = lane - sub * SV;   // lane 63: idle
         for (int r0 = wave * 7; r0 < cnt; r0 += 28) {
             const int r = r0 + sub;
             const bool in = lane < 63 && r < cnt;
-            const float v = in ? s_acc[r * SV + col] : 0.0f;
-            const unsigned long long nz = ballot(v != 0.0f);
+            const float x = in ? s_acc[r * SV + col] : 0.0f;
+            const unsigned long long nz = ballot(x != 0.0f);
             const bool any = in && ((nz >> (sub * SV)) & 0x1ffull) != 0;
             if (any) {
                 const int g = s_idx[r];
-                if (col == 0) global_add(grad_z + g, v);
-                else if (col >= 3) global_add(slab + (size_t)g * SV + col, v);
+                if (col >= 3) global_add(slab + (size_t)g * SV + col, x);
+                else ch.send(g, col, x);
             }
         }
     }
+    ch.finish();
+}
+
+// The depth policy: one channel, z = xyz_camera_frame[:, 2], staged into the record's first colour word (word 9, which
+// nobody here reads as a colour).
+struct DepthChannel {
+    const float* __restrict__ xyz_cam;
+    __device__ __forceinline__ void stage(const int* __restrict__ sorted, int first, int cnt, int tid, float* s_geom,
+                                          const int* s_idx) const {
+        if (tid < cnt) {
+            const int g = s_idx != nullptr ? s_idx[tid] : sorted[first + tid];   // (what this thread staged)
+            s_geom[tid * GS_PACKED_WIDTH + 9] = xyz_cam[(size_t)g * 3 + 2];
+        }
+    }
+};
+struct DepthFwd : DepthChannel {
+    float* __restrict__ depth;
+    static constexpr int N = 1;
+    __device__ __forceinline__ void add(float (&D)[1], float w, const float* rec, int) const {
+        D[0] = __builtin_fmaf(w, rec[9], D[0]);
+    }
+    __device__ __forceinline__ void store(const float (&D)[1], size_t p) const { depth[p] = D[0]; }
+};
+// c_k = g_depth z_k + g_alpha, dL/dz_k = g_depth w_k: sum 0 of the slot, added to grad_z[g]
+struct DepthBwd : DepthChannel {
+    const float* __restrict__ g_depth;
+    float* __restrict__ grad_z;
+    float gd = 0.0f;
+    __device__ __forceinline__ void load(size_t p) {
+        if (g_depth != nullptr) gd = g_depth[p];
+    }
+    __device__ __forceinline__ void begin(int, int) const {}
+    __device__ __forceinline__ float c(float ga, const Vec4<float>& g2, int) const { return __builtin_fmaf(gd, g2.y, ga); }
+    __device__ __forceinline__ float column0(float aT) const { return gd * aT; }
+    __device__ __forceinline__ void visited(float, int) const {}
+    __device__ __forceinline__ void send(int g, int col, float x) const {
+        if (col == 0) global_add(grad_z + g, x);
+    }
+    __device__ __forceinline__ void finish() const {}
+};
+
+__global__ __launch_bounds__(RB) void k_render_zalpha_fwd(
+    const float* __restrict__ packed, const float* __restrict__ xyz_cam, const int* __restrict__ ranges,
+    const int* __restrict__ sorted, const int* __restrict__ nsp_in, int W, int H, int ntx, int tile0, int nt,
+    float* __restrict__ depth, float* __restrict__ alpha_out, float* __restrict__ t_out) {
+    __shared__ alignas(16) float s_geom[MAP_FWD_CHUNK * GS_PACKED_WIDTH];
+    __shared__ unsigned long long s_mask[4][MAP_FWD_CHUNK / 64];
+    __shared__ int s_max[4];
+    DepthFwd ch{{xyz_cam}, depth};
+    render_map_fwd(ch, packed, ranges, sorted, nsp_in, W, H, ntx, tile0, nt, alpha_out, t_out, s_geom, s_mask, s_max);
+}
+
+__global__ __launch_bounds__(RB) void k_render_zalpha_bwd(
+    const float* __restrict__ packed, const float* __restrict__ xyz_cam, const int* __restrict__ ranges,
+    const int* __restrict__ sorted, const int* __restrict__ nsp_in, const float* __restrict__ t_in,
+    const float* __restrict__ g_depth, const float* __restrict__ g_alpha, int W, int H, int ntx, int tile0, int nt,
+    float* __restrict__ slab, float* __restrict__ grad_z) {
+    __shared__ alignas(16) float s_geom[MAP_BWD_CHUNK * GS_PACKED_WIDTH];
+    __shared__ int s_idx[MAP_BWD_CHUNK];
+    __shared__ float s_acc[4 * MAP_BWD_CHUNK * 9];   // [wave][entry][9]
+    __shared__ int s_max[4];
+    __shared__ unsigned long long s_mask[4][1];
+    __shared__ unsigned long long s_hit[4][1];       // slots written by each wave
+    DepthBwd ch{{xyz_cam}, g_depth, grad_z};
+    render_map_bwd(ch, packed, ranges, sorted, nsp_in, t_in, g_alpha, W, H, ntx, tile0, nt, slab, s_geom, s_idx, s_acc,
+                   s_max, s_mask, s_hit);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // per-Gaussian feature vectors composited with the frame's weights (no reference counterpart), fp32
 // ---------------------------------------------------------------------------------------------------
-// The depth / alpha walks above with the one channel z generalised to C <= 32 caller-supplied channels:
+// render_map_fwd / render_map_bwd with C <= 32 caller-supplied channels in place of the one channel z:
 //   feature_map[p, c] = sum w_k features[g_k, c]      alpha[p] = sum w_k      T_end
-// with alpha_k, the contribute decision and w_k = alpha_k T_k from zalpha_alpha and the same update order, so alpha and
-// T_end are bit-equal to k_render_zalpha_fwd's and a channel holding z gives its depth.  The kernels are templated on
-// a padded channel count CP and instantiated for CP = 4, 8, 16, 32 (the next one at or above n_channels runs): a
-// feature row is staged into LDS beside the geometry records with a pitch of CP floats (16-byte aligned, read as
-// ds_read_b128 broadcasts), the channels from n_channels to CP - 1 staged as zeros.  Nothing beyond column
-// n_channels - 1 of features, feature_map, grad_feature_map or grad_features is read or written.
+// The walk is the depth kernels' own, so alpha and T_end are bit-equal to k_render_zalpha_fwd's and a channel holding
+// z gives its depth.  The policies are templated on a padded channel count CP and instantiated for CP = 4, 8, 16, 32
+// (the next one at or above n_channels runs): a feature row is staged into LDS beside the geometry records with a
+// pitch of CP floats (16-byte aligned, read as ds_read_b128 broadcasts), the channels from n_channels to CP - 1 staged
+// as zeros.  Nothing beyond column n_channels - 1 of features, feature_map, grad_feature_map or grad_features is read
+// or written.
 template <int CP>
 __device__ __forceinline__ void stage_features(const float* __restrict__ features, int C, const int* __restrict__ sorted,
                                                int first, int cnt, int tid, float* s_feat) {
@@ -2538,79 +2616,43 @@ __device__ __forceinline__ void stage_features(const float* __restrict__ feature
     }
 }
 
-// One workgroup per tile, a wave per 8 x 8 patch.  Writes feature_map [H, W, C], alpha and T_end [H, W] of the tile's
-// pixels inside the image.  LDS: 12 KB of records + CP KB of feature rows.
 template <int CP>
-__global__ __launch_bounds__(RB) void k_render_features_fwd(
-    const float* __restrict__ packed, const float* __restrict__ features, int C, const int* __restrict__ ranges,
-    const int* __restrict__ sorted, const int* __restrict__ nsp_in, int W, int H, int ntx, int tile0, int nt,
-    float* __restrict__ fmap, float* __restrict__ alpha_out, float* __restrict__ t_out) {
+struct FeatureRows {
     static_assert(CP % 4 == 0 && CP >= 4 && CP <= 32, "padded channel count");
-    constexpr int RCHUNK = 256;
-    constexpr int NW = RCHUNK / 64;
-    __shared__ alignas(16) float s_geom[RCHUNK * GS_PACKED_WIDTH];
-    __shared__ alignas(16) float s_feat[RCHUNK * CP];
-    __shared__ unsigned long long s_mask[4][NW];
-    __shared__ int s_max[4];
-    const int t_local = tile_of_block(blockIdx.x, nt);
-    if (t_local >= nt) return;
-    const int tile = tile0 + t_local;
-    const int tid = threadIdx.x, wave = tid >> 6;
-    const PixelMap px = pixel_of_thread(tile % ntx, tile / ntx, tid);
-    const bool valid = px.u < W && px.v < H;
-    const size_t p = (size_t)px.v * W + px.u;
-    const int s0 = ranges[tile];
-    const int n_tile = ranges[tile + 1] - s0;
-    const int nsp = valid ? nsp_in[p] : 0;
-    int n_used, wave_used;
-    zalpha_reach(nsp, n_tile, tid, s_max, n_used, wave_used);
-    const float pu = float(px.u), pv = float(px.v);
-    float T = 1.0f, A = 0.0f;
-    float F[CP];
+    const float* __restrict__ features;
+    int C;
+    float* s_feat;   // [chunk entry][CP]
+    __device__ __forceinline__ void stage(const int* __restrict__ sorted, int first, int cnt, int tid, float*,
+                                          const int*) const {
+        stage_features<CP>(features, C, sorted, first, cnt, tid, s_feat);
+    }
+    // whether the C-float rows of a [H, W, C] map are whole 16-byte words (workgroup-uniform): a quarter of the memory
+    // instructions; at 32 channels the map is 128 bytes per pixel and the forward of a short-list frame is bound by
+    // writing it
+    __device__ __forceinline__ bool rows_of_vec4(const float* map) const {
+        return (C & 3) == 0 && ((uintptr_t)map & 15) == 0;
+    }
+};
+
+template <int CP>
+struct FeaturesFwd : FeatureRows<CP> {
+    float* __restrict__ fmap;
+    static constexpr int N = CP;
+    __device__ __forceinline__ void add(float (&F)[CP], float w, const float*, int i) const {
+        const Vec4<float>* f4 = reinterpret_cast<const Vec4<float>*>(this->s_feat + i * CP);
 #pragma unroll
-    for (int c = 0; c < CP; c++) F[c] = 0.0f;
-    for (int base = 0; base < n_used; base += RCHUNK) {
-        const int cnt = min(RCHUNK, n_used - base);
-        if (base > 0) __syncthreads();   // the previous chunk's readers are done
-        stage_chunk<float, 1>(packed, nullptr, sorted, s0 + base, cnt, tid, s_geom, nullptr, nullptr);
-        stage_features<CP>(features, C, sorted, s0 + base, cnt, tid, s_feat);
-        // (no barrier in between: thread t tests the record thread t staged)
-        build_touch_masks<float, RCHUNK>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
-        __syncthreads();
-        for (int word = 0; word < NW && word * 64 < cnt; word++) {
-            if (base + word * 64 >= wave_used) break;   // wave-uniform: no pixel of the patch walked this far
-            unsigned long long m = wave_uniform(s_mask[wave][word]);
-            while (m) {
-                const int i = word * 64 + __builtin_ctzll(m);
-                m &= m - 1;
-                const int k = base + i;
-                if (k >= wave_used) break;
-                const float* rec = s_geom + i * GS_PACKED_WIDTH;
-                const Vec4<float> g0 = *reinterpret_cast<const Vec4<float>*>(rec);       // u v r2 opacity
-                const Vec4<float> g1 = *reinterpret_cast<const Vec4<float>*>(rec + 4);   // a b c det
-                const ZalphaVisit v = zalpha_alpha(g0, g1, rec[8], pu, pv, k < nsp);
-                if (v.contrib) {
-                    const float w = v.alpha * T;
-                    const Vec4<float>* f4 = reinterpret_cast<const Vec4<float>*>(s_feat + i * CP);
-#pragma unroll
-                    for (int c4 = 0; c4 < CP / 4; c4++) {
-                        const Vec4<float> f = f4[c4];
-                        F[4 * c4 + 0] = __builtin_fmaf(w, f.x, F[4 * c4 + 0]);
-                        F[4 * c4 + 1] = __builtin_fmaf(w, f.y, F[4 * c4 + 1]);
-                        F[4 * c4 + 2] = __builtin_fmaf(w, f.z, F[4 * c4 + 2]);
-                        F[4 * c4 + 3] = __builtin_fmaf(w, f.w, F[4 * c4 + 3]);
-                    }
-                    A += w;
-                    T = __builtin_fmaf(-v.alpha, T, T);   // T (1 - alpha), one rounding
-                }
-            }
+        for (int c4 = 0; c4 < CP / 4; c4++) {
+            const Vec4<float> f = f4[c4];
+            F[4 * c4 + 0] = __builtin_fmaf(w, f.x, F[4 * c4 + 0]);
+            F[4 * c4 + 1] = __builtin_fmaf(w, f.y, F[4 * c4 + 1]);
+            F[4 * c4 + 2] = __builtin_fmaf(w, f.z, F[4 * c4 + 2]);
+            F[4 * c4 + 3] = __builtin_fmaf(w, f.w, F[4 * c4 + 3]);
         }
     }
-    if (valid) {
+    __device__ __forceinline__ void store(const float (&F)[CP], size_t p) const {
+        const int C = this->C;
         float* row = fmap + p * C;
-        if ((C & 3) == 0 && ((uintptr_t)fmap & 15) == 0) {
-            // rows of whole 16-byte words (workgroup-uniform): a quarter of the store instructions; at 32 channels the
-            // map is 128 bytes per pixel and the forward of a short-list frame is bound by writing it
+        if (this->rows_of_vec4(fmap)) {
 #pragma unroll
             for (int c4 = 0; c4 < CP / 4; c4++) {
                 if (4 * c4 < C) {
@@ -2624,103 +2666,62 @@ __global__ __launch_bounds__(RB) void k_render_features_fwd(
             for (int c = 0; c < CP; c++)
                 if (c < C) row[c] = F[c];
         }
-        alpha_out[p] = A;
-        t_out[p] = T;
     }
-}
+};
 
-// The true derivative of the two maps (decisions held constant), k_render_zalpha_bwd's walk with
-//   c_k = g_alpha + sum_c g[c] f_k[c]   (a fused multiply-add chain from g_alpha, channels ascending)
-//   T_k = T / (1 - alpha_k)      dL/dalpha_k = T_k c_k - S / (1 - alpha_k)      S += alpha_k T_k c_k
-// The six geometry sums go through reduce9_to_slot (three zero inputs) and the two-phase flush into columns 3..8 of
-// the slab.  The feature gradient dL/df[k, c] = sum_pixels w_k(p) g[p, c] does not: per wave it is the contraction
-// [channels x 64 pixels] x [64 pixels x 16 entries], done with v_mfma_f32_16x16x4_f32 (exact fp32) on batches of 16
-// contributing entries as k_render_bwd_sh contracts its coefficient gradients -- the pixel-side operand g[pixel][channel]
-// stays in registers for the whole walk (y_op, one set of 16 per block of 16 channels), the entries' w_k go to the
-// wave's LDS batch, two accumulator chains per channel block, and the results are added straight to grad_features
-// rows, consecutive lanes on consecutive words of a row.  A batch stays open across chunks (it keeps the Gaussian
-// indices itself) and the partial one is flushed at the end of the walk.  grad_features == nullptr: none of it runs.
-// LDS: 3 KB records + CP / 4 KB feature rows + 9 KB slots + 17 KB batches.
+// c_k = g_alpha + sum_c g[c] f_k[c] (a fused multiply-add chain from g_alpha, channels ascending); the slot's sum 0
+// stays zero.  The feature gradient dL/df[k, c] = sum_pixels w_k(p) g[p, c] does not go through the slots: per wave it
+// is the contraction [channels x 64 pixels] x [64 pixels x 16 entries], done with v_mfma_f32_16x16x4_f32 (exact fp32)
+// on batches of 16 contributing entries as k_render_bwd_sh contracts its coefficient gradients -- the pixel-side
+// operand g[pixel][channel] stays in registers for the whole walk (y_op, one set of 16 per block of 16 channels), the
+// entries' w_k go to the wave's LDS batch, two accumulator chains per channel block, and the results are added
+// straight to grad_features rows, consecutive lanes on consecutive words of a row.  A batch stays open across chunks
+// (it keeps the Gaussian indices itself) and the partial one is flushed at the end of the walk.
+// grad_features == nullptr: none of it runs.
 template <int CP>
-__global__ __launch_bounds__(RB) void k_render_features_bwd(
-    const float* __restrict__ packed, const float* __restrict__ features, int C, const int* __restrict__ ranges,
-    const int* __restrict__ sorted, const int* __restrict__ nsp_in, const float* __restrict__ t_in,
-    const float* __restrict__ g_map, const float* __restrict__ g_alpha, int W, int H, int ntx, int tile0, int nt,
-    float* __restrict__ slab, float* __restrict__ grad_features) {
-    static_assert(CP % 4 == 0 && CP >= 4 && CP <= 32, "padded channel count");
-    constexpr int SV = 9;        // width of a slot: 0, 0, 0 | w, w du, w dv | conic terms 3
-    constexpr int RCHUNK = 64;
-    constexpr int MB = 16;               // entries per MFMA batch (the N of 16x16x4)
-    constexpr int BROW = 64 + 4;         // floats per row of the batch's weight matrix [slot][pixel]
-    constexpr int NBLK = (CP + 15) / 16; // blocks of 16 channels (the M of 16x16x4)
-    constexpr int OW = 16 * NBLK;        // floats per slot of the batch's result [slot][channel]
+struct FeaturesBwd : FeatureRows<CP> {
+    static constexpr int MB = 16;               // entries per MFMA batch (the N of 16x16x4)
+    static constexpr int BROW = 64 + 4;         // floats per row of the batch's weight matrix [slot][pixel]
+    static constexpr int NBLK = (CP + 15) / 16; // blocks of 16 channels (the M of 16x16x4)
+    static constexpr int OW = 16 * NBLK;        // floats per slot of the batch's result [slot][channel]
     static_assert(64 * 17 <= MB * BROW && MB * OW <= MB * BROW, "scratch uses of the wave's batch rows");
-    __shared__ alignas(16) float s_geom[RCHUNK * GS_PACKED_WIDTH];
-    __shared__ alignas(16) float s_feat[RCHUNK * CP];
-    __shared__ int s_idx[RCHUNK];
-    __shared__ float s_acc[4 * RCHUNK * SV];          // [wave][splat][9]
-    __shared__ alignas(16) float s_B[4 * MB * BROW];  // [wave][slot][pixel] w of the open batch
-    __shared__ int s_bidx[4 * MB];                    // [wave][slot] Gaussian index of the entry
-    __shared__ int s_max[4];
-    __shared__ unsigned long long s_mask[4][1];
-    __shared__ unsigned long long s_hit[4];           // slots written by each wave
-    const int t_local = tile_of_block(blockIdx.x, nt);
-    if (t_local >= nt) return;
-    const int tile = tile0 + t_local;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const PixelMap px = pixel_of_thread(tile % ntx, tile / ntx, tid);
-    const bool valid = px.u < W && px.v < H;
-    const int s0 = ranges[tile];
-    const int n_tile = ranges[tile + 1] - s0;
-    if (n_tile <= 0) return;
-    int nsp = 0;
-    float T = 1.0f, ga = 0.0f;
-    float g[CP];
-#pragma unroll
-    for (int c = 0; c < CP; c++) g[c] = 0.0f;
-    if (valid) {
-        const size_t p = (size_t)px.v * W + px.u;
-        nsp = nsp_in[p];
-        T = t_in[p];
-        if (g_map != nullptr) {
-            if ((C & 3) == 0 && ((uintptr_t)g_map & 15) == 0) {   // rows of whole 16-byte words (workgroup-uniform)
-#pragma unroll
-                for (int c4 = 0; c4 < CP / 4; c4++) {
-                    if (4 * c4 < C) {
-                        const Vec4<float> v4 = reinterpret_cast<const Vec4<float>*>(g_map + p * C)[c4];
-                        g[4 * c4 + 0] = v4.x; g[4 * c4 + 1] = v4.y; g[4 * c4 + 2] = v4.z; g[4 * c4 + 3] = v4.w;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < CP; c++)
-                    if (c < C) g[c] = g_map[p * C + c];
-            }
-        }
-        if (g_alpha != nullptr) ga = g_alpha[p];
-    }
-    int n_used, wave_used;
-    zalpha_reach(nsp, n_tile, tid, s_max, n_used, wave_used);
-    if (n_used <= 0) return;
-    const float pu = float(px.u), pv = float(px.v);
-    const int slot_off = slot_lane_offset(lane);
-    const bool slot_stores = slot_off >= 0;
-    const int slot_lane_base = wave * RCHUNK * SV + (slot_stores ? slot_off : 0);
-    const bool want_f = grad_features != nullptr;   // workgroup-uniform
+    const float* __restrict__ g_map;
+    float* __restrict__ grad_features;   // nullptr: no batch runs
+    float* mine;                         // s_B, from begin() the wave's rows of it: [slot][pixel] w of the open batch
+    int* bidx;                           // s_bidx, the wave's row of it: [slot] Gaussian index of the entry
+    int lane = 0;
+    bool want_f = false;   // grad_features != nullptr (workgroup-uniform)
+    float g[CP] = {};
+    float y_op[NBLK][16] = {};
+    int nb = 0;   // filled slots of the wave's open batch (wave-uniform)
 
+    __device__ __forceinline__ void load(size_t p) {
+        const int C = this->C;
+        if (g_map == nullptr) return;
+        if (this->rows_of_vec4(g_map)) {
+#pragma unroll
+            for (int c4 = 0; c4 < CP / 4; c4++) {
+                if (4 * c4 < C) {
+                    const Vec4<float> v4 = reinterpret_cast<const Vec4<float>*>(g_map + p * C)[c4];
+                    g[4 * c4 + 0] = v4.x; g[4 * c4 + 1] = v4.y; g[4 * c4 + 2] = v4.z; g[4 * c4 + 3] = v4.w;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < CP; c++)
+                if (c < C) g[c] = g_map[p * C + c];
+        }
+    }
     // The batch GEMM per block of 16 channels  D[c][j] = sum_k A[c][k] B[k][j]  with  A[c][k] = g[pixel k][channel c]
     // (constant over the walk) and B[k][j] = w of batch slot j at pixel k.  As in k_render_bwd_sh the contraction index
     // of MFMA step t, sub-index q (= lane >> 4) is pixel 16 q + t of the wave, so that lane 16 q + j finds its sixteen
     // B values (slot j, pixels 16 q .. 16 q + 15) contiguous in LDS:  y_op[blk][t] = g[pixel 16 q + t][16 blk + (lane & 15)]
-    float y_op[NBLK][16];
-    float* mine = s_B + wave * MB * BROW;
-    int nb = 0;   // filled slots of the wave's open batch (wave-uniform)
-#pragma unroll
-    for (int blk = 0; blk < NBLK; blk++) {
-#pragma unroll
-        for (int t = 0; t < 16; t++) y_op[blk][t] = 0.0f;
-    }
-    if (want_f) {
+    __device__ __forceinline__ void begin(int lane_, int wave) {
+        lane = lane_;
+        want_f = grad_features != nullptr;
+        mine += wave * MB * BROW;
+        bidx += wave * MB;
+        if (!want_f) return;
 #pragma unroll
         for (int blk = 0; blk < NBLK; blk++) {
             // the wave's batch rows as [pixel][17] for the transposition
@@ -2736,10 +2737,39 @@ __global__ __launch_bounds__(RB) void k_render_features_bwd(
             __builtin_amdgcn_wave_barrier();
         }
     }
+    __device__ __forceinline__ float c(float ga, const Vec4<float>&, int i) const {
+        float c = ga;
+        const Vec4<float>* f4 = reinterpret_cast<const Vec4<float>*>(this->s_feat + i * CP);
+#pragma unroll
+        for (int c4 = 0; c4 < CP / 4; c4++) {
+            const Vec4<float> f = f4[c4];
+            c = __builtin_fmaf(g[4 * c4 + 0], f.x, c);
+            c = __builtin_fmaf(g[4 * c4 + 1], f.y, c);
+            c = __builtin_fmaf(g[4 * c4 + 2], f.z, c);
+            c = __builtin_fmaf(g[4 * c4 + 3], f.w, c);
+        }
+        return c;
+    }
+    __device__ __forceinline__ float column0(float) const { return 0.0f; }
+    // column nb of the batch's B: this entry's w at the wave's 64 pixels (0 where it does not contribute)
+    __device__ __forceinline__ void visited(float aT, int g_index) {
+        if (!want_f) return;
+        mine[nb * BROW + lane] = aT;
+        if (lane == 0) bidx[nb] = g_index;
+        if (++nb == MB) {
+            mma_flush(MB);
+            nb = 0;
+        }
+    }
+    __device__ __forceinline__ void send(int, int, float) const {}
+    __device__ __forceinline__ void finish() {
+        if (nb > 0) mma_flush(nb);   // the partial batch
+    }
     // The GEMM of the open batch; its results are the wave's complete sums for (tile patch, entry) and go straight to
     // the global gradient rows
-    auto mma_flush = [&](int n_filled) {
+    __device__ __forceinline__ void mma_flush(int n_filled) {
         typedef float f32x4 __attribute__((ext_vector_type(4)));
+        const int C = this->C;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -2777,136 +2807,47 @@ __global__ __launch_bounds__(RB) void k_render_features_bwd(
         // consecutive lanes, consecutive words of a gradient row
         for (int k = lane; k < n_filled * CP; k += 64) {
             const int row = k / CP, c = k - row * CP;
-            if (c < C) global_add(grad_features + (size_t)s_bidx[wave * MB + row] * C + c, mine[row * OW + c]);
+            if (c < C) global_add(grad_features + (size_t)bidx[row] * C + c, mine[row * OW + c]);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-    };
-
-    float S = 0.0f;   // sum of alpha_j T_j c_j over the contributors behind the current entry
-    for (int chunk = (n_used - 1) / RCHUNK; chunk >= 0; chunk--) {
-        const int base = chunk * RCHUNK;
-        const int cnt = min(RCHUNK, n_used - base);
-        __syncthreads();   // previous chunk fully flushed
-        stage_chunk<float, 1>(packed, nullptr, sorted, s0 + base, cnt, tid, s_geom, nullptr, s_idx);
-        stage_features<CP>(features, C, sorted, s0 + base, cnt, tid, s_feat);
-        // (no barrier in between: thread t tests the record thread t staged)
-        build_touch_masks<float, RCHUNK>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
-        __syncthreads();
-        unsigned long long m = wave_uniform(s_mask[wave][0]);
-        unsigned long long hit = 0;   // the entries of this chunk whose slot the wave wrote
-        while (m) {
-            const int i = 63 - __builtin_clzll(m);
-            m &= ~(1ull << i);
-            const int k = base + i;
-            if (k >= wave_used) continue;   // wave-uniform: no pixel of the patch walked this far
-            const float* rec = s_geom + i * GS_PACKED_WIDTH;
-            const Vec4<float> g0 = *reinterpret_cast<const Vec4<float>*>(rec);       // u v r2 opacity
-            const Vec4<float> g1 = *reinterpret_cast<const Vec4<float>*>(rec + 4);   // a b c det
-            const ZalphaVisit v = zalpha_alpha(g0, g1, rec[8], pu, pv, k < nsp);
-            if (ballot(v.contrib) == 0) continue;   // every reaching lane skipped the entry
-            float w = 0.0f, aT = 0.0f;
-            if (v.contrib) {
-                float alpha = v.alpha;
-                if (alpha > Thr<float>::sat_gt()) alpha = Thr<float>::alpha_cap();   // min(0.9999, .)
-                const float r1ma = fast_rcp(1.0f - alpha);
-                float c = ga;
-                const Vec4<float>* f4 = reinterpret_cast<const Vec4<float>*>(s_feat + i * CP);
-#pragma unroll
-                for (int c4 = 0; c4 < CP / 4; c4++) {
-                    const Vec4<float> f = f4[c4];
-                    c = __builtin_fmaf(g[4 * c4 + 0], f.x, c);
-                    c = __builtin_fmaf(g[4 * c4 + 1], f.y, c);
-                    c = __builtin_fmaf(g[4 * c4 + 2], f.z, c);
-                    c = __builtin_fmaf(g[4 * c4 + 3], f.w, c);
-                }
-                T = T * r1ma;                        // T_k: the transmittance in front of the entry
-                aT = alpha * T;                      // w_k
-                const float dalpha = T * c - S * r1ma;
-                S = __builtin_fmaf(aT, c, S);
-                w = v.norm_prob * dalpha;
-            }
-            float val[9];
-            const float du2 = v.du * v.du, dv2 = v.dv * v.dv, duv = v.du * v.dv;
-            val[0] = 0.0f; val[1] = 0.0f; val[2] = 0.0f;
-            val[3] = w; val[4] = w * v.du; val[5] = w * v.dv;
-            val[6] = (dv2 - g1.z * v.mh) * w;
-            val[7] = (g1.y * v.mh - duv) * w;
-            val[8] = (du2 - g1.x * v.mh) * w;
-            int slot_i = i * SV;
-            asm volatile("" : "+s"(slot_i));
-            reduce9_to_slot(val, slot_stores, s_acc, slot_lane_base + slot_i);
-            hit |= 1ull << i;
-            if (want_f) {
-                // column nb of the batch's B: this entry's w at the wave's 64 pixels (0 where it does not contribute)
-                mine[nb * BROW + lane] = aT;
-                if (lane == 0) s_bidx[wave * MB + nb] = s_idx[i];
-                if (++nb == MB) {
-                    mma_flush(MB);
-                    nb = 0;
-                }
-            }
-        }
-        if (lane == 0) s_hit[wave] = hit;
-        __syncthreads();
-        // the flush, as k_render_zalpha_bwd's.  Phase 1, thread = entry: add the slots of the waves that wrote it, in
-        // wave order, apply the per-splat factors and park the row in wave 0's slot of the same entry
-        if (tid < cnt) {
-            float a[SV];
-#pragma unroll
-            for (int j = 0; j < SV; j++) a[j] = 0;
-#pragma unroll
-            for (int w4 = 0; w4 < 4; w4++) {
-                if ((s_hit[w4] >> tid) & 1ull) {
-                    const float* sl = s_acc + (w4 * RCHUNK + tid) * SV;
-#pragma unroll
-                    for (int j = 0; j < SV; j++) a[j] += sl[j];
-                }
-            }
-            const float* rec = s_geom + tid * GS_PACKED_WIDTH;
-            const float ca = rec[4], cb = rec[5], cc = rec[6];
-            const float kf = -0.5f * rec[3] * rec[8];
-            const float Mu = a[4], Mv = a[5];
-            a[4] = -2.0f * kf * (cc * Mu - cb * Mv);
-            a[5] = -2.0f * kf * (ca * Mv - cb * Mu);
-            a[6] *= kf;
-            a[7] *= kf;
-            a[8] *= kf;
-            float* row = s_acc + tid * SV;
-#pragma unroll
-            for (int j = 0; j < SV; j++) row[j] = a[j];
-        }
-        __syncthreads();
-        // Phase 2, nine lanes = one row (seven rows per wave instruction); rows of zeros stay untouched, and so do
-        // the slab's colour columns
-        const int sub = lane / SV, col = lane - sub * SV;   // lane 63: idle
-        for (int r0 = wave * 7; r0 < cnt; r0 += 28) {
-            const int r = r0 + sub;
-            const bool in = lane < 63 && r < cnt;
-            const float v = in ? s_acc[r * SV + col] : 0.0f;
-            const unsigned long long nz = ballot(v != 0.0f);
-            const bool any = in && ((nz >> (sub * SV)) & 0x1ffull) != 0;
-            if (any && col >= 3) global_add(slab + (size_t)s_idx[r] * SV + col, v);
-        }
     }
-    if (nb > 0) mma_flush(nb);   // the partial batch
+};
+
+// LDS: 12 KB of records + CP KB of feature rows.
+template <int CP>
+__global__ __launch_bounds__(RB) void k_render_features_fwd(
+    const float* __restrict__ packed, const float* __restrict__ features, int C, const int* __restrict__ ranges,
+    const int* __restrict__ sorted, const int* __restrict__ nsp_in, int W, int H, int ntx, int tile0, int nt,
+    float* __restrict__ fmap, float* __restrict__ alpha_out, float* __restrict__ t_out) {
+    __shared__ alignas(16) float s_geom[MAP_FWD_CHUNK * GS_PACKED_WIDTH];
+    __shared__ alignas(16) float s_feat[MAP_FWD_CHUNK * CP];
+    __shared__ unsigned long long s_mask[4][MAP_FWD_CHUNK / 64];
+    __shared__ int s_max[4];
+    FeaturesFwd<CP> ch{{features, C, s_feat}, fmap};
+    render_map_fwd(ch, packed, ranges, sorted, nsp_in, W, H, ntx, tile0, nt, alpha_out, t_out, s_geom, s_mask, s_max);
 }
 
-// the instantiation at or above n_channels: 4, 8, 16, 32
+// LDS: 3 KB records + CP / 4 KB feature rows + 9 KB slots + 17 KB batches.
 template <int CP>
-static void launch_features_fwd(int nt, hipStream_t st, const float* packed, const float* features, int C,
-                                const int32_t* ranges, const int32_t* sorted, const int32_t* nsp, int W, int H, int ntx,
-                                int tile0, float* fmap, float* alpha, float* t_out) {
-    k_render_features_fwd<CP><<<render_grid(nt), RB, 0, st>>>(packed, features, C, ranges, sorted, nsp, W, H, ntx, tile0,
-                                                              nt, fmap, alpha, t_out);
-}
-template <int CP>
-static void launch_features_bwd(int nt, hipStream_t st, const float* packed, const float* features, int C,
-                                const int32_t* ranges, const int32_t* sorted, const int32_t* nsp, const float* t_in,
-                                const float* g_map, const float* g_alpha, int W, int H, int ntx, int tile0, float* slab,
-                                float* grad_features) {
-    k_render_features_bwd<CP><<<render_grid(nt), RB, 0, st>>>(packed, features, C, ranges, sorted, nsp, t_in, g_map,
-                                                              g_alpha, W, H, ntx, tile0, nt, slab, grad_features);
+__global__ __launch_bounds__(RB) void k_render_features_bwd(
+    const float* __restrict__ packed, const float* __restrict__ features, int C, const int* __restrict__ ranges,
+    const int* __restrict__ sorted, const int* __restrict__ nsp_in, const float* __restrict__ t_in,
+    const float* __restrict__ g_map, const float* __restrict__ g_alpha, int W, int H, int ntx, int tile0, int nt,
+    float* __restrict__ slab, float* __restrict__ grad_features) {
+    using Ch = FeaturesBwd<CP>;
+    __shared__ alignas(16) float s_geom[MAP_BWD_CHUNK * GS_PACKED_WIDTH];
+    __shared__ alignas(16) float s_feat[MAP_BWD_CHUNK * CP];
+    __shared__ int s_idx[MAP_BWD_CHUNK];
+    __shared__ float s_acc[4 * MAP_BWD_CHUNK * 9];            // [wave][entry][9]
+    __shared__ alignas(16) float s_B[4 * Ch::MB * Ch::BROW];  // [wave][slot][pixel]
+    __shared__ int s_bidx[4 * Ch::MB];                        // [wave][slot]
+    __shared__ int s_max[4];
+    __shared__ unsigned long long s_mask[4][1];
+    __shared__ unsigned long long s_hit[4][1];                // slots written by each wave
+    Ch ch{{features, C, s_feat}, g_map, grad_features, s_B, s_bidx};
+    render_map_bwd(ch, packed, ranges, sorted, nsp_in, t_in, g_alpha, W, H, ntx, tile0, nt, slab, s_geom, s_idx, s_acc,
+                   s_max, s_mask, s_hit);
 }
 
 }  // namespace gs
@@ -2935,6 +2876,13 @@ using namespace gs;
             gs::set_error("Unsupported number of SH coefficients: %d", n_sh);                      \
             return GS_EINVAL;                                                                      \
     }
+
+// the feature kernels' instantiation at or above n_channels (checked to be in 1..32): CP = 4, 8, 16, 32
+#define DISPATCH_CP(n_channels, CALL)                                                              \
+    if ((n_channels) <= 4) { constexpr int CP = 4; CALL; }                                         \
+    else if ((n_channels) <= 8) { constexpr int CP = 8; CALL; }                                    \
+    else if ((n_channels) <= 16) { constexpr int CP = 16; CALL; }                                  \
+    else { constexpr int CP = 32; CALL; }
 
 static int check_rows(int H, int row0, int row1) {
     const int nty = (H + 15) / 16;
@@ -3373,22 +3321,47 @@ int gs_render_depth(const void* packed, const void* xyz_camera_frame, const int3
     return check_launch("render_depth");
 }
 
+// What the four map entry points (`name`) check alike, in the order each always did, and the tiles of the call's rows.
+// The forward passes its three outputs (transmittance among them); the backward transmittance, an input there, and no
+// map_out / alpha_out.  n_channels: 1 for the depth map.  (packed, the channel source and sorted_gaussians are only
+// read where a list has entries: V == 0 passes anything)
+struct MapTiles {
+    int ntx, tile0, nt;   // nt == 0: nothing to launch
+};
+static int map_entry_tiles(const char* name, bool backward, int n_channels, const void* packed,
+                           const int32_t* tile_ranges, const int32_t* num_splats_per_pixel, const void* transmittance,
+                           const void* map_out, const void* alpha_out, int W, int H, int tile_row0, int tile_row1,
+                           MapTiles* t) {
+    GS_REQUIRE(W > 0 && H > 0, "image must be non-empty");
+    GS_REQUIRE(n_channels >= 1 && n_channels <= 32, "%s: n_channels must be in 1..32", name);
+    if (backward) {
+        GS_REQUIRE(tile_ranges != nullptr && num_splats_per_pixel != nullptr && transmittance != nullptr,
+                   "%s: tile_ranges, num_splats_per_pixel or transmittance is NULL", name);
+    } else {
+        GS_REQUIRE(tile_ranges != nullptr && num_splats_per_pixel != nullptr,
+                   "%s: tile_ranges or num_splats_per_pixel is NULL", name);
+        GS_REQUIRE(map_out != nullptr && alpha_out != nullptr && transmittance != nullptr, "%s: an output is NULL",
+                   name);
+    }
+    GS_REQUIRE(((uintptr_t)packed & 15) == 0, "%s: packed must be 16-byte aligned", name);
+    if (int e = check_rows(H, tile_row0, tile_row1)) return e;
+    t->ntx = (W + 15) / 16;
+    t->tile0 = tile_row0 * t->ntx;
+    t->nt = (tile_row1 - tile_row0) * t->ntx;
+    return GS_OK;
+}
+
 int gs_render_zalpha(const void* packed, const void* xyz_camera_frame, const int32_t* tile_ranges,
                      const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel, int W, int H,
                      int tile_row0, int tile_row1, void* depth, void* alpha, void* transmittance, void* stream) {
-    GS_REQUIRE(W > 0 && H > 0, "image must be non-empty");
-    GS_REQUIRE(tile_ranges != nullptr && num_splats_per_pixel != nullptr,
-               "render_zalpha: tile_ranges or num_splats_per_pixel is NULL");
-    GS_REQUIRE(depth != nullptr && alpha != nullptr && transmittance != nullptr, "render_zalpha: an output is NULL");
-    GS_REQUIRE(((uintptr_t)packed & 15) == 0, "render_zalpha: packed must be 16-byte aligned");
-    if (int e = check_rows(H, tile_row0, tile_row1)) return e;
-    const int ntx = (W + 15) / 16;
-    const int nt = (tile_row1 - tile_row0) * ntx;
-    if (nt == 0) return GS_OK;
-    // (packed, xyz_camera_frame and sorted_gaussians are only read where a list has entries: V == 0 passes anything)
-    k_render_zalpha_fwd<<<render_grid(nt), RB, 0, (hipStream_t)stream>>>(
+    MapTiles t;
+    if (int e = map_entry_tiles("render_zalpha", false, 1, packed, tile_ranges, num_splats_per_pixel, transmittance,
+                                depth, alpha, W, H, tile_row0, tile_row1, &t))
+        return e;
+    if (t.nt == 0) return GS_OK;
+    k_render_zalpha_fwd<<<render_grid(t.nt), RB, 0, (hipStream_t)stream>>>(
         (const float*)packed, (const float*)xyz_camera_frame, tile_ranges, sorted_gaussians, num_splats_per_pixel, W, H,
-        ntx, tile_row0 * ntx, nt, (float*)depth, (float*)alpha, (float*)transmittance);
+        t.ntx, t.tile0, t.nt, (float*)depth, (float*)alpha, (float*)transmittance);
     return check_launch("render_zalpha");
 }
 
@@ -3396,18 +3369,15 @@ int gs_render_zalpha_backward(const void* packed, const void* xyz_camera_frame, 
                               const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel,
                               const void* transmittance, const void* grad_depth, const void* grad_alpha, int W, int H,
                               int tile_row0, int tile_row1, void* grad_slab, void* grad_z, void* stream) {
-    GS_REQUIRE(W > 0 && H > 0, "image must be non-empty");
-    GS_REQUIRE(tile_ranges != nullptr && num_splats_per_pixel != nullptr && transmittance != nullptr,
-               "render_zalpha_backward: tile_ranges, num_splats_per_pixel or transmittance is NULL");
-    GS_REQUIRE(((uintptr_t)packed & 15) == 0, "render_zalpha_backward: packed must be 16-byte aligned");
-    if (int e = check_rows(H, tile_row0, tile_row1)) return e;
-    const int ntx = (W + 15) / 16;
-    const int nt = (tile_row1 - tile_row0) * ntx;
-    if (nt == 0 || (grad_depth == nullptr && grad_alpha == nullptr)) return GS_OK;   // nothing to add
+    MapTiles t;
+    if (int e = map_entry_tiles("render_zalpha_backward", true, 1, packed, tile_ranges, num_splats_per_pixel,
+                                transmittance, nullptr, nullptr, W, H, tile_row0, tile_row1, &t))
+        return e;
+    if (t.nt == 0 || (grad_depth == nullptr && grad_alpha == nullptr)) return GS_OK;   // nothing to add
     GS_REQUIRE(grad_slab != nullptr && grad_z != nullptr, "render_zalpha_backward: grad_slab or grad_z is NULL");
-    k_render_zalpha_bwd<<<render_grid(nt), RB, 0, (hipStream_t)stream>>>(
+    k_render_zalpha_bwd<<<render_grid(t.nt), RB, 0, (hipStream_t)stream>>>(
         (const float*)packed, (const float*)xyz_camera_frame, tile_ranges, sorted_gaussians, num_splats_per_pixel,
-        (const float*)transmittance, (const float*)grad_depth, (const float*)grad_alpha, W, H, ntx, tile_row0 * ntx, nt,
+        (const float*)transmittance, (const float*)grad_depth, (const float*)grad_alpha, W, H, t.ntx, t.tile0, t.nt,
         (float*)grad_slab, (float*)grad_z);
     return check_launch("render_zalpha_backward");
 }
@@ -3416,22 +3386,14 @@ int gs_render_features(const void* packed, const void* features, int n_channels,
                        const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel, int W, int H,
                        int tile_row0, int tile_row1, void* feature_map, void* alpha, void* transmittance,
                        void* stream) {
-    GS_REQUIRE(W > 0 && H > 0, "image must be non-empty");
-    GS_REQUIRE(n_channels >= 1 && n_channels <= 32, "render_features: n_channels must be in 1..32");
-    GS_REQUIRE(tile_ranges != nullptr && num_splats_per_pixel != nullptr,
-               "render_features: tile_ranges or num_splats_per_pixel is NULL");
-    GS_REQUIRE(feature_map != nullptr && alpha != nullptr && transmittance != nullptr,
-               "render_features: an output is NULL");
-    GS_REQUIRE(((uintptr_t)packed & 15) == 0, "render_features: packed must be 16-byte aligned");
-    if (int e = check_rows(H, tile_row0, tile_row1)) return e;
-    const int ntx = (W + 15) / 16;
-    const int nt = (tile_row1 - tile_row0) * ntx;
-    if (nt == 0) return GS_OK;
-    // (packed, features and sorted_gaussians are only read where a list has entries: V == 0 passes anything)
-    auto go = n_channels <= 4 ? launch_features_fwd<4> : n_channels <= 8 ? launch_features_fwd<8>
-              : n_channels <= 16 ? launch_features_fwd<16> : launch_features_fwd<32>;
-    go(nt, (hipStream_t)stream, (const float*)packed, (const float*)features, n_channels, tile_ranges, sorted_gaussians,
-       num_splats_per_pixel, W, H, ntx, tile_row0 * ntx, (float*)feature_map, (float*)alpha, (float*)transmittance);
+    MapTiles t;
+    if (int e = map_entry_tiles("render_features", false, n_channels, packed, tile_ranges, num_splats_per_pixel,
+                                transmittance, feature_map, alpha, W, H, tile_row0, tile_row1, &t))
+        return e;
+    if (t.nt == 0) return GS_OK;
+    DISPATCH_CP(n_channels, (k_render_features_fwd<CP><<<render_grid(t.nt), RB, 0, (hipStream_t)stream>>>(
+        (const float*)packed, (const float*)features, n_channels, tile_ranges, sorted_gaussians, num_splats_per_pixel,
+        W, H, t.ntx, t.tile0, t.nt, (float*)feature_map, (float*)alpha, (float*)transmittance)));
     return check_launch("render_features");
 }
 
@@ -3440,21 +3402,16 @@ int gs_render_features_backward(const void* packed, const void* features, int n_
                                 const void* transmittance, const void* grad_feature_map, const void* grad_alpha, int W,
                                 int H, int tile_row0, int tile_row1, void* grad_slab, void* grad_features,
                                 void* stream) {
-    GS_REQUIRE(W > 0 && H > 0, "image must be non-empty");
-    GS_REQUIRE(n_channels >= 1 && n_channels <= 32, "render_features_backward: n_channels must be in 1..32");
-    GS_REQUIRE(tile_ranges != nullptr && num_splats_per_pixel != nullptr && transmittance != nullptr,
-               "render_features_backward: tile_ranges, num_splats_per_pixel or transmittance is NULL");
-    GS_REQUIRE(((uintptr_t)packed & 15) == 0, "render_features_backward: packed must be 16-byte aligned");
-    if (int e = check_rows(H, tile_row0, tile_row1)) return e;
-    const int ntx = (W + 15) / 16;
-    const int nt = (tile_row1 - tile_row0) * ntx;
-    if (nt == 0 || (grad_feature_map == nullptr && grad_alpha == nullptr)) return GS_OK;   // nothing to add
+    MapTiles t;
+    if (int e = map_entry_tiles("render_features_backward", true, n_channels, packed, tile_ranges,
+                                num_splats_per_pixel, transmittance, nullptr, nullptr, W, H, tile_row0, tile_row1, &t))
+        return e;
+    if (t.nt == 0 || (grad_feature_map == nullptr && grad_alpha == nullptr)) return GS_OK;   // nothing to add
     GS_REQUIRE(grad_slab != nullptr, "render_features_backward: grad_slab is NULL");
-    auto go = n_channels <= 4 ? launch_features_bwd<4> : n_channels <= 8 ? launch_features_bwd<8>
-              : n_channels <= 16 ? launch_features_bwd<16> : launch_features_bwd<32>;
-    go(nt, (hipStream_t)stream, (const float*)packed, (const float*)features, n_channels, tile_ranges, sorted_gaussians,
-       num_splats_per_pixel, (const float*)transmittance, (const float*)grad_feature_map, (const float*)grad_alpha, W, H,
-       ntx, tile_row0 * ntx, (float*)grad_slab, (float*)grad_features);
+    DISPATCH_CP(n_channels, (k_render_features_bwd<CP><<<render_grid(t.nt), RB, 0, (hipStream_t)stream>>>(
+        (const float*)packed, (const float*)features, n_channels, tile_ranges, sorted_gaussians, num_splats_per_pixel,
+        (const float*)transmittance, (const float*)grad_feature_map, (const float*)grad_alpha, W, H, t.ntx, t.tile0,
+        t.nt, (float*)grad_slab, (float*)grad_features)));
     return check_launch("render_features_backward");
 }
 

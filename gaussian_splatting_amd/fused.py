@@ -1069,6 +1069,42 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
     return image, culling_mask, uv
 
 
+def _map_frame(name, gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+               use_sh_precompute, background_rgb, frame_options, adam_plan, features=None):
+    """What rasterize_rgbd and rasterize_features (`name`) do before their render node: refuse what they do not serve,
+    then preprocess the frame -- with z as one more output when there are no features.
+    -> (_Preprocess's outputs, sort_prefix, height, width)"""
+    g = gaussians
+    _require(not any(frame_options),
+             f"{name} serves whole single-GPU frames: tile_rows, return_aux, grad_sync, slab_sync and "
+             "frame_hook are not supported")
+    _require(adam_plan is None, f"{name} does not take the fused optimizer step (adam_plan)")
+    _require(g.sh is None or use_sh_precompute,
+             f"{name} needs the SH-precompute colour mode: per-pixel SH (use_sh_precompute=False) is not supported")
+    tensors = [t for t in (g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
+                           background_rgb) if t is not None]
+    _require(all(t.is_cuda and t.dtype == torch.float32 for t in tensors),
+             f"{name} needs float32 tensors on the GPU (no fp64, no CPU path)")
+    if features is not None:
+        _require(torch.is_tensor(features) and features.dim() == 2 and features.shape[0] == g.xyz.shape[0],
+                 f"{name}: features must be [N, C], one row per Gaussian")
+        _require(1 <= features.shape[1] <= 32,
+                 f"{name}: features must have 1 to 32 columns (callers with more split the channels)")
+        _require(features.dtype == torch.float32 and features.device == g.xyz.device,
+                 f"{name}: features must be float32 on the Gaussians' device (no fp64, no CPU path)")
+    validate(g, camera_T_world, camera, background_rgb)
+    sh = g.sh.contiguous() if g.sh is not None else None
+    sort_prefix = _hip.GS_SORT_PREFIX if SORT_PREFIX else 0
+    height, width = int(camera.height), int(camera.width)
+    # (no cut_box: the depth cut stays off -- a cut frame's flagged tiles keep their lists elsewhere)
+    out = _Preprocess.apply(
+        g.xyz.contiguous(), g.quaternion.contiguous(), g.scale.contiguous(), g.opacity.contiguous(),
+        g.rgb.contiguous(), sh, camera_T_world.contiguous(), camera.K.contiguous(), width, height, near_thresh,
+        far_thresh, cull_mask_padding, mh_dist, None, sort_prefix, background_rgb.contiguous(), None, None, True,
+        features is None)
+    return out, sort_prefix, height, width
+
+
 def rasterize_rgbd(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
                    use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None, slab_sync=None,
                    frame_hook=None, adam_plan=None):
@@ -1083,26 +1119,10 @@ def rasterize_rgbd(gaussians, camera_T_world, camera, near_thresh, far_thresh, c
     camera_T_world; the backward of depth and alpha is their true derivative (DESIGN.md "Depth and alpha maps").
     Whole single-GPU fp32 frames in the SH-precompute colour mode, Python orchestration, depth cut off: anything
     else raises RuntimeError (the trailing keyword arguments exist only to say so)."""
-    g = gaussians
-    _require(tile_rows is None and not (return_aux or grad_sync or slab_sync or frame_hook),
-             "rasterize_rgbd serves whole single-GPU frames: tile_rows, return_aux, grad_sync, slab_sync and "
-             "frame_hook are not supported")
-    _require(adam_plan is None, "rasterize_rgbd does not take the fused optimizer step (adam_plan)")
-    _require(g.sh is None or use_sh_precompute,
-             "rasterize_rgbd needs the SH-precompute colour mode: per-pixel SH (use_sh_precompute=False) is not supported")
-    tensors = [t for t in (g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
-                           background_rgb) if t is not None]
-    _require(all(t.is_cuda and t.dtype == torch.float32 for t in tensors),
-             "rasterize_rgbd needs float32 tensors on the GPU (no fp64, no CPU path)")
-    validate(g, camera_T_world, camera, background_rgb)
-    sh = g.sh.contiguous() if g.sh is not None else None
-    sort_prefix = _hip.GS_SORT_PREFIX if SORT_PREFIX else 0
-    height, width = int(camera.height), int(camera.width)
-    # (no cut_box: the depth cut stays off -- a cut frame's flagged tiles keep their lists elsewhere)
-    out = _Preprocess.apply(
-        g.xyz.contiguous(), g.quaternion.contiguous(), g.scale.contiguous(), g.opacity.contiguous(),
-        g.rgb.contiguous(), sh, camera_T_world.contiguous(), camera.K.contiguous(), width, height, near_thresh,
-        far_thresh, cull_mask_padding, mh_dist, None, sort_prefix, background_rgb.contiguous(), None, None, True, True)
+    out, sort_prefix, height, width = _map_frame(
+        "rasterize_rgbd", gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+        use_sh_precompute, background_rgb, (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook),
+        adam_plan)
     uv, conic, opacity, rgb, packed, xyz_cam, culling_mask, ranges, sorted_g, _vis_idx, keys = out[:11]
     image, depth, alpha = _RenderRGBD.apply(uv, conic, opacity, rgb, out[-1], packed, xyz_cam, ranges, sorted_g,
                                             background_rgb.contiguous(), height, width, keys, sort_prefix,
@@ -1126,33 +1146,10 @@ def rasterize_features(gaussians, features, camera_T_world, camera, near_thresh,
     pose term); their backward is the true derivative (DESIGN.md "Feature maps").  Whole single-GPU fp32 frames in the
     SH-precompute colour mode, Python orchestration, depth cut off: anything else raises RuntimeError (the trailing
     keyword arguments exist only to say so)."""
-    g = gaussians
-    _require(tile_rows is None and not (return_aux or grad_sync or slab_sync or frame_hook),
-             "rasterize_features serves whole single-GPU frames: tile_rows, return_aux, grad_sync, slab_sync and "
-             "frame_hook are not supported")
-    _require(adam_plan is None, "rasterize_features does not take the fused optimizer step (adam_plan)")
-    _require(g.sh is None or use_sh_precompute,
-             "rasterize_features needs the SH-precompute colour mode: per-pixel SH (use_sh_precompute=False) is not "
-             "supported")
-    tensors = [t for t in (g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
-                           background_rgb) if t is not None]
-    _require(all(t.is_cuda and t.dtype == torch.float32 for t in tensors),
-             "rasterize_features needs float32 tensors on the GPU (no fp64, no CPU path)")
-    _require(torch.is_tensor(features) and features.dim() == 2 and features.shape[0] == g.xyz.shape[0],
-             "rasterize_features: features must be [N, C], one row per Gaussian")
-    _require(1 <= features.shape[1] <= 32,
-             "rasterize_features: features must have 1 to 32 columns (callers with more split the channels)")
-    _require(features.dtype == torch.float32 and features.device == g.xyz.device,
-             "rasterize_features: features must be float32 on the Gaussians' device (no fp64, no CPU path)")
-    validate(g, camera_T_world, camera, background_rgb)
-    sh = g.sh.contiguous() if g.sh is not None else None
-    sort_prefix = _hip.GS_SORT_PREFIX if SORT_PREFIX else 0
-    height, width = int(camera.height), int(camera.width)
-    # (no cut_box: the depth cut stays off -- a cut frame's flagged tiles keep their lists elsewhere)
-    out = _Preprocess.apply(
-        g.xyz.contiguous(), g.quaternion.contiguous(), g.scale.contiguous(), g.opacity.contiguous(),
-        g.rgb.contiguous(), sh, camera_T_world.contiguous(), camera.K.contiguous(), width, height, near_thresh,
-        far_thresh, cull_mask_padding, mh_dist, None, sort_prefix, background_rgb.contiguous(), None, None, True)
+    out, sort_prefix, height, width = _map_frame(
+        "rasterize_features", gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+        use_sh_precompute, background_rgb, (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook),
+        adam_plan, features)
     uv, conic, opacity, rgb, packed, _xyz_cam, culling_mask, ranges, sorted_g, vis_idx, keys = out[:11]
     feat = _GatherRows.apply(features, vis_idx.long()).contiguous()
     image, feature_map, alpha = _RenderFeatures.apply(uv, conic, opacity, rgb, feat, packed, ranges, sorted_g,

@@ -7,7 +7,7 @@
 
 Per kernel: the function body (its label to .Lfunc_end), the .amdhsa_kernel descriptor block and the resource
 counts (.set <kernel>.num_vgpr ...), with only the
-function index of local labels (.LBB<n>_, .Lfunc_end<n>) normalised -- it shifts when a kernel is added to or
+function index of local labels (.LBB<n>_, .Lfunc_end<n>, and BB<n>_ in the loop comments) normalised -- it shifts when a kernel is added to or
 removed from the file.  Prints one line per kernel (instruction count and "identical", "only in ..." or the
 unified diff) and exits 1 if a kernel present in both files differs.
 
@@ -23,6 +23,7 @@ import subprocess
 import sys
 
 LABEL = re.compile(r"\.(LBB|Lfunc_end|Lfunc_begin)\d+")
+LOOP_NOTE = re.compile(r"\bBB\d+_")   # the same index in the "; in Loop: Header=BB<n>_<m>" comments
 
 
 def kernels(path):
@@ -35,7 +36,7 @@ def kernels(path):
         d0 = lines.index("\t.amdhsa_kernel " + name)
         d1 = lines.index("\t.end_amdhsa_kernel", d0)
         sets = [l for l in lines[d1:] if l.startswith("\t.set " + name + ".")]   # the resource counts
-        text = [LABEL.sub(r".\1N", l) for l in lines[start:end + 1] + lines[d0:d1 + 1] + sets]
+        text = [LOOP_NOTE.sub("BBN_", LABEL.sub(r".\1N", l)) for l in lines[start:end + 1] + lines[d0:d1 + 1] + sets]
         mnem = [l.split()[0] for l in lines[start:end] if l.startswith("\t") and not l.lstrip().startswith((".", ";"))]
         out[name] = (text, len(mnem), mnem)
     return out
