@@ -189,6 +189,44 @@ __device__ inline void pack_record(T u, T v, const T* conic3, T opa, const T* co
     p[11] = col3 ? T(GS_SH_0) * col3[2] : T(0);
 }
 
+// ---- antialiased opacity (GS_RASTER_ANTIALIASED; include/gsplat_hip.h "antialiased opacity") ----
+// The fp32 record dilates Sigma_2D by 0.25 px^2 and leaves the opacity alone; the factor comp = sqrt(det Sigma_2D /
+// det(Sigma_2D + 0.25 I)) keeps a splat's integrated weight independent of the dilation.  a, b, c, det_d are the
+// expressions of pack_record on the same bits (det_d == packed[7]); IEEE divide and square root; a NaN compares false
+// and gives comp = 0.  The forward (k_preprocess) and both backwards (k_preprocess_bwd, k_pose_bwd) call this one
+// function on the conic conic_of gives them.
+struct AaTerms {
+    float a0, c0, b, a, c, det_0, det_d, comp;
+};
+__device__ inline AaTerms aa_terms_of(const float* conic3) {
+    AaTerms t;
+    t.a0 = conic3[0];
+    t.c0 = conic3[2];
+    t.b = conic3[1] * 0.5;
+    t.a = conic3[0] + 0.25;
+    t.c = conic3[2] + 0.25;
+    t.det_d = t.a * t.c - t.b * t.b;
+    t.det_0 = t.a0 * t.c0 - t.b * t.b;
+    const float rho = t.det_0 / t.det_d;
+    t.comp = (t.det_0 > 0.0f && t.det_d > 0.0f) ? __builtin_sqrtf(rho) : 0.0f;
+    return t;
+}
+
+// The backward of opa_eff = y * comp folded into one row of the render-gradient slab, in registers: g = dL/d opa_eff
+// (slab column 3) becomes dL/dy, and the conic columns gain dL/d opa_eff * y * d comp / d conic -- the true derivative,
+// no epsilon (d comp / d rho = 0.5 / comp grows without bound as det_0 cancels; comp == 0 rows get nothing).
+__device__ inline void aa_fold_row(const AaTerms& t, float y, float& g_opa, float* gc3) {
+    const float g = g_opa;
+    g_opa = g * t.comp;
+    if (t.comp > 0.0f) {
+        const float g_rho = g * y * 0.5f / t.comp;
+        const float dd = t.det_d * t.det_d;
+        gc3[0] += g_rho * (t.c0 * t.det_d - t.det_0 * t.c) / dd;
+        gc3[1] += g_rho * t.b * (t.det_0 - t.det_d) / dd;   // conic1 = 2 b
+        gc3[2] += g_rho * (t.a0 * t.det_d - t.det_0 * t.a) / dd;
+    }
+}
+
 // projection_backward.cu:174-315
 template <typename T>
 __device__ inline void sigma_world_bwd_of(const T* q4, const T* s3, const T* G, T* g_q4, T* g_s3) {

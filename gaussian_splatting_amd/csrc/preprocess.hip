@@ -239,7 +239,9 @@ struct Band {
 // evaluated only for Gaussians whose candidate tile window (tile_culling.cu:138-156) reaches the
 // rank's rows; the others cannot appear in any of the rank's tile lists.  SH rows are then read
 // directly (no LDS staging: most rows are skipped).
-template <int N_SH, bool BAND>
+// AA (GS_RASTER_ANTIALIASED, whole frames): the record's opacity is sigmoid * comp (pg_math.h: aa_terms_of) and its cutoff
+// radius is taken for that opacity; everything else the kernel writes -- o.opacity, the sigmoid, included -- is unchanged.
+template <int N_SH, bool BAND, bool AA = false>
 __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))) void k_preprocess(
     const float* __restrict__ xyz, const float* __restrict__ quat, const float* __restrict__ scale,
     const float* __restrict__ opacity, const float* __restrict__ rgb, const float* __restrict__ sh,
@@ -420,7 +422,14 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))
 
     // packed render record, identical to k_pack
     float pk[GS_PACKED_WIDTH];
-    pack_record<float>(uv[0], uv[1], c3, opa, col, pk);
+    if constexpr (AA) {
+        static_assert(!BAND, "the antialiased mode serves whole frames");
+        const AaTerms t = aa_terms_of(c3);
+        pack_record<float>(uv[0], uv[1], c3, opa * t.comp, col, pk);
+        if (!(t.comp > 0.0f)) pk[2] = -1.0f;   // never contributes, whatever the dilated conic is
+    } else {
+        pack_record<float>(uv[0], uv[1], c3, opa, col, pk);
+    }
     float4* dst = reinterpret_cast<float4*>(o.packed + (size_t)v * GS_PACKED_WIDTH);
     dst[0] = make_float4(pk[0], pk[1], pk[2], pk[3]);
     dst[1] = make_float4(pk[4], pk[5], pk[6], pk[7]);
@@ -937,7 +946,9 @@ constexpr bool adam_rows_early(int n_sh) { return n_sh < 16; }
 // ADAM: quat / scale are not dereferenced (they would alias the parameters the step writes; the rows are read
 // through PreAdam, once, before anything is written), o carries only xyz, and every Gaussian of the launch --
 // culled ones too, with gradient 0 -- is stepped, as the dense gradient + k_adam would.
-template <int N_SH, bool GATHER = false, bool ADAM = false>
+// AA (GS_RASTER_ANTIALIASED): slab column 3 is dL/d(sigmoid * comp); the row is folded in registers (pg_math.h:
+// aa_fold_row) with comp recomputed from the S9, J6, W at hand -- the forward's functions on the forward's bits.
+template <int N_SH, bool GATHER = false, bool ADAM = false, bool AA = false>
 __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_preprocess_bwd(
     const float* __restrict__ xyz, const float* __restrict__ quat, const float* __restrict__ scale,
     const float* __restrict__ M, const float* __restrict__ K, const float* __restrict__ center,
@@ -945,6 +956,7 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))
     const float* __restrict__ g_slab, int v_base, int N, PreGrad o, GatherPlan gp = GatherPlan{},
     std::conditional_t<ADAM, PreAdam, NoAdam> ad = {}) {
     static_assert(!(ADAM && GATHER), "the fused optimizer step serves the single-GPU frame");
+    static_assert(!(AA && (ADAM || GATHER)), "the antialiased mode serves the plain single-GPU backward");
     constexpr int SHW = 3 * (N_SH - 1);
     __shared__ int s_gather[GATHER ? GS_MAX_RANKS : 1][PP_BLOCK / GS_WAVE];
     float gathered[9];
@@ -1017,7 +1029,7 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))
         }
         // opacity: d sigmoid = y (1 - y)
         const float y = opacity_act[v];
-        go = gsl[3] * (1.0f - y) * y;
+        if constexpr (!AA) go = gsl[3] * (1.0f - y) * y;
         // conic -> Sigma_world, J (projection_backward.cu:385-471)
         float q4[4], s3[3];
         if constexpr (ADAM) {
@@ -1034,7 +1046,13 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))
         const float fx = K[0], fy = K[4];
         J6[0] = fx / z; J6[1] = 0; J6[2] = -fx * c[0] / z2;
         J6[3] = 0; J6[4] = fy / z; J6[5] = -fy * c[1] / z2;
-        const float gc3[3] = {gsl[6], gsl[7], gsl[8]};
+        float gc3[3] = {gsl[6], gsl[7], gsl[8]};
+        if constexpr (AA) {
+            float c3[3], g_opa = gsl[3];
+            conic_of(J6, W, S9, c3);
+            aa_fold_row(aa_terms_of(c3), y, g_opa, gc3);
+            go = g_opa * (1.0f - y) * y;
+        }
         conic_bwd_of(J6, W, S9, gc3, gS9, gJ6);
         // Sigma_world -> quaternion, scale (projection_backward.cu:174-315)
         sigma_world_bwd_of(q4, s3, gS9, gq, gs);
@@ -1162,10 +1180,15 @@ inline int pose_blocks(int N) {
     return nb < POSE_MAX_BLOCKS ? nb : POSE_MAX_BLOCKS;
 }
 
+// AA (GS_RASTER_ANTIALIASED): the conic columns first gain the opacity column's share (aa_fold_row, as k_preprocess_bwd
+// folds the same row), which needs the sigmoid opacity_act[v]; the non-AA instantiation takes no such pointer.
+struct NoOpacity {};
+template <bool AA = false>
 __global__ __launch_bounds__(PP_BLOCK) void k_pose_bwd(
     const float* __restrict__ xyz, const float* __restrict__ quat, const float* __restrict__ scale,
     const float* __restrict__ M, const float* __restrict__ K, const int* __restrict__ rank,
-    const float* __restrict__ g_slab, int v_base, int N, float* __restrict__ rows) {
+    const float* __restrict__ g_slab, int v_base, int N, float* __restrict__ rows,
+    std::conditional_t<AA, const float*, NoOpacity> opacity_act = {}) {
     __shared__ float s_part[PP_BLOCK / GS_WAVE][12];
     float acc[12];
 #pragma unroll
@@ -1186,7 +1209,12 @@ __global__ __launch_bounds__(PP_BLOCK) void k_pose_bwd(
         const float z = c[2], z2 = c[2] * c[2];
         J6[0] = fx / z; J6[1] = 0; J6[2] = -fx * c[0] / z2;
         J6[3] = 0; J6[4] = fy / z; J6[5] = -fy * c[1] / z2;
-        const float gc3[3] = {gsl[6], gsl[7], gsl[8]};
+        float gc3[3] = {gsl[6], gsl[7], gsl[8]};
+        if constexpr (AA) {
+            float c3[3], g_opa = gsl[3];
+            conic_of(J6, W, S9, c3);
+            aa_fold_row(aa_terms_of(c3), opacity_act[v], g_opa, gc3);
+        }
         conic_bwd_pose_of(J6, W, S9, gc3, gJ6, gW9);
         cam_grad_of(c, fx, fy, gJ6, gsl + 4, gcam);
 #pragma unroll
@@ -1258,20 +1286,23 @@ static Frustum make_frustum(int W, int H, float near, float far, float padding) 
             return GS_EINVAL;                                                                      \
     }
 
-extern "C" {
+// GS_RASTER_CLASSIC / GS_RASTER_ANTIALIASED -> whether the antialiased instantiations run; anything else is refused
+#define GS_RASTER_MODE(raster_mode, aa)                                                                      \
+    GS_REQUIRE((raster_mode) == GS_RASTER_CLASSIC || (raster_mode) == GS_RASTER_ANTIALIASED,               \
+               "raster_mode must be GS_RASTER_CLASSIC or GS_RASTER_ANTIALIASED, got %d", (int)(raster_mode)); \
+    const bool aa = (raster_mode) == GS_RASTER_ANTIALIASED
 
-size_t gs_preprocess_workspace_ints(int N) { return (size_t)div_up(N > 0 ? N : 1, PP_BLOCK) * 2 + 8; }
-
-int gs_preprocess_forward_cut(const void* xyz, const void* quaternion, const void* scale,
-                              const void* opacity, const void* rgb, const void* sh, int n_sh,
-                              const void* camera_T_world, const void* K, int N, int W, int H,
-                              float near_thresh, float far_thresh, float cull_mask_padding,
-                              float mh_dist, int band_row0, int band_row1,
-                              int32_t* workspace, void* camera_center, int32_t* visible_count,
-                              uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
-                              void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
-                              void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
-                              int sample_stride, void* stream) {
+// gs_preprocess_forward_cut and gs_preprocess_forward_mode: aa selects the AA instantiation of k_preprocess, nothing else
+static int preprocess_forward_launch(const void* xyz, const void* quaternion, const void* scale,
+                                     const void* opacity, const void* rgb, const void* sh, int n_sh,
+                                     const void* camera_T_world, const void* K, int N, int W, int H,
+                                     float near_thresh, float far_thresh, float cull_mask_padding,
+                                     float mh_dist, int band_row0, int band_row1,
+                                     int32_t* workspace, void* camera_center, int32_t* visible_count,
+                                     uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
+                                     void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
+                                     void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
+                                     int sample_stride, bool aa, void* stream) {
     GS_REQUIRE((bin_records == nullptr) == (cut_workspace == nullptr) && (bin_records == nullptr) == (depth_hist == nullptr),
                "bin_records, cut_workspace and depth_hist go together");
     GS_REQUIRE(depth_hist == nullptr || sample_stride >= 1, "sample_stride must be gs_cut_sample_stride(N)");
@@ -1316,7 +1347,14 @@ int gs_preprocess_forward_cut(const void* xyz, const void* quaternion, const voi
     GS_REQUIRE(band_row0 >= 0 && band_row1 <= band.nty && band_row0 <= band_row1, "bad tile row band");
     const bool banded = !(band_row0 == 0 && band_row1 == band.nty);
     GS_REQUIRE(!(banded && bin_records != nullptr), "the depth-bucketed binning serves whole frames");
-    if (banded) {
+    GS_REQUIRE(!(banded && aa), "GS_RASTER_ANTIALIASED serves whole frames (no tile-row band)");
+    if (aa) {
+        DISPATCH_SH(n_sh, (k_preprocess<N_SH, false, true><<<nb, PP_BLOCK, 0, s>>>(
+                              (const float*)xyz, (const float*)quaternion, (const float*)scale,
+                              (const float*)opacity, (const float*)rgb, (const float*)sh,
+                              (const float*)camera_T_world, (const float*)K,
+                              (const float*)camera_center, N, fr, block_offsets, o, band)));
+    } else if (banded) {
         DISPATCH_SH(n_sh, (k_preprocess<N_SH, true><<<nb, PP_BLOCK, 0, s>>>(
                               (const float*)xyz, (const float*)quaternion, (const float*)scale,
                               (const float*)opacity, (const float*)rgb, (const float*)sh,
@@ -1330,6 +1368,43 @@ int gs_preprocess_forward_cut(const void* xyz, const void* quaternion, const voi
                               (const float*)camera_center, N, fr, block_offsets, o, band)));
     }
     return check_launch("preprocess_forward");
+}
+
+extern "C" {
+
+size_t gs_preprocess_workspace_ints(int N) { return (size_t)div_up(N > 0 ? N : 1, PP_BLOCK) * 2 + 8; }
+
+int gs_preprocess_forward_cut(const void* xyz, const void* quaternion, const void* scale,
+                              const void* opacity, const void* rgb, const void* sh, int n_sh,
+                              const void* camera_T_world, const void* K, int N, int W, int H,
+                              float near_thresh, float far_thresh, float cull_mask_padding,
+                              float mh_dist, int band_row0, int band_row1,
+                              int32_t* workspace, void* camera_center, int32_t* visible_count,
+                              uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
+                              void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
+                              void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
+                              int sample_stride, void* stream) {
+    return preprocess_forward_launch(xyz, quaternion, scale, opacity, rgb, sh, n_sh, camera_T_world, K, N, W, H, near_thresh,
+                                     far_thresh, cull_mask_padding, mh_dist, band_row0, band_row1, workspace, camera_center,
+                                     visible_count, culling_mask, rank, vis_idx, uv, xyz_camera_frame, conic, opacity_act,
+                                     rgb_render, packed, bin_records, cut_workspace, depth_hist, sample_stride, false, stream);
+}
+
+int gs_preprocess_forward_mode(const void* xyz, const void* quaternion, const void* scale,
+                               const void* opacity, const void* rgb, const void* sh, int n_sh,
+                               const void* camera_T_world, const void* K, int N, int W, int H,
+                               float near_thresh, float far_thresh, float cull_mask_padding,
+                               float mh_dist, int band_row0, int band_row1,
+                               int32_t* workspace, void* camera_center, int32_t* visible_count,
+                               uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
+                               void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
+                               void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
+                               int sample_stride, int raster_mode, void* stream) {
+    GS_RASTER_MODE(raster_mode, aa);
+    return preprocess_forward_launch(xyz, quaternion, scale, opacity, rgb, sh, n_sh, camera_T_world, K, N, W, H, near_thresh,
+                                     far_thresh, cull_mask_padding, mh_dist, band_row0, band_row1, workspace, camera_center,
+                                     visible_count, culling_mask, rank, vis_idx, uv, xyz_camera_frame, conic, opacity_act,
+                                     rgb_render, packed, bin_records, cut_workspace, depth_hist, sample_stride, aa, stream);
 }
 
 
@@ -1553,12 +1628,13 @@ int gs_preprocess_backward_adam(const void* xyz, int n_sh, const void* camera_T_
     return check_launch("preprocess_backward_adam");
 }
 
-int gs_preprocess_backward(const void* xyz, const void* quaternion, const void* scale, int n_sh,
-                           const void* camera_T_world, const void* K, const void* camera_center,
-                           const int32_t* rank, const void* opacity_act, const void* grad_slab,
-                           int v_base, int N, void* grad_xyz, void* grad_quaternion, void* grad_scale,
-                           void* grad_opacity_logit, void* grad_rgb_param, void* grad_sh,
-                           void* stream) {
+int gs_preprocess_backward_mode(const void* xyz, const void* quaternion, const void* scale, int n_sh,
+                                const void* camera_T_world, const void* K, const void* camera_center,
+                                const int32_t* rank, const void* opacity_act, const void* grad_slab,
+                                int v_base, int N, void* grad_xyz, void* grad_quaternion, void* grad_scale,
+                                void* grad_opacity_logit, void* grad_rgb_param, void* grad_sh,
+                                int raster_mode, void* stream) {
+    GS_RASTER_MODE(raster_mode, aa);
     GS_REQUIRE(n_sh == 1 || grad_sh != nullptr, "grad_sh must be given when n_sh > 1");
     hipStream_t s = (hipStream_t)stream;
     if (N <= 0) return GS_OK;
@@ -1569,32 +1645,65 @@ int gs_preprocess_backward(const void* xyz, const void* quaternion, const void* 
     o.opacity = (float*)grad_opacity_logit;
     o.rgb = (float*)grad_rgb_param;
     o.sh = (float*)grad_sh;
-    DISPATCH_SH(n_sh, (k_preprocess_bwd<N_SH><<<div_up(N, PP_BLOCK), PP_BLOCK, 0, s>>>(
-                          (const float*)xyz, (const float*)quaternion, (const float*)scale,
-                          (const float*)camera_T_world, (const float*)K,
-                          (const float*)camera_center, rank, (const float*)opacity_act,
-                          (const float*)grad_slab, v_base, N, o)));
+    if (aa) {
+        DISPATCH_SH(n_sh, (k_preprocess_bwd<N_SH, false, false, true><<<div_up(N, PP_BLOCK), PP_BLOCK, 0, s>>>(
+                              (const float*)xyz, (const float*)quaternion, (const float*)scale,
+                              (const float*)camera_T_world, (const float*)K,
+                              (const float*)camera_center, rank, (const float*)opacity_act,
+                              (const float*)grad_slab, v_base, N, o)));
+    } else {
+        DISPATCH_SH(n_sh, (k_preprocess_bwd<N_SH><<<div_up(N, PP_BLOCK), PP_BLOCK, 0, s>>>(
+                              (const float*)xyz, (const float*)quaternion, (const float*)scale,
+                              (const float*)camera_T_world, (const float*)K,
+                              (const float*)camera_center, rank, (const float*)opacity_act,
+                              (const float*)grad_slab, v_base, N, o)));
+    }
     return check_launch("preprocess_backward");
+}
+
+int gs_preprocess_backward(const void* xyz, const void* quaternion, const void* scale, int n_sh,
+                           const void* camera_T_world, const void* K, const void* camera_center,
+                           const int32_t* rank, const void* opacity_act, const void* grad_slab,
+                           int v_base, int N, void* grad_xyz, void* grad_quaternion, void* grad_scale,
+                           void* grad_opacity_logit, void* grad_rgb_param, void* grad_sh,
+                           void* stream) {
+    return gs_preprocess_backward_mode(xyz, quaternion, scale, n_sh, camera_T_world, K, camera_center, rank, opacity_act,
+                                       grad_slab, v_base, N, grad_xyz, grad_quaternion, grad_scale, grad_opacity_logit,
+                                       grad_rgb_param, grad_sh, GS_RASTER_CLASSIC, stream);
 }
 
 size_t gs_pose_workspace_floats(int N) { return (size_t)pose_blocks(N) * 12 + 4; }
 
-int gs_pose_backward(const void* xyz, const void* quaternion, const void* scale, const void* camera_T_world,
-                     const void* K, const int32_t* rank, const void* grad_slab, int v_base, int N, void* workspace,
-                     void* grad_camera_T_world, void* stream) {
+int gs_pose_backward_mode(const void* xyz, const void* quaternion, const void* scale, const void* camera_T_world,
+                          const void* K, const int32_t* rank, const void* opacity_act, const void* grad_slab, int v_base,
+                          int N, void* workspace, void* grad_camera_T_world, int raster_mode, void* stream) {
+    GS_RASTER_MODE(raster_mode, aa);
+    GS_REQUIRE(!aa || N <= 0 || opacity_act != nullptr, "pose_backward: GS_RASTER_ANTIALIASED needs opacity_act");
     GS_REQUIRE(grad_camera_T_world != nullptr, "pose_backward: grad_camera_T_world is NULL");
     GS_REQUIRE(N <= 0 || (workspace != nullptr && xyz != nullptr && quaternion != nullptr && scale != nullptr &&
                           rank != nullptr && grad_slab != nullptr && camera_T_world != nullptr && K != nullptr),
                "pose_backward: an input or the workspace is NULL");
     hipStream_t s = (hipStream_t)stream;
     const int nb = pose_blocks(N);
-    if (nb > 0)
-        k_pose_bwd<<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)quaternion, (const float*)scale,
-                                           (const float*)camera_T_world, (const float*)K, rank, (const float*)grad_slab,
-                                           v_base, N, (float*)workspace);
+    if (nb > 0 && aa)
+        k_pose_bwd<true><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)quaternion, (const float*)scale,
+                                                 (const float*)camera_T_world, (const float*)K, rank,
+                                                 (const float*)grad_slab, v_base, N, (float*)workspace,
+                                                 (const float*)opacity_act);
+    else if (nb > 0)
+        k_pose_bwd<false><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)quaternion, (const float*)scale,
+                                                  (const float*)camera_T_world, (const float*)K, rank,
+                                                  (const float*)grad_slab, v_base, N, (float*)workspace);
     // (N == 0: no rows, the sum writes the zeros)
     k_pose_sum<<<1, POSE_SUM_BLOCK, 0, s>>>((const float*)workspace, nb, (float*)grad_camera_T_world);
     return check_launch("pose_backward");
+}
+
+int gs_pose_backward(const void* xyz, const void* quaternion, const void* scale, const void* camera_T_world,
+                     const void* K, const int32_t* rank, const void* grad_slab, int v_base, int N, void* workspace,
+                     void* grad_camera_T_world, void* stream) {
+    return gs_pose_backward_mode(xyz, quaternion, scale, camera_T_world, K, rank, nullptr, grad_slab, v_base, N, workspace,
+                                 grad_camera_T_world, GS_RASTER_CLASSIC, stream);
 }
 
 }  // extern "C"

@@ -247,8 +247,9 @@ def want_depth_cut(hint_key, N, ntx, row0, row1, whole):
 
 def preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, width, height, near_thresh,
                        far_thresh, cull_mask_padding, mh_dist, tile_rows, sort_prefix, plan=None, plan_ints=0,
-                       defer=False, depth_cut=False):
-    """Per-Gaussian stage, binning and per-tile sort of one frame.  `plan`, if given, is called as
+                       defer=False, depth_cut=False, antialiased=False):
+    """Per-Gaussian stage, binning and per-tile sort of one frame.  antialiased: the packed record's opacity carries the
+    factor sqrt(det Sigma_2D / det(Sigma_2D + 0.25 I)) (gs_preprocess_forward_mode, GS_RASTER_ANTIALIASED; whole frames).  `plan`, if given, is called as
     plan(f) after the per-Gaussian stage is enqueued and fills the device record f.record
     (plan_ints int32) that rides on the frame's one host read (its host copy is left in f.host:
     multi-GPU, the split sizes of the gradient exchange); it may set f.subset = (index list, device
@@ -263,7 +264,8 @@ def preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world,
     T = ntx * nty
     row0, row1 = tile_rows if tile_rows is not None else (0, nty)
     f = SimpleNamespace(N=N, n_sh=n_sh, ntx=ntx, nty=nty, T=T, row0=row0, row1=row1, width=width, height=height,
-                        mh_dist=mh_dist, sort_prefix=sort_prefix)
+                        mh_dist=mh_dist, sort_prefix=sort_prefix, antialiased=bool(antialiased))
+    _require(not (antialiased and tile_rows is not None), "antialiased=True serves whole frames: tile_rows is not supported")
 
     stream = f.stream = _stream()
     f.hint_key = (dev.index, N, T, row0, row1)
@@ -283,10 +285,17 @@ def preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world,
     f.uv, f.xyz_cam, f.conic = uv.view(N, 2), xyz_cam.view(N, 3), conic.view(N, 3)
     f.opacity_act, f.rgb_render, f.packed = opa.view(N, 1), rgbr.view(N, 3), packed.view(N, 12)
     f.cut = None
-    _hip.call("gs_preprocess_forward", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), n_sh,
-              _p(camera_T_world), _p(K), N, width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, row0,
-              row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx), _p(f.uv),
-              _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), stream)
+    if antialiased:
+        _hip.call("gs_preprocess_forward_mode", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), n_sh,
+                  _p(camera_T_world), _p(K), N, width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, row0,
+                  row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx), _p(f.uv),
+                  _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), None, None, None, 0,
+                  _hip.GS_RASTER_ANTIALIASED, stream)
+    else:
+        _hip.call("gs_preprocess_forward", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), n_sh,
+                  _p(camera_T_world), _p(K), N, width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, row0,
+                  row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx), _p(f.uv),
+                  _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), stream)
 
     # the plan's record lives right behind (S, V) at the tail of ranges_buf: one host read gets both
     f.subset = (None, None)
@@ -366,11 +375,18 @@ def _preprocess_forward_cut(f, xyz, quaternion, scale, opacity, rgb, sh, camera_
     f.center, uv, xyz_cam, conic, opa, rgbr, packed, bin_rec = far.blocks()
     f.uv, f.xyz_cam, f.conic = uv.view(N, 2), xyz_cam.view(N, 3), conic.view(N, 3)
     f.opacity_act, f.rgb_render, f.packed = opa.view(N, 1), rgbr.view(N, 3), packed.view(N, 12)
-    _hip.call("gs_preprocess_forward_cut", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), f.n_sh,
-              _p(camera_T_world), _p(K), N, f.width, f.height, near_thresh, far_thresh, cull_mask_padding, f.mh_dist,
-              row0, row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx), _p(f.uv),
-              _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), _p(bin_rec), _p(cut_ws),
-              _p(_depth_hist(dev)), stride, stream)
+    if f.antialiased:
+        _hip.call("gs_preprocess_forward_mode", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), f.n_sh,
+                  _p(camera_T_world), _p(K), N, f.width, f.height, near_thresh, far_thresh, cull_mask_padding, f.mh_dist,
+                  row0, row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx),
+                  _p(f.uv), _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), _p(bin_rec),
+                  _p(cut_ws), _p(_depth_hist(dev)), stride, _hip.GS_RASTER_ANTIALIASED, stream)
+    else:
+        _hip.call("gs_preprocess_forward_cut", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), f.n_sh,
+                  _p(camera_T_world), _p(K), N, f.width, f.height, near_thresh, far_thresh, cull_mask_padding, f.mh_dist,
+                  row0, row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx),
+                  _p(f.uv), _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), _p(bin_rec),
+                  _p(cut_ws), _p(_depth_hist(dev)), stride, stream)
     _hip.call("gs_tile_count_cut", _p(bin_rec), N, _p(f.count), ntx, nty, f.mh_dist, row0, row1,
               _p(f.tile_counts), _p(cut_ws), _p(f.ranges_buf), _p(full_ranges), None, stream)
     f.subset = (None, None)
@@ -429,9 +445,10 @@ def preprocess_finish(f):
     return redone
 
 
-def preprocess_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_base=0, i0=0, i1=None):
+def preprocess_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_base=0, i0=0, i1=None, antialiased=False):
     """Dense parameter gradients of the Gaussians [i0, i1) from the render-gradient slab
-    (row of visible Gaussian v at slab[v - v_base]).  xyz, quaternion, scale: the full tensors."""
+    (row of visible Gaussian v at slab[v - v_base]).  xyz, quaternion, scale: the full tensors.
+    antialiased: the slab's opacity column is the gradient of the antialiased opacity (gs_preprocess_backward_mode)."""
     i1 = f.N if i1 is None else i1
     n = i1 - i0
     dev = xyz.device
@@ -440,14 +457,19 @@ def preprocess_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_ba
     grad_xyz, grad_q, grad_scale = gx.view(n, 3), gq.view(n, 4), gs.view(n, 3)
     grad_opacity, grad_rgb = go.view(n, 1), gc.view(n, 3)
     grad_sh = gsh.view(n, 3, f.n_sh - 1) if f.n_sh > 1 else None
-    if n > 0:
+    if n > 0 and antialiased:
+        _hip.call("gs_preprocess_backward_mode", _p(xyz[i0:i1]), _p(quaternion[i0:i1]), _p(scale[i0:i1]), f.n_sh,
+                  _p(camera_T_world), _p(K), _p(f.center), _p(f.rank[i0:i1]), _p(f.opacity_act), _p(slab), v_base, n,
+                  _p(grad_xyz), _p(grad_q), _p(grad_scale), _p(grad_opacity), _p(grad_rgb), _p(grad_sh),
+                  _hip.GS_RASTER_ANTIALIASED, _stream())
+    elif n > 0:
         _hip.call("gs_preprocess_backward", _p(xyz[i0:i1]), _p(quaternion[i0:i1]), _p(scale[i0:i1]), f.n_sh,
                   _p(camera_T_world), _p(K), _p(f.center), _p(f.rank[i0:i1]), _p(f.opacity_act), _p(slab), v_base, n,
                   _p(grad_xyz), _p(grad_q), _p(grad_scale), _p(grad_opacity), _p(grad_rgb), _p(grad_sh), _stream())
     return grad_xyz, grad_q, grad_scale, grad_opacity, grad_rgb, grad_sh
 
 
-def pose_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_base=0):
+def pose_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_base=0, antialiased=False):
     """The gradient of camera_T_world [4, 4] from the render-gradient slab of frame record f (gs_pose_backward): the
     rotation block and the translation as twelve free numbers, the last row 0.  Reads the quaternion and scale the
     forward saw: with the fused optimizer step it goes BEFORE preprocess_backward_adam on the same stream."""
@@ -455,8 +477,12 @@ def pose_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_base=0):
     # (two allocations: the gradient outlives the backward, the workspace must not live as long)
     grad = torch.empty(4, 4, dtype=torch.float32, device=xyz.device)
     ws = torch.empty(_hip.lib().gs_pose_workspace_floats(n), dtype=torch.float32, device=xyz.device)
-    _hip.call("gs_pose_backward", _p(xyz), _p(quaternion), _p(scale), _p(camera_T_world), _p(K), _p(f.rank), _p(slab),
-              v_base, n, _p(ws), _p(grad), _stream())
+    if antialiased:   # (the opacity column reaches the pose through the factor's conic terms)
+        _hip.call("gs_pose_backward_mode", _p(xyz), _p(quaternion), _p(scale), _p(camera_T_world), _p(K), _p(f.rank),
+                  _p(f.opacity_act), _p(slab), v_base, n, _p(ws), _p(grad), _hip.GS_RASTER_ANTIALIASED, _stream())
+    else:
+        _hip.call("gs_pose_backward", _p(xyz), _p(quaternion), _p(scale), _p(camera_T_world), _p(K), _p(f.rank),
+                  _p(slab), v_base, n, _p(ws), _p(grad), _stream())
     return grad
 
 
@@ -693,7 +719,7 @@ class _Preprocess(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, width, height, near_thresh,
                 far_thresh, cull_mask_padding, mh_dist, tile_rows, sort_prefix=0, background_rgb=None, cut_box=None,
-                adam_plan=None, pose_grad=False, z_out=False):
+                adam_plan=None, pose_grad=False, z_out=False, antialiased=False):
         # cut_box: a list; when the frame takes the depth cut its record (what _Render's two passes need) is left in it
         # adam_plan: train_ops.FusedRasterAdam's plan -> the backward steps quaternion, scale, opacity, rgb and sh
         # itself (preprocess_backward_adam) and returns a gradient for xyz only
@@ -701,6 +727,8 @@ class _Preprocess(torch.autograd.Function):
         # the pose a constant (multi-GPU frames: the sum would need an all-reduce; per-pixel SH: its rays depend on it)
         # z_out (rasterize_rgbd only): one more output BEHIND everything else, z = xyz_camera_frame[:V, 2] as a
         # differentiable tensor -- the handle through which the depth map's dL/dz comes back to this node
+        # antialiased: the record's opacity is sigmoid * comp; the opacity OUTPUT stays the sigmoid (the render reads the
+        # record), so the gradient that comes back for it is dL/d(sigmoid * comp) and the backward folds it
         ntx = (width + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
         nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
         row0, row1 = tile_rows if tile_rows is not None else (0, nty)
@@ -710,7 +738,7 @@ class _Preprocess(torch.autograd.Function):
         f = preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, width, height,
                                near_thresh, far_thresh, cull_mask_padding, mh_dist, tile_rows, sort_prefix,
                                defer=(not cut) and EARLY_RENDER and background_rgb is not None and sort_prefix != 0,
-                               depth_cut=cut)
+                               depth_cut=cut, antialiased=antialiased)
         if cut:
             cut_box.append(f.cut)
             pre = render_forward(f.packed, f.rgb_render, f.ranges, f.sorted_g, f.keys, background_rgb, height, width,
@@ -737,6 +765,7 @@ class _Preprocess(torch.autograd.Function):
         ctx.adam_plan = adam_plan
         ctx.pose_grad = pose_grad
         ctx.z_out = z_out
+        ctx.antialiased = bool(antialiased)
         ctx.f = SimpleNamespace(N=f.N, V=V, n_sh=f.n_sh, center=f.center, rank=f.rank, opacity_act=f.opacity_act,
                                 vis_idx=f.vis_idx[:V])
         uv_v, conic_v, opa_v, rgb_v = f.uv[:V], f.conic[:V], f.opacity_act[:V], f.rgb_render[:V]
@@ -758,7 +787,7 @@ class _Preprocess(torch.autograd.Function):
         # (before the fused optimizer step, which overwrites the quaternion and scale the pose terms read)
         g_pose = None
         if ctx.pose_grad and ctx.needs_input_grad[6]:
-            g_pose = pose_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab)
+            g_pose = pose_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab, antialiased=ctx.antialiased)
             if g_z is not None:
                 # the direct term of z = T[2, 0:3] . xyz + T[2, 3] (the slab's terms above already hold the depth map's
                 # uv / conic columns): plumbing on the visible rows, not a hot path
@@ -768,10 +797,11 @@ class _Preprocess(torch.autograd.Function):
         if ctx.adam_plan is not None:
             grads = (preprocess_backward_adam(xyz, camera_T_world, K, ctx.f, slab, ctx.adam_plan),) + (None,) * 5
         else:
-            grads = preprocess_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab)
+            grads = preprocess_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab,
+                                        antialiased=ctx.antialiased)
         if g_z is not None:
             _hip.call("gs_z_backward", _p(ctx.f.rank), _p(g_z), _p(camera_T_world), 0, ctx.f.N, _p(grads[0]), _stream())
-        return grads + (g_pose,) + (None,) * 14
+        return grads + (g_pose,) + (None,) * 15
 
 
 class _Render(torch.autograd.Function):
@@ -1010,14 +1040,21 @@ def supported(gaussians, camera_T_world, camera, use_sh_precompute):
 
 def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
               use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None, slab_sync=None,
-              frame_hook=None, adam_plan=None):
+              frame_hook=None, adam_plan=None, antialiased=False):
     """tile_rows=(row0, row1) restricts binning and rendering to those tile rows; slab_sync(flat) is
     called on the flat [9 V] render-gradient slab in the backward (grad_sync is the generic
     per-tensor form used by the reference-shaped path): the hooks gaussian_splatting_amd.sharded
     uses; all default to the single-GPU behaviour.  frame_hook(dict) receives the frame's tile ranges.
     adam_plan: only train_ops.FusedRasterAdam.rasterize passes it (the per-Gaussian backward then steps
-    quaternion, scale, opacity, rgb and sh itself): whole single-GPU frames without hooks, SH-precompute colour."""
+    quaternion, scale, opacity, rgb and sh itself): whole single-GPU frames without hooks, SH-precompute colour.
+    antialiased=True multiplies every splat's opacity by sqrt(det Sigma_2D / det(Sigma_2D + 0.25 I)), so that the 0.25 px^2
+    dilation of the fp32 record no longer adds light to splats smaller than a pixel, and differentiates through the
+    factor: whole single-GPU fp32 frames without hooks or adam_plan in the SH-precompute colour mode,
+    anything else raises RuntimeError before a kernel is enqueued."""
     hooks = return_aux or grad_sync or slab_sync or frame_hook
+    if antialiased:
+        _require_antialias_frame("rasterize", gaussians, camera_T_world, camera, use_sh_precompute, background_rgb,
+                                 (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), adam_plan)
     if adam_plan is not None:
         _require(not hooks and tile_rows is None, "the fused optimizer step serves whole single-GPU frames without hooks")
         _require(supported(gaussians, camera_T_world, camera, use_sh_precompute),
@@ -1045,6 +1082,10 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
             return nat.rasterize_adam(g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
                                       int(camera.width), int(camera.height), near_thresh, far_thresh, cull_mask_padding,
                                       mh_dist, background_rgb, adam_plan)
+        if antialiased:
+            return nat.rasterize(g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
+                                 int(camera.width), int(camera.height), near_thresh, far_thresh, cull_mask_padding,
+                                 mh_dist, background_rgb, row0, row1, True)
         return nat.rasterize(g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
                              int(camera.width), int(camera.height), near_thresh, far_thresh, cull_mask_padding, mh_dist,
                              background_rgb, row0, row1)
@@ -1055,7 +1096,7 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
         g.xyz.contiguous(), g.quaternion.contiguous(), g.scale.contiguous(), g.opacity.contiguous(),
         g.rgb.contiguous(), sh, camera_T_world.contiguous(), camera.K.contiguous(), int(camera.width),
         int(camera.height), near_thresh, far_thresh, cull_mask_padding, mh_dist, tile_rows, sort_prefix,
-        background_rgb.contiguous(), cut_box, adam_plan, not (grad_sync or slab_sync))
+        background_rgb.contiguous(), cut_box, adam_plan, not (grad_sync or slab_sync), False, bool(antialiased))
     uv, conic, opacity, rgb, packed, xyz_cam, culling_mask, ranges, sorted_g, vis_idx, keys = out[:11]
     if frame_hook is not None:   # multi-GPU cost-balanced bands: the band's tile ranges
         frame_hook(dict(ranges=ranges, ntx=(int(camera.width) + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX))
@@ -1069,8 +1110,25 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
     return image, culling_mask, uv
 
 
+def _require_antialias_frame(name, gaussians, camera_T_world, camera, use_sh_precompute, background_rgb, frame_options,
+                             adam_plan):
+    """what antialiased=True is served on, checked before anything is enqueued: each refusal names its reason"""
+    g = gaussians
+    _require(adam_plan is None, f"{name}(antialiased=True) does not take the fused optimizer step (adam_plan)")
+    _require(not any(frame_options),
+             f"{name}(antialiased=True) serves whole single-GPU frames: tile_rows, return_aux, grad_sync, slab_sync and "
+             "frame_hook are not supported")
+    _require(g.sh is None or use_sh_precompute,
+             f"{name}(antialiased=True) needs the SH-precompute colour mode: per-pixel SH (use_sh_precompute=False) is "
+             "not supported")
+    tensors = [t for t in (g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
+                           background_rgb) if t is not None]
+    _require(all(t.is_cuda and t.dtype == torch.float32 for t in tensors),
+             f"{name}(antialiased=True) needs float32 tensors on the GPU (no fp64, no CPU path)")
+
+
 def _map_frame(name, gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
-               use_sh_precompute, background_rgb, frame_options, adam_plan, features=None):
+               use_sh_precompute, background_rgb, frame_options, adam_plan, features=None, antialiased=False):
     """What rasterize_rgbd and rasterize_features (`name`) do before their render node: refuse what they do not serve,
     then preprocess the frame -- with z as one more output when there are no features.
     -> (_Preprocess's outputs, sort_prefix, height, width)"""
@@ -1101,13 +1159,13 @@ def _map_frame(name, gaussians, camera_T_world, camera, near_thresh, far_thresh,
         g.xyz.contiguous(), g.quaternion.contiguous(), g.scale.contiguous(), g.opacity.contiguous(),
         g.rgb.contiguous(), sh, camera_T_world.contiguous(), camera.K.contiguous(), width, height, near_thresh,
         far_thresh, cull_mask_padding, mh_dist, None, sort_prefix, background_rgb.contiguous(), None, None, True,
-        features is None)
+        features is None, bool(antialiased))
     return out, sort_prefix, height, width
 
 
 def rasterize_rgbd(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
                    use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None, slab_sync=None,
-                   frame_hook=None, adam_plan=None):
+                   frame_hook=None, adam_plan=None, antialiased=False):
     """rasterize() with a differentiable depth map and accumulated opacity:
 
         image, depth, alpha, culling_mask, uv = rasterize_rgbd(...)
@@ -1118,11 +1176,12 @@ def rasterize_rgbd(gaussians, camera_T_world, camera, near_thresh, far_thresh, c
     depth / alpha).  All three carry gradients to the Gaussians' parameters and, when it requires one, to
     camera_T_world; the backward of depth and alpha is their true derivative (DESIGN.md "Depth and alpha maps").
     Whole single-GPU fp32 frames in the SH-precompute colour mode, Python orchestration, depth cut off: anything
-    else raises RuntimeError (the trailing keyword arguments exist only to say so)."""
+    else raises RuntimeError (the trailing keyword arguments exist only to say so).  antialiased: as rasterize()'s --
+    the maps' weights then carry the antialiased opacity too."""
     out, sort_prefix, height, width = _map_frame(
         "rasterize_rgbd", gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
         use_sh_precompute, background_rgb, (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook),
-        adam_plan)
+        adam_plan, antialiased=antialiased)
     uv, conic, opacity, rgb, packed, xyz_cam, culling_mask, ranges, sorted_g, _vis_idx, keys = out[:11]
     image, depth, alpha = _RenderRGBD.apply(uv, conic, opacity, rgb, out[-1], packed, xyz_cam, ranges, sorted_g,
                                             background_rgb.contiguous(), height, width, keys, sort_prefix,
@@ -1132,7 +1191,7 @@ def rasterize_rgbd(gaussians, camera_T_world, camera, near_thresh, far_thresh, c
 
 def rasterize_features(gaussians, features, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
                        use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None,
-                       slab_sync=None, frame_hook=None, adam_plan=None):
+                       slab_sync=None, frame_hook=None, adam_plan=None, antialiased=False):
     """rasterize() with a map of caller-supplied per-Gaussian feature vectors and the accumulated opacity:
 
         image, feature_map, alpha, culling_mask, uv = rasterize_features(gaussians, features, ...)
@@ -1145,11 +1204,11 @@ def rasterize_features(gaussians, features, camera_T_world, camera, near_thresh,
     Gaussians' parameters and, when it requires one, to camera_T_world (through the slab; features have no direct
     pose term); their backward is the true derivative (DESIGN.md "Feature maps").  Whole single-GPU fp32 frames in the
     SH-precompute colour mode, Python orchestration, depth cut off: anything else raises RuntimeError (the trailing
-    keyword arguments exist only to say so)."""
+    keyword arguments exist only to say so).  antialiased: as rasterize()'s."""
     out, sort_prefix, height, width = _map_frame(
         "rasterize_features", gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
         use_sh_precompute, background_rgb, (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook),
-        adam_plan, features)
+        adam_plan, features, antialiased=antialiased)
     uv, conic, opacity, rgb, packed, _xyz_cam, culling_mask, ranges, sorted_g, vis_idx, keys = out[:11]
     feat = _GatherRows.apply(features, vis_idx.long()).contiguous()
     image, feature_map, alpha = _RenderFeatures.apply(uv, conic, opacity, rgb, feat, packed, ranges, sorted_g,

@@ -299,6 +299,60 @@ int gs_pose_backward(const void* xyz, const void* quaternion, const void* scale,
                      const void* K, const int32_t* rank, const void* grad_slab, int v_base, int N, void* workspace,
                      void* grad_camera_T_world, void* stream);
 
+/* ---- antialiased opacity (fp32, ABI 14; the 2D factor of Mip-Splatting, no reference counterpart) -----------
+ * The fp32 packed record dilates every projected covariance by 0.25 px^2 and leaves the opacity alone, so a splat
+ * smaller than a pixel deposits several times the light it holds.  GS_RASTER_ANTIALIASED multiplies the record's
+ * opacity by comp = sqrt(det Sigma_2D / det(Sigma_2D + 0.25 I)), which makes a splat's integrated weight independent of
+ * the dilation, and differentiates through the factor.  Arithmetic (fp32, no contraction, IEEE divide and square root;
+ * one definition, csrc/pg_math.h aa_terms_of / aa_fold_row), with conic = the per-Gaussian stage's conic output:
+ *     a0 = conic0, c0 = conic2, b = conic1 * 0.5, a = a0 + 0.25, c = c0 + 0.25
+ *     det_d = a c - b b   (the bits of packed[7])        det_0 = a0 c0 - b b        rho = det_0 / det_d
+ *     comp = (det_0 > 0 && det_d > 0) ? sqrt(rho) : 0    (a NaN compares false: 0)
+ *     opa_eff = opacity_act * comp
+ *   forward   packed[3] = opa_eff, packed[2] = the cutoff radius for opa_eff (-1 when comp == 0: the row never
+ *             contributes).  opacity_act (the sigmoid), uv, xyz_camera_frame, conic, rgb_render, bin_records, every other
+ *             packed column, the culling mask, rank and vis_idx keep the classic call's bits; the binning never reads the
+ *             opacity, so tile ranges and sorted lists do too.
+ *   backward  column 3 of a slab row is g = dL/d opa_eff.  With y = opacity_act the row is folded in registers where
+ *             the kernels load it (the slab in memory is not rewritten):
+ *                 slab3' = g comp                        (then d sigmoid: grad_opacity_logit = slab3' (1 - y) y)
+ *                 comp > 0:  g_rho = g y 0.5 / comp
+ *                     slab6 += g_rho (c0 det_d - det_0 c) / (det_d det_d)
+ *                     slab7 += g_rho b (det_0 - det_d)   / (det_d det_d)
+ *                     slab8 += g_rho (a0 det_d - det_0 a) / (det_d det_d)
+ *             comp recomputed from the parameters with the forward's functions.  The true derivative: no epsilon guards
+ *             0.5 / comp, which grows without bound for a needle whose det_0 cancels; a row with comp == 0 gets no conic
+ *             term and opacity gradient 0.
+ * gs_preprocess_forward_mode   the arguments of gs_preprocess_forward_cut + raster_mode; bin_records, cut_workspace and
+ *                              depth_hist all NULL = the form of gs_preprocess_forward.  Whole frames only with
+ *                              GS_RASTER_ANTIALIASED (band_row0 = 0, band_row1 = n_tile_rows).
+ * gs_preprocess_backward_mode  gs_preprocess_backward + raster_mode; slices [i0, i1) and v_base as there.
+ * gs_pose_backward_mode        gs_pose_backward + opacity_act (the full [V,1] array, indexed by v: the fold needs y; may
+ *                              be NULL with GS_RASTER_CLASSIC) + raster_mode.
+ * With GS_RASTER_CLASSIC each launches exactly the kernels of the entry it extends; any other raster_mode value returns
+ * GS_EINVAL.  The band, list, gathered and Adam forms of the per-Gaussian stage have no antialiased mode. */
+#define GS_RASTER_CLASSIC 0
+#define GS_RASTER_ANTIALIASED 1
+int gs_preprocess_forward_mode(const void* xyz, const void* quaternion, const void* scale,
+                               const void* opacity, const void* rgb, const void* sh, int n_sh,
+                               const void* camera_T_world, const void* K, int N, int W, int H,
+                               float near_thresh, float far_thresh, float cull_mask_padding,
+                               float mh_dist, int band_row0, int band_row1,
+                               int32_t* workspace, void* camera_center, int32_t* visible_count,
+                               uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
+                               void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
+                               void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
+                               int sample_stride, int raster_mode, void* stream);
+int gs_preprocess_backward_mode(const void* xyz, const void* quaternion, const void* scale, int n_sh,
+                                const void* camera_T_world, const void* K, const void* camera_center,
+                                const int32_t* rank, const void* opacity_act, const void* grad_slab,
+                                int v_base, int N, void* grad_xyz, void* grad_quaternion,
+                                void* grad_scale, void* grad_opacity_logit, void* grad_rgb_param,
+                                void* grad_sh, int raster_mode, void* stream);
+int gs_pose_backward_mode(const void* xyz, const void* quaternion, const void* scale, const void* camera_T_world,
+                          const void* K, const int32_t* rank, const void* opacity_act, const void* grad_slab, int v_base,
+                          int N, void* workspace, void* grad_camera_T_world, int raster_mode, void* stream);
+
 /* ---- tile renderer ---------------------------------------------------------------------------- */
 /* Packs what the render kernels read per splat into one 48-byte (fp32) record per visible Gaussian:
  *   packed[V][12] = (u, v, r2, opacity | a, b, c, det | 1/det, SH_0*col0, SH_0*col1, SH_0*col2)
