@@ -2850,6 +2850,152 @@ __global__ __launch_bounds__(RB) void k_render_features_bwd(
                    s_max, s_mask, s_hit);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// per-Gaussian contribution statistics (no reference counterpart), fp32, forward only
+// ---------------------------------------------------------------------------------------------------
+// The blending weights w_k = alpha_k T_k of the frame whose colour forward left num_splats_per_pixel, reduced over the
+// pixels per Gaussian instead of over the Gaussians per pixel: their sum, their largest and the number of pixels.  alpha,
+// the contribute decision and T are the depth kernel's (zalpha_alpha; w = alpha T, T = fma(-alpha, T, T)), so a weight
+// here has the bits of k_render_zalpha_fwd's.  The kernel has its OWN walk body (render_map_fwd keeps its ISA): front to
+// back with T in a register like the forward, but with the backward's exchange -- per visited entry the wave reduces over
+// its patch's pixels (lanes that do not contribute hold 0) and leaves the result in the wave's own LDS slot of the
+// entry, plain stores; s_hit marks the slots a wave wrote; after the chunk thread = staged entry combines the four
+// waves' slots in wave order and sends at most three global atomics to the Gaussian's row.
+//   count  popcount of the ballot of `contrib`: scalar, no lane traffic
+//   sum, max   four DPP steps inside the 16-lane rows (xor 1, xor 2, row_ror 4, row_ror 8: every lane holds its row's
+//          total), then rows -> wave for BOTH values with the two swaps of reduce9_to_slot: permlane16_swap(sum, max)
+//          pairs the rows -- the sums of row pairs (0,1), (2,3) land in rows 0, 2, the maxima in rows 1, 3 -- and
+//          permlane32_swap joins the halves.  Rows 0 / 2 add, rows 1 / 3 take the maximum (one select each): lane 0
+//          ends with the wave's sum ((r0 + r1) + (r2 + r3), a fixed order), lane 16 with its maximum.
+//   slot   three words per (wave, entry): sum | max | count.  Lanes 0, 16 and 32 store them with ONE ds_write_b32 (lane
+//          32 carries the count's bits).  A pitch of three words is odd: the flush's reads, thread t at word 3 t, are
+//          free of bank conflicts.
+// The maximum goes out as a signed integer atomic on the float's bits: the weights are positive (alpha >= 1/255, T > 0),
+// where the order of the bits is the order of the values, so the result does not depend on the order of the tiles.
+// RCHUNK entries are staged per step (GS_CONTRIB_CHUNK; gs_debug_contributions_chunk selects the other instantiation
+// for the measurement, scripts/contributions_cost.py).
+template <int CTRL>
+__device__ __forceinline__ unsigned dpp_lanes(unsigned x) {   // x of the lane the DPP control names (all of them in range)
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, false);
+}
+template <int CTRL>
+__device__ __forceinline__ float dpp_lanes(float x) { return __uint_as_float(dpp_lanes<CTRL>(__float_as_uint(x))); }
+// the maximum's bits where the lane's mask is set, the sum elsewhere: one select on a mask formed before the walk (with
+// `odd_row ? max : sum` the compiler puts each value into an exec-masked branch of its own)
+__device__ __forceinline__ float row_select(unsigned mask, unsigned max_bits, float sum) {
+    return __uint_as_float((max_bits & mask) | (__float_as_uint(sum) & ~mask));
+}
+constexpr int CONTRIB_SLOT = 3;   // words per (wave, entry) slot: sum | max | count
+
+template <int RCHUNK>
+__global__ __launch_bounds__(RB) void k_render_contrib(
+    const float* __restrict__ packed, const int* __restrict__ ranges, const int* __restrict__ sorted,
+    const int* __restrict__ nsp_in, const int* __restrict__ row_index, int W, int H, int ntx, int tile0, int nt,
+    float* __restrict__ weight_sum, int* __restrict__ weight_max_bits, int* __restrict__ pixel_count) {
+    constexpr int NW = RCHUNK / 64;
+    constexpr int SV = CONTRIB_SLOT;
+    __shared__ alignas(16) float s_geom[RCHUNK * GS_PACKED_WIDTH];
+    __shared__ int s_idx[RCHUNK];
+    __shared__ int s_slot[4 * RCHUNK * SV];          // [wave][entry][sum | max | count], the floats as their bits
+    __shared__ int s_max[4];
+    __shared__ unsigned long long s_mask[4][NW];
+    __shared__ unsigned long long s_hit[4][NW];      // slots written by each wave
+    const int t_local = tile_of_block(blockIdx.x, nt);
+    if (t_local >= nt) return;
+    const int tile = tile0 + t_local;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const PixelMap px = pixel_of_thread(tile % ntx, tile / ntx, tid);
+    const bool valid = px.u < W && px.v < H;
+    const int s0 = ranges[tile];
+    const int n_tile = ranges[tile + 1] - s0;
+    const int nsp = valid ? nsp_in[(size_t)px.v * W + px.u] : 0;
+    int n_used, wave_used;
+    zalpha_reach(nsp, n_tile, tid, s_max, n_used, wave_used);
+    if (n_used <= 0) return;
+    const float pu = float(px.u), pv = float(px.v);
+    const unsigned odd_mask = (lane & 16) != 0 ? ~0u : 0u;         // rows 1, 3 carry the maximum, rows 0, 2 the sum
+    const bool slot_stores = (lane & 15) == 0 && lane < 48;        // lanes 0, 16, 32: sum, max, count
+    const int slot_lane_base = wave * RCHUNK * SV + (lane >> 4);   // (lane 48: word 3 = the next entry's, never stored)
+    float T = 1.0f;
+    for (int base = 0; base < n_used; base += RCHUNK) {
+        const int cnt = min(RCHUNK, n_used - base);
+        if (base > 0) __syncthreads();   // the previous chunk is flushed
+        stage_chunk<float, 1>(packed, nullptr, sorted, s0 + base, cnt, tid, s_geom, nullptr, s_idx);
+        if (lane < NW) s_hit[wave][lane] = 0;   // (the wave's own words; a wave that stops early leaves them so)
+        // (no barrier in between: thread t tests the record thread t staged)
+        build_touch_masks<float, RCHUNK>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
+        __syncthreads();
+        for (int word = 0; word < NW && word * 64 < cnt; word++) {
+            if (base + word * 64 >= wave_used) break;   // wave-uniform: no pixel of the patch walked this far
+            unsigned long long m = wave_uniform(s_mask[wave][word]);
+            unsigned long long hit = 0;   // the entries of this word whose slot the wave wrote
+            while (m) {
+                const int b = __builtin_ctzll(m);
+                const int i = word * 64 + b;
+                m &= m - 1;
+                const int k = base + i;
+                if (k >= wave_used) break;
+                const float* rec = s_geom + i * GS_PACKED_WIDTH;
+                const Vec4<float> g0 = *reinterpret_cast<const Vec4<float>*>(rec);       // u v r2 opacity
+                const Vec4<float> g1 = *reinterpret_cast<const Vec4<float>*>(rec + 4);   // a b c det
+                const ZalphaVisit v = zalpha_alpha(g0, g1, rec[8], pu, pv, k < nsp);
+                const unsigned long long bal = ballot(v.contrib);
+                if (bal == 0) continue;   // every reaching lane skipped the entry
+                float w = 0.0f;
+                if (v.contrib) {
+                    w = v.alpha * T;
+                    T = __builtin_fmaf(-v.alpha, T, T);   // T (1 - alpha), one rounding
+                }
+                // rows: every lane ends with its row's sum and maximum.  The maximum is taken on the bits as unsigned
+                // integers (w >= 0: the same order; v_max_u32 takes the DPP operand directly and 0 is its identity, where
+                // v_max_f32 first canonicalises both operands)
+                float sum = w;
+                unsigned mxb = __float_as_uint(w);
+                sum += dpp_lanes<0xB1>(sum);  mxb = max(mxb, dpp_lanes<0xB1>(mxb));    // quad_perm [1,0,3,2]
+                sum += dpp_lanes<0x4E>(sum);  mxb = max(mxb, dpp_lanes<0x4E>(mxb));    // quad_perm [2,3,0,1]
+                sum += dpp_lanes<0x124>(sum); mxb = max(mxb, dpp_lanes<0x124>(mxb));   // row_ror:4
+                sum += dpp_lanes<0x128>(sum); mxb = max(mxb, dpp_lanes<0x128>(mxb));   // row_ror:8
+                // rows -> wave
+                float mx = __uint_as_float(mxb);
+                permlane16_swap(sum, mx);        // sum: rows (s0, m0, s2, m2); mx: rows (s1, m1, s3, m3)
+                float z = row_select(odd_mask, max(__float_as_uint(sum), __float_as_uint(mx)), sum + mx);
+                float z2 = z;
+                permlane32_swap(z, z2);          // z: rows 0, 1 twice; z2: rows 2, 3 twice
+                const float total = row_select(odd_mask, max(__float_as_uint(z), __float_as_uint(z2)), z + z2);
+                const int out = lane == 32 ? (int)__builtin_popcountll(bal) : __float_as_int(total);
+                int slot_i = i * SV;
+                asm volatile("" : "+s"(slot_i));
+                if (slot_stores) s_slot[slot_lane_base + slot_i] = out;
+                hit |= 1ull << b;
+            }
+            if (lane == 0) s_hit[wave][word] = hit;
+        }
+        __syncthreads();
+        // thread = staged entry: the waves' slots in wave order, then one atomic per output to the Gaussian's row
+        if (tid < cnt) {
+            float sum = 0.0f;
+            unsigned mxb = 0;   // (the bits of 0.0f)
+            int n = 0;
+#pragma unroll
+            for (int w4 = 0; w4 < 4; w4++) {
+                if ((s_hit[w4][tid >> 6] >> (tid & 63)) & 1ull) {
+                    const int* sl = s_slot + (w4 * RCHUNK + tid) * SV;
+                    sum += __int_as_float(sl[0]);
+                    mxb = max(mxb, (unsigned)sl[1]);
+                    n += sl[2];
+                }
+            }
+            if (n > 0) {
+                const int g = s_idx[tid];
+                const size_t r = row_index != nullptr ? (size_t)row_index[g] : (size_t)g;
+                if (weight_sum != nullptr) global_add(weight_sum + r, sum);
+                if (weight_max_bits != nullptr) atomicMax(weight_max_bits + r, (int)mxb);
+                if (pixel_count != nullptr) atomicAdd(pixel_count + r, n);
+            }
+        }
+    }
+}
+
 }  // namespace gs
 
 using namespace gs;
@@ -3413,6 +3559,45 @@ int gs_render_features_backward(const void* packed, const void* features, int n_
         (const float*)transmittance, (const float*)grad_feature_map, (const float*)grad_alpha, W, H, t.ntx, t.tile0,
         t.nt, (float*)grad_slab, (float*)grad_features)));
     return check_launch("render_features_backward");
+}
+
+// entries staged per chunk of k_render_contrib: 64 (the backward walks') or 256 (the forward walks').  Measured in
+// alternating blocks of one process (profiles/r13/contributions_cost.json): 64 is 9 % faster at workload B (short
+// lists: 6.3 KB of LDS and 49 VGPRs against 25.3 KB and 73) and within 0.5 % of 256 at D
+#ifndef GS_CONTRIB_CHUNK
+#define GS_CONTRIB_CHUNK 64
+#endif
+static std::atomic<int> g_contrib_chunk{GS_CONTRIB_CHUNK};
+
+int gs_debug_contributions_chunk(int chunk) {
+    const int before = g_contrib_chunk.load(std::memory_order_relaxed);
+    if (chunk == 0) return before;
+    GS_REQUIRE(chunk == 64 || chunk == 256, "gs_debug_contributions_chunk: 64, 256 or 0 (query)");
+    g_contrib_chunk.store(chunk, std::memory_order_relaxed);
+    return before;
+}
+
+int gs_render_contributions(const void* packed, const int32_t* tile_ranges, const int32_t* sorted_gaussians,
+                            const int32_t* num_splats_per_pixel, const int32_t* row_index, int W, int H,
+                            int tile_row0, int tile_row1, void* weight_sum, void* weight_max,
+                            int32_t* pixel_count, void* stream) {
+    GS_REQUIRE(W > 0 && H > 0, "image must be non-empty");
+    GS_REQUIRE(tile_ranges != nullptr && num_splats_per_pixel != nullptr,
+               "render_contributions: tile_ranges or num_splats_per_pixel is NULL");
+    GS_REQUIRE(((uintptr_t)packed & 15) == 0, "render_contributions: packed must be 16-byte aligned");
+    if (int e = check_rows(H, tile_row0, tile_row1)) return e;
+    const int ntx = (W + 15) / 16;
+    const int tile0 = tile_row0 * ntx, nt = (tile_row1 - tile_row0) * ntx;
+    if (nt == 0 || (weight_sum == nullptr && weight_max == nullptr && pixel_count == nullptr)) return GS_OK;
+    if (g_contrib_chunk.load(std::memory_order_relaxed) != 256)
+        k_render_contrib<64><<<render_grid(nt), RB, 0, (hipStream_t)stream>>>(
+            (const float*)packed, tile_ranges, sorted_gaussians, num_splats_per_pixel, row_index, W, H, ntx, tile0, nt,
+            (float*)weight_sum, (int*)weight_max, pixel_count);
+    else
+        k_render_contrib<256><<<render_grid(nt), RB, 0, (hipStream_t)stream>>>(
+            (const float*)packed, tile_ranges, sorted_gaussians, num_splats_per_pixel, row_index, W, H, ntx, tile0, nt,
+            (float*)weight_sum, (int*)weight_max, pixel_count);
+    return check_launch("render_contributions");
 }
 
 }  // extern "C"

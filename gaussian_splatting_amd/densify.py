@@ -258,3 +258,61 @@ class DensityController:
             self._swap(k, d, m, v)
         self.reset_grad_accum()
         return info
+
+    # ---- pruning (no reference counterpart) -------------------------------------------------------------------
+    @torch.no_grad()
+    def prune(self, keep):
+        """Deletes the Gaussians whose row of keep ([N] bool on the Gaussians' device) is False: the delete of
+        adaptive_density_control on its own, with the caller's decision.  One gs_densify_move with destinations only
+        (dst_self = the prefix-sum index of the kept rows, no clone, no split) moves every parameter tensor and its
+        Adam moments; the step counts are kept, the gradient accumulators reset, the optimizer groups re-keyed.  One
+        host read (the new count).  -> {"deleted", "n_before", "n_after"}"""
+        g = self.gaussians
+        dev = g.xyz.device
+        N0 = g.xyz.shape[0]
+        if not (torch.is_tensor(keep) and keep.dtype == torch.bool and tuple(keep.shape) == (N0,) and keep.device == dev):
+            raise RuntimeError(f"prune: keep must be a [{N0}] bool tensor on {dev}")
+        dst_pos = torch.cumsum(keep, 0, dtype=torch.int32) - 1
+        n_new = int(dst_pos[-1].item()) + 1 if N0 else 0   # the host read
+        info = self.last_info = dict(deleted=N0 - n_new, n_before=N0, n_after=n_new)
+        if n_new == N0:
+            return info
+        minus = torch.full((N0,), -1, dtype=torch.int32, device=dev)
+        dst_self = torch.where(keep, dst_pos, minus)
+        names = self._names()
+        src, dst, src_m, dst_m, src_v, dst_v = [], [], [], [], [], []
+        for k in names:
+            t = getattr(g, k).detach().contiguous()
+            st = self._state(k)
+            has = bool(st) and "exp_avg" in st
+            src.append(t)
+            dst.append(torch.empty((n_new,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev))
+            src_m.append(st["exp_avg"].contiguous() if has else None)
+            src_v.append(st["exp_avg_sq"].contiguous() if has else None)
+            dst_m.append(torch.empty_like(dst[-1]) if has else None)
+            dst_v.append(torch.empty_like(dst[-1]) if has else None)
+        n = len(names)
+        arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in ts])
+        widths = (ctypes.c_int32 * n)(*[int(math.prod(t.shape[1:])) for t in src])
+        kinds = (ctypes.c_int32 * n)(*[_KIND.get(k, 0) for k in names])
+        xyz_s, scale_s, quat_s = (src[names.index(k)] for k in ("xyz", "scale", "quaternion"))
+        no_samples = torch.zeros(1, 3, device=dev)   # (n_split == 0: never read)
+        _hip.call("gs_densify_move", n, arr(src), arr(dst), arr(src_m), arr(dst_m), arr(src_v), arr(dst_v), widths,
+                  kinds, N0, _p(dst_self), _p(minus), _p(minus), _p(minus), _p(xyz_s), _p(scale_s), _p(quat_s),
+                  _p(self.xyz_grad_accum), _p(self.grad_accum_count), _p(no_samples), 0, 0, n_new, 1.0,
+                  _hip.current_stream())
+        for k, d, m, v in zip(names, dst, dst_m, dst_v):
+            self._swap(k, d, m, v)
+        self.reset_grad_accum()
+        return info
+
+    def prune_by_contribution(self, stats, min_weight_max):
+        """prune() by RadSplat's criterion on a fused.ContributionStats swept over the training views: keeps the
+        Gaussians whose largest blending weight at any pixel reached min_weight_max.  With min_weight_max = 0 only the
+        Gaussians that contributed to no pixel of any view (pixel_count == 0) go."""
+        n = self.gaussians.xyz.shape[0]
+        if stats.weight_max.shape[0] != n or stats.pixel_count.shape[0] != n:
+            raise RuntimeError(f"prune_by_contribution: the statistics are of {stats.weight_max.shape[0]} Gaussians, the set "
+                               f"has {n} (sweep the views again after N changed)")
+        # (a positive threshold implies pixel_count > 0; at 0 the count alone decides)
+        return self.prune((stats.weight_max >= min_weight_max) & (stats.pixel_count > 0))

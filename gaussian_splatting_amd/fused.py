@@ -696,6 +696,16 @@ def features_backward(packed, feat, ranges, sorted_g, nsp, t_end, grad_map, grad
               _p(t_end), _p(gm), _p(ga), width, height, 0, nty, _p(slab), _p(grad_feat), _stream())
 
 
+def contributions_forward(packed, ranges, sorted_g, nsp, height, width, row_index=None, weight_sum=None,
+                          weight_max=None, pixel_count=None):
+    """adds the per-Gaussian contribution statistics of the frame whose colour forward left nsp to the given buffers
+    (gs_render_contributions): weight_sum / weight_max float32, pixel_count int32, rows named by row_index (int32 [V];
+    None: the visible index itself); a buffer that is None is skipped"""
+    nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
+    _hip.call("gs_render_contributions", _p(packed), _p(ranges), _p(sorted_g), _p(nsp), _p(row_index), width, height, 0,
+              nty, _p(weight_sum), _p(weight_max), _p(pixel_count), _stream())
+
+
 def _as_slab(g_uv, g_conic, g_opa, g_rgb, V, dev):
     """the four render gradients as one [V, 9] slab: the slab they are views of when they come
     straight from _Render.backward, a packed copy otherwise (outputs nobody consumed count as 0)"""
@@ -1128,9 +1138,10 @@ def _require_antialias_frame(name, gaussians, camera_T_world, camera, use_sh_pre
 
 
 def _map_frame(name, gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
-               use_sh_precompute, background_rgb, frame_options, adam_plan, features=None, antialiased=False):
-    """What rasterize_rgbd and rasterize_features (`name`) do before their render node: refuse what they do not serve,
-    then preprocess the frame -- with z as one more output when there are no features.
+               use_sh_precompute, background_rgb, frame_options, adam_plan, features=None, antialiased=False, z_out=None):
+    """What rasterize_rgbd, rasterize_features and rasterize_contributions (`name`) do before their render node: refuse
+    what they do not serve, then preprocess the frame -- with z as one more output when there are no features (z_out:
+    says so itself).
     -> (_Preprocess's outputs, sort_prefix, height, width)"""
     g = gaussians
     _require(not any(frame_options),
@@ -1159,7 +1170,7 @@ def _map_frame(name, gaussians, camera_T_world, camera, near_thresh, far_thresh,
         g.xyz.contiguous(), g.quaternion.contiguous(), g.scale.contiguous(), g.opacity.contiguous(),
         g.rgb.contiguous(), sh, camera_T_world.contiguous(), camera.K.contiguous(), width, height, near_thresh,
         far_thresh, cull_mask_padding, mh_dist, None, sort_prefix, background_rgb.contiguous(), None, None, True,
-        features is None, bool(antialiased))
+        features is None if z_out is None else bool(z_out), bool(antialiased))
     return out, sort_prefix, height, width
 
 
@@ -1215,3 +1226,83 @@ def rasterize_features(gaussians, features, camera_T_world, camera, near_thresh,
                                                       background_rgb.contiguous(), height, width, keys, sort_prefix,
                                                       tuple(out[11:]))
     return image, feature_map, alpha, culling_mask, uv
+
+
+class ContributionStats:
+    """How much each of the N Gaussians contributed to the frames swept into the record, from the blending weights
+    w = alpha T of fused.rasterize_contributions:
+
+        weight_sum  [N] float32   sum of w over the pixels and frames
+        weight_max  [N] float32   largest w at any pixel of any frame
+        pixel_count [N] int32     pixels the Gaussian contributed to, summed over the frames
+        frames      int           frames accumulated
+
+    `touched` is pixel_count > 0: the Gaussian reached at least one pixel (a frame's culling_mask is only the frustum
+    test).  Passing the record back to rasterize_contributions adds the next view to it."""
+
+    def __init__(self, weight_sum, weight_max, pixel_count, frames=0):
+        self.weight_sum, self.weight_max, self.pixel_count, self.frames = weight_sum, weight_max, pixel_count, int(frames)
+
+    @classmethod
+    def zeros(cls, n, device):
+        return cls(torch.zeros(n, dtype=torch.float32, device=device), torch.zeros(n, dtype=torch.float32, device=device),
+                   torch.zeros(n, dtype=torch.int32, device=device), 0)
+
+    @property
+    def n(self):
+        return int(self.weight_sum.shape[0])
+
+    @property
+    def touched(self):
+        return self.pixel_count > 0
+
+    def check(self, n, device=None):
+        """raises unless the record is one of n Gaussians (on `device`) in the layout the kernel writes"""
+        for name, t, dtype in (("weight_sum", self.weight_sum, torch.float32), ("weight_max", self.weight_max, torch.float32),
+                               ("pixel_count", self.pixel_count, torch.int32)):
+            _require(torch.is_tensor(t) and t.dim() == 1 and t.dtype == dtype and t.is_contiguous(),
+                     f"ContributionStats.{name} must be a contiguous [N] {dtype} tensor")
+            _require(t.shape[0] == n,
+                     f"ContributionStats holds {t.shape[0]} Gaussians, the frame has {n}: statistics cannot be accumulated "
+                     "across a change of N (start a new record after densification or pruning)")
+            _require(device is None or t.device == device, f"ContributionStats.{name} is not on {device}")
+
+
+def rasterize_contributions(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+                            use_sh_precompute, background_rgb, stats=None, antialiased=False, tile_rows=None,
+                            return_aux=False, grad_sync=None, slab_sync=None, frame_hook=None, adam_plan=None):
+    """rasterize() without gradients, with the per-Gaussian contribution statistics of the frame:
+
+        image, stats, culling_mask = rasterize_contributions(gaussians, ...)                # a new record
+        image, stats, culling_mask = rasterize_contributions(gaussians, ..., stats=stats)   # the next view, added to it
+
+    image and culling_mask are those of rasterize() on the same inputs, bit for bit.  stats is a ContributionStats over
+    all N Gaussians (culled rows: untouched): for every pixel and every entry the colour forward walked and found
+    contributing, w = alpha T (the compositing weight, bit-equal to the one behind rasterize_rgbd's alpha) enters
+    weight_sum, weight_max and pixel_count of its Gaussian.  One forward-only kernel on the frame's own lists
+    (gs_render_contributions with row_index = the frame's visible indices): no [V] temporary, no scatter.  Runs under
+    torch.no_grad(); nothing returned carries a gradient.  Whole single-GPU fp32 frames in the SH-precompute colour
+    mode, Python orchestration, depth cut off: anything else raises RuntimeError before a kernel is enqueued (the
+    trailing keyword arguments exist only to say so).  A stats of another N raises too.  antialiased: as rasterize()'s."""
+    with torch.no_grad():
+        n = int(gaussians.xyz.shape[0])
+        if stats is not None:
+            _require(isinstance(stats, ContributionStats), "rasterize_contributions: stats must be a ContributionStats")
+            stats.check(n)
+        out, sort_prefix, height, width = _map_frame(
+            "rasterize_contributions", gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding,
+            mh_dist, use_sh_precompute, background_rgb,
+            (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), adam_plan, antialiased=antialiased,
+            z_out=False)
+        if stats is None:
+            stats = ContributionStats.zeros(n, gaussians.xyz.device)
+        else:
+            stats.check(n, gaussians.xyz.device)
+        _uv, _conic, _opacity, rgb, packed, _xyz_cam, culling_mask, ranges, sorted_g, vis_idx, keys = out[:11]
+        image, nsp, _fw, _cost, _seg = out[11:] if len(out) > 11 else render_forward(
+            packed, rgb, ranges, sorted_g, keys, background_rgb.contiguous(), height, width, None, sort_prefix)
+        if vis_idx.shape[0] > 0:   # (nothing visible: nothing to add, and empty tensors have no address)
+            contributions_forward(packed, ranges, sorted_g, nsp, height, width, vis_idx, stats.weight_sum,
+                                  stats.weight_max, stats.pixel_count)
+        stats.frames += 1
+        return image.detach(), stats, culling_mask

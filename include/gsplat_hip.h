@@ -573,6 +573,36 @@ int gs_render_features_backward(const void* packed, const void* features, int n_
                                 int H, int tile_row0, int tile_row1, void* grad_slab, void* grad_features,
                                 void* stream);
 
+/* Per-Gaussian contribution statistics of a rendered frame (ABI 15; no reference counterpart), fp32, forward only:
+ * the blending weights of the frame reduced over the PIXELS per Gaussian.  Packed records, lists and
+ * num_splats_per_pixel as gs_render_zalpha takes them; nothing beyond num_splats_per_pixel is read, so the lists may
+ * be prefix-sorted.  For pixel p and the entries k < num_splats_per_pixel[p], alpha_k, the contribute decision and T_k
+ * are formed by the code of gs_render_zalpha, w_k = alpha_k T_k, then T = fma(-alpha, T, T): w_k has the bits of the
+ * depth kernel's weight.  For every contributing visit of Gaussian g = sorted_gaussians[k], with the row
+ * r = row_index ? row_index[g] : g:
+ *   weight_sum[r]  += w_k            float.  Added within a tile in a fixed order (lanes, then the tile's four 8 x 8
+ *                                    patches), one float atomic per (list entry, tile): a Gaussian inside one tile has
+ *                                    a reproducible sum, one in several tiles a sum in the order the tiles arrive
+ *   weight_max[r]   = max(., w_k)    float.  The weights are positive, so the maximum is taken as an integer atomic on
+ *                                    the bits: independent of any order, bit-reproducible.  The caller starts it at 0
+ *                                    (any non-negative float is a valid start; negative values are not)
+ *   pixel_count[r] += 1              int32, exact: the pixels the Gaussian contributes to
+ * All three are ACCUMULATED, so a caller sweeps many views into the same buffers; any of them may be NULL, which
+ * skips it (all three NULL: the arguments are checked, nothing is launched, GS_OK).  Rows of Gaussians no pixel uses
+ * are not touched, bit for bit.
+ *   row_index  NULL or int32[V]: the caller's row of each visible Gaussian (the frame's vis_idx), so that a sweep
+ *              accumulates straight into [N] arrays -- no [V] temporary, no scatter
+ * GS_EINVAL with a gs_last_error() text for an empty image, bad tile rows, NULL tile_ranges / num_splats_per_pixel or
+ * a packed pointer that is not 16-byte aligned.  Empty lists (V == 0) touch nothing. */
+int gs_render_contributions(const void* packed, const int32_t* tile_ranges, const int32_t* sorted_gaussians,
+                            const int32_t* num_splats_per_pixel, const int32_t* row_index, int W, int H,
+                            int tile_row0, int tile_row1, void* weight_sum, void* weight_max,
+                            int32_t* pixel_count, void* stream);
+/* Measurement aid (ABI 15; scripts/contributions_cost.py): the list entries gs_render_contributions stages per step
+ * from the next call on, 64 (the default, the backward walks' chunk) or 256 (the forward walks'); 0 only asks.
+ * -> the value before the call.  Both instantiations compute the same statistics. */
+int gs_debug_contributions_chunk(int chunk);
+
 /* Cost-balanced bands (multi-GPU; no reference counterpart): the band images of unequal bands are all-gathered as
  * equal chunks of chunk_rows = 16 x (tallest band) + 1 pixel rows, each starting at its rank's band; the last row of
  * a chunk carries the per-tile-row costs of that band (floats; 0 outside the band).
