@@ -6,10 +6,12 @@
 Two autograd nodes instead of six-plus-glue:
 
     _Preprocess   gs_preprocess_forward + tile binning + per-tile sort   (parameters -> uv, conic,
-                  opacity, colour; non-differentiable: packed records, tile lists, culling mask)
+                  opacity, colour)
     _Render       gs_render_tiles_prefix (_packed) / gs_render_tiles_backward_slab
 
-so `uv` is still an autograd intermediate between two nodes: `uv.retain_grad()` followed by
+Both get the frame record (_frame_record) as a non-tensor argument: the frame's options from the entry point and, after
+_Preprocess.forward, what is not differentiable (packed records, tile lists, culling mask, an early render).  Every entry
+point starts with the same prelude (_begin_frame: refuse, validate, make contiguous, _Preprocess).  So `uv` is still an autograd intermediate between two nodes: `uv.retain_grad()` followed by
 `uv.grad` gives the render-backward grad_uv exactly as the trainer expects (trainer.py:360,379).
 One small device->host read per frame (V and S, to size the outputs); the reference has ~25
 synchronisation points.  fp32, SH-precompute colour mode; anything else is routed
@@ -19,12 +21,12 @@ The four stages are plain functions (preprocess_forward, render_forward, render_
 preprocess_backward) that gaussian_splatting_amd.sharded composes differently for multi-GPU frames.
 
 rasterize_rgbd is the same frame with two more differentiable outputs, depth and accumulated opacity [H, W]
-(_RenderRGBD: gs_render_zalpha / gs_render_zalpha_backward next to the colour kernels, gs_z_backward behind the
-per-Gaussian backward).
+(_Render with the map policy _DepthMap: gs_render_zalpha / gs_render_zalpha_backward next to the colour kernels,
+gs_z_backward behind the per-Gaussian backward).
 
 rasterize_features composites caller-supplied per-Gaussian feature vectors [N, C <= 32] with the frame's weights into a
-differentiable [H, W, C] map next to the image and the accumulated opacity (_RenderFeatures: gs_render_features /
-gs_render_features_backward).
+differentiable [H, W, C] map next to the image and the accumulated opacity (_Render with the map policy _FeatureMap:
+gs_render_features / gs_render_features_backward).
 """
 import os
 from types import SimpleNamespace
@@ -221,6 +223,12 @@ class _Arena:
 # ---------------------------------------------------------------------------------------------------
 # stages
 # ---------------------------------------------------------------------------------------------------
+def _tile_grid(width, height):
+    """-> (n_tiles_x, n_tiles_y) of a width x height image"""
+    return ((width + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX,
+            (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX)
+
+
 def want_depth_cut(hint_key, N, ntx, row0, row1, whole):
     """the "auto" policy of DEPTH_CUT for one frame"""
     if DEPTH_CUT is False or not whole:
@@ -258,9 +266,7 @@ def preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world,
     dev = xyz.device
     N = xyz.shape[0]
     n_sh = 1 if sh is None else sh.shape[2] + 1
-    i32 = dict(dtype=torch.int32, device=dev)
-    ntx = (width + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
-    nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
+    ntx, nty = _tile_grid(width, height)
     T = ntx * nty
     row0, row1 = tile_rows if tile_rows is not None else (0, nty)
     f = SimpleNamespace(N=N, n_sh=n_sh, ntx=ntx, nty=nty, T=T, row0=row0, row1=row1, width=width, height=height,
@@ -306,20 +312,10 @@ def preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world,
     _hip.call("gs_tile_count", _p(f.uv), _p(f.conic), N, _p(f.count), _p(subset), _p(subset_n), ntx, nty,
               mh_dist, row0, row1, _p(f.tile_counts), _p(f.ranges_buf), None, stream)
 
-    def emit_sort(capacity):
-        sorted_buf = torch.empty(capacity, **i32)
-        keys = torch.empty(capacity, dtype=torch.int64, device=dev)
-        if capacity > 0:
-            _hip.call("gs_tile_emit_sort", _p(f.uv), _p(f.xyz_cam), _p(f.conic), N, _p(f.count), _p(subset),
-                      _p(subset_n), ntx, nty, mh_dist, row0, row1, _p(f.ranges_buf), _p(f.tile_counts), _p(keys),
-                      capacity, _p(sorted_buf), sort_prefix, stream)
-        return sorted_buf, keys
-
     # The frame's only device->host read: (S, V) [+ the plan's record], to size the outputs.  If a
     # previous frame of the same shape is known, the emit + sort are enqueued first with a capacity
     # guessed from it, so the GPU keeps working while the host waits for the integers; the kernels
     # never write beyond the capacity and the step is repeated only if S turned out larger.
-    f.emit_sort = emit_sort
     guess = _capacity_hint.get(f.hint_key)
     f.host_buf = _pinned_ints(dev, 2 + plan_ints)
 
@@ -333,15 +329,28 @@ def preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world,
         f.ready = torch.cuda.Event()
         f.ready.record()
         f.capacity = guess
-        f.sorted_buf, f.keys_buf = emit_sort(guess)
     else:
         read_back(False)
         f.capacity = int(f.host_buf[0])
-        f.sorted_buf, f.keys_buf = emit_sort(f.capacity)
+    f.sorted_buf, f.keys_buf = _emit_sort(f, f.capacity)
     f.deferred = defer
     if not defer:
         preprocess_finish(f)
     return f
+
+
+def _emit_sort(f, capacity):
+    """-> the sorted lists and keys of stage record f in buffers of `capacity` instances (gs_tile_emit_sort).  (A plain
+    function of f: a closure kept on f would tie the record to itself, and the frame's arenas to the cyclic collector.)"""
+    dev = f.uv.device
+    sorted_buf = torch.empty(capacity, dtype=torch.int32, device=dev)
+    keys = torch.empty(capacity, dtype=torch.int64, device=dev)
+    if capacity > 0:
+        subset, subset_n = f.subset
+        _hip.call("gs_tile_emit_sort", _p(f.uv), _p(f.xyz_cam), _p(f.conic), f.N, _p(f.count), _p(subset),
+                  _p(subset_n), f.ntx, f.nty, f.mh_dist, f.row0, f.row1, _p(f.ranges_buf), _p(f.tile_counts), _p(keys),
+                  capacity, _p(sorted_buf), f.sort_prefix, f.stream)
+    return sorted_buf, keys
 
 
 _DEPTH_HIST = {}
@@ -429,7 +438,7 @@ def preprocess_finish(f):
     c["S_min"] = S if c["S_min"] is None else min(c["S_min"], S)
     c["S_max"] = S if c["S_max"] is None else max(c["S_max"], S)
     if S > f.capacity:
-        f.sorted_buf, f.keys_buf = f.emit_sort(S)
+        f.sorted_buf, f.keys_buf = _emit_sort(f, S)
         f.capacity = S
         redone = True
         c["capacity_misses"] += 1
@@ -561,8 +570,7 @@ def render_forward(packed, rgb, ranges, sorted_g, keys, background_rgb, height, 
     hint render_backward hands back to the library.  segment state: the workspace for the depth-segmented
     backward (empty when segments are off; `segments` None = the module's policy), for render_backward."""
     dev = packed.device
-    ntx = (width + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
-    nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
+    ntx, nty = _tile_grid(width, height)
     row0, row1 = tile_rows if tile_rows is not None else (0, nty)
     # one allocation: image [H,W,3] | final weight [H,W] | splat count [H,W] (int32 view).  Rows outside
     # [row0, row1) are not written by the kernel: zero-fill only when sharded
@@ -581,12 +589,19 @@ def render_forward(packed, rgb, ranges, sorted_g, keys, background_rgb, height, 
         seg = torch.empty(_hip.lib().gs_render_segment_workspace_bytes(width, height, row0, row1) // 4,
                           dtype=torch.float32, device=dev)
     seg_p = _p(seg) if segments else None
+    if cut is None and not (sort_prefix and sorted_g.shape[0] > sort_prefix):
+        cost = _empty(dev, torch.int32)
+        _hip.call("gs_render_tiles_packed", _p(packed), _p(rgb), None, _p(ranges), _p(sorted_g), _p(background_rgb),
+                  width, height, 1, row0, row1, _p(nsp), _p(fw), _p(image), _hip.GS_F32, seg_p, stream)
+        return image, nsp, fw, cost, seg
+    # cut and prefix lists: a provisional render, whose tiles that ran out of list are flagged and rendered again
+    # from their complete lists -- one call, the host never looks at the flags
+    scratch = torch.empty(2 * ntx * nty, dtype=torch.int32, device=dev)
+    flags, cost = scratch[:ntx * nty], scratch[ntx * nty:]
     if cut is not None:
         # depth-cut lists (preprocess_forward(depth_cut=True)): kept prefixes first, flagged tiles repaired from
-        # their complete lists in the overflow buffers -- one call, the host never looks at the flags
+        # their complete lists in the overflow buffers
         assert not segments, "depth segments and the depth cut are not combined"
-        scratch = torch.empty(2 * ntx * nty, dtype=torch.int32, device=dev)
-        flags, cost = scratch[:ntx * nty], scratch[ntx * nty:]
         # (never empty: a frame without a visible Gaussian still hands the backward a non-null overflow list)
         okeys = torch.empty(max(cut.S_full, 1), dtype=torch.int64, device=dev)
         osorted = torch.empty(max(cut.S_full, 1), dtype=torch.int32, device=dev)
@@ -595,26 +610,15 @@ def render_forward(packed, rgb, ranges, sorted_g, keys, background_rgb, height, 
                   _p(okeys), _p(osorted), cut.S_full, _p(background_rgb), width, height, row0, row1,
                   _p(flags), _p(nsp), _p(fw), _p(image), _p(cost), None, stream)
         cut.flags, cut.overflow_sorted = flags, osorted
-        global last_tile_flags
-        last_tile_flags = flags
-        if len(_flag_log) < 512:
-            _flag_log.append(flags)
-        return image, nsp, fw, cost, seg
-    if sort_prefix and sorted_g.shape[0] > sort_prefix:
-        # provisional render from the ordered prefixes; tiles that ran out of prefix are flagged,
-        # sorted in full and rendered again -- one call, the host never looks at the flags
-        scratch = torch.empty(2 * ntx * nty, dtype=torch.int32, device=dev)
-        flags, cost = scratch[:ntx * nty], scratch[ntx * nty:]
+    else:
+        # the ordered prefixes; flagged tiles are sorted in full from `keys`
         _hip.call("gs_render_tiles_prefix", _p(packed), _p(rgb), _p(ranges), _p(sorted_g), _p(keys),
                   sorted_g.shape[0], _p(background_rgb), width, height, row0, row1, _p(flags),
                   _p(nsp), _p(fw), _p(image), _p(cost), seg_p, stream)
-        last_tile_flags = flags
-        if len(_flag_log) < 512:
-            _flag_log.append(flags)
-    else:
-        cost = _empty(dev, torch.int32)
-        _hip.call("gs_render_tiles_packed", _p(packed), _p(rgb), None, _p(ranges), _p(sorted_g), _p(background_rgb),
-                  width, height, 1, row0, row1, _p(nsp), _p(fw), _p(image), _hip.GS_F32, seg_p, stream)
+    global last_tile_flags
+    last_tile_flags = flags
+    if len(_flag_log) < 512:
+        _flag_log.append(flags)
     return image, nsp, fw, cost, seg
 
 
@@ -626,7 +630,7 @@ def render_backward(packed, rgb, ranges, sorted_g, background_rgb, nsp, fw, grad
     tile_cost: render_forward's fourth output (the tiles are then started longest-first).
     seg_state: render_forward's fifth output; non-empty -> one workgroup per (tile, depth segment).
     backward_mode: _hip.GS_BACKWARD_COMPAT / _EXACT, per call (ABI 5); None = the process default at the call"""
-    nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
+    nty = _tile_grid(width, height)[1]
     row0, row1 = tile_rows if tile_rows is not None else (0, nty)
     # (cleared by the call itself, in the launch that also orders the tiles: zero_slab_rows)
     rows = max(V, 1)
@@ -656,7 +660,7 @@ def render_backward(packed, rgb, ranges, sorted_g, background_rgb, nsp, fw, grad
 def zalpha_forward(packed, xyz_cam, ranges, sorted_g, nsp, height, width):
     """-> depth, alpha, T_end, each [H, W] (gs_render_zalpha): the differentiable depth and accumulated opacity of the
     frame whose colour forward left nsp; one allocation"""
-    nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
+    nty = _tile_grid(width, height)[1]
     buf = torch.empty(3, height, width, dtype=torch.float32, device=packed.device)
     _hip.call("gs_render_zalpha", _p(packed), _p(xyz_cam), _p(ranges), _p(sorted_g), _p(nsp), width, height, 0, nty,
               _p(buf[0]), _p(buf[1]), _p(buf[2]), _stream())
@@ -666,7 +670,7 @@ def zalpha_forward(packed, xyz_cam, ranges, sorted_g, nsp, height, width):
 def zalpha_backward(packed, xyz_cam, ranges, sorted_g, nsp, t_end, grad_depth, grad_alpha, height, width, slab, grad_z):
     """adds the depth / alpha maps' gradients to columns 3..8 of the (cleared or colour-filled) slab and to grad_z
     (gs_render_zalpha_backward); either grad may be None"""
-    nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
+    nty = _tile_grid(width, height)[1]
     gd = grad_depth.contiguous() if grad_depth is not None else None
     ga = grad_alpha.contiguous() if grad_alpha is not None else None
     _hip.call("gs_render_zalpha_backward", _p(packed), _p(xyz_cam), _p(ranges), _p(sorted_g), _p(nsp), _p(t_end),
@@ -676,7 +680,7 @@ def zalpha_backward(packed, xyz_cam, ranges, sorted_g, nsp, t_end, grad_depth, g
 def features_forward(packed, feat, ranges, sorted_g, nsp, height, width):
     """-> feature_map [H, W, C], alpha, T_end [H, W] (gs_render_features) for the visible Gaussians' feature rows
     feat [V, C] on the lists of the frame whose colour forward left nsp; one allocation"""
-    nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
+    nty = _tile_grid(width, height)[1]
     C, P = int(feat.shape[1]), height * width
     buf = torch.empty((C + 2) * P, dtype=torch.float32, device=packed.device)
     fmap, alpha, t_end = buf[:C * P].view(height, width, C), buf[C * P:(C + 1) * P].view(height, width), \
@@ -689,7 +693,7 @@ def features_forward(packed, feat, ranges, sorted_g, nsp, height, width):
 def features_backward(packed, feat, ranges, sorted_g, nsp, t_end, grad_map, grad_alpha, height, width, slab, grad_feat):
     """adds the feature / alpha maps' gradients to columns 3..8 of the (cleared or colour-filled) slab and, unless it
     is None, to grad_feat [V, C] (gs_render_features_backward); either map gradient may be None"""
-    nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
+    nty = _tile_grid(width, height)[1]
     gm = grad_map.contiguous() if grad_map is not None else None
     ga = grad_alpha.contiguous() if grad_alpha is not None else None
     _hip.call("gs_render_features_backward", _p(packed), _p(feat), int(feat.shape[1]), _p(ranges), _p(sorted_g), _p(nsp),
@@ -701,7 +705,7 @@ def contributions_forward(packed, ranges, sorted_g, nsp, height, width, row_inde
     """adds the per-Gaussian contribution statistics of the frame whose colour forward left nsp to the given buffers
     (gs_render_contributions): weight_sum / weight_max float32, pixel_count int32, rows named by row_index (int32 [V];
     None: the visible index itself); a buffer that is None is skipped"""
-    nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
+    nty = _tile_grid(width, height)[1]
     _hip.call("gs_render_contributions", _p(packed), _p(ranges), _p(sorted_g), _p(nsp), _p(row_index), width, height, 0,
               nty, _p(weight_sum), _p(weight_max), _p(pixel_count), _stream())
 
@@ -725,34 +729,52 @@ def _as_slab(g_uv, g_conic, g_opa, g_rgb, V, dev):
 # ---------------------------------------------------------------------------------------------------
 # autograd nodes
 # ---------------------------------------------------------------------------------------------------
+def _frame_record(width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, tile_rows=None, sort_prefix=0,
+                  background=None, pose_grad=False, adam_plan=None, antialiased=False, z_out=False, may_cut=False,
+                  slab_sync=None):
+    """What one frame's two nodes share and autograd does not differentiate: the frame's options, set here by the entry
+    point, and -- filled by _Preprocess.forward -- the stage record's tensors the render and the caller read.  Handed
+    to both nodes as a non-tensor argument.  The differentiable outputs are not kept on it (that would tie the record to
+    the graph), and what a backward reads still goes through its ctx.save_for_backward.
+    adam_plan: train_ops.FusedRasterAdam's plan -> the per-Gaussian backward steps quaternion, scale, opacity, rgb and
+    sh itself (preprocess_backward_adam) and returns a gradient for xyz only
+    pose_grad: the frame gives camera_T_world its gradient when it requires one (pose_backward); False keeps the pose a
+    constant (multi-GPU frames: the sum would need an all-reduce; per-pixel SH: its rays depend on it)
+    z_out (rasterize_rgbd only): _Preprocess has one more output, z = xyz_camera_frame[:V, 2] as a differentiable
+    tensor -- the handle through which the depth map's dL/dz comes back to that node
+    antialiased: the packed record's opacity is sigmoid * comp; the opacity OUTPUT stays the sigmoid (the render reads
+    the record), so the gradient that comes back for it is dL/d(sigmoid * comp) and the backward folds it
+    may_cut: the frame may take the depth cut (want_depth_cut decides); its record, what _Render's two passes need,
+    is then left in `cut`
+    slab_sync: see rasterize()"""
+    return SimpleNamespace(
+        width=width, height=height, near_thresh=near_thresh, far_thresh=far_thresh, cull_mask_padding=cull_mask_padding,
+        mh_dist=mh_dist, tile_rows=tile_rows, sort_prefix=sort_prefix, background=background, pose_grad=pose_grad,
+        adam_plan=adam_plan, antialiased=bool(antialiased), z_out=z_out, may_cut=may_cut, slab_sync=slab_sync,
+        # after _Preprocess.forward (xyz_cam and vis_idx: the V visible rows)
+        packed=None, xyz_cam=None, culling_mask=None, ranges=None, sorted_g=None, vis_idx=None, keys=None, cut=None,
+        rendered=None)   # (image, nsp, fw, cost, seg) when _Preprocess.forward already enqueued _Render's kernels
+
+
 class _Preprocess(torch.autograd.Function):
+    """parameters, pose, frame record -> uv, conic, opacity, rgb of the visible Gaussians (+ z when fr.z_out);
+    everything else the frame made is left on the record"""
+
     @staticmethod
-    def forward(ctx, xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, width, height, near_thresh,
-                far_thresh, cull_mask_padding, mh_dist, tile_rows, sort_prefix=0, background_rgb=None, cut_box=None,
-                adam_plan=None, pose_grad=False, z_out=False, antialiased=False):
-        # cut_box: a list; when the frame takes the depth cut its record (what _Render's two passes need) is left in it
-        # adam_plan: train_ops.FusedRasterAdam's plan -> the backward steps quaternion, scale, opacity, rgb and sh
-        # itself (preprocess_backward_adam) and returns a gradient for xyz only
-        # pose_grad: the frame gives camera_T_world its gradient when it requires one (pose_backward); False keeps
-        # the pose a constant (multi-GPU frames: the sum would need an all-reduce; per-pixel SH: its rays depend on it)
-        # z_out (rasterize_rgbd only): one more output BEHIND everything else, z = xyz_camera_frame[:V, 2] as a
-        # differentiable tensor -- the handle through which the depth map's dL/dz comes back to this node
-        # antialiased: the record's opacity is sigmoid * comp; the opacity OUTPUT stays the sigmoid (the render reads the
-        # record), so the gradient that comes back for it is dL/d(sigmoid * comp) and the backward folds it
-        ntx = (width + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
-        nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
-        row0, row1 = tile_rows if tile_rows is not None else (0, nty)
-        cut = (cut_box is not None and background_rgb is not None and sort_prefix != 0 and
+    def forward(ctx, xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, fr):
+        ntx, nty = _tile_grid(fr.width, fr.height)
+        row0, row1 = fr.tile_rows if fr.tile_rows is not None else (0, nty)
+        # (a frame that is rendered from prefix lists always has a background: every entry point passes one)
+        cut = (fr.may_cut and fr.sort_prefix != 0 and
                want_depth_cut((xyz.device.index, xyz.shape[0], ntx * nty, row0, row1), xyz.shape[0], ntx, row0, row1,
-                              tile_rows is None))
-        f = preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, width, height,
-                               near_thresh, far_thresh, cull_mask_padding, mh_dist, tile_rows, sort_prefix,
-                               defer=(not cut) and EARLY_RENDER and background_rgb is not None and sort_prefix != 0,
-                               depth_cut=cut, antialiased=antialiased)
+                              fr.tile_rows is None))
+        f = preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, fr.width, fr.height,
+                               fr.near_thresh, fr.far_thresh, fr.cull_mask_padding, fr.mh_dist, fr.tile_rows,
+                               fr.sort_prefix, defer=(not cut) and EARLY_RENDER and fr.sort_prefix != 0, depth_cut=cut,
+                               antialiased=fr.antialiased)
         if cut:
-            cut_box.append(f.cut)
-            pre = render_forward(f.packed, f.rgb_render, f.ranges, f.sorted_g, f.keys, background_rgb, height, width,
-                                 tile_rows, sort_prefix, segments=False, cut=f.cut)
+            fr.rendered = render_forward(f.packed, f.rgb_render, f.ranges, f.sorted_g, f.keys, fr.background, fr.height,
+                                         fr.width, fr.tile_rows, fr.sort_prefix, segments=False, cut=f.cut)
         elif f.deferred:
             # the render (the _Render node's forward) is enqueued on the speculative tile lists before
             # the host waits for the frame's counts, so a short frame leaves no bubble on the GPU;
@@ -760,161 +782,135 @@ class _Preprocess(torch.autograd.Function):
             def render(exact_count):
                 seg = segments_for(f.hint_key, f.sorted_buf.shape[0] if not exact_count else f.S, exact_count,
                                    (f.row1 - f.row0) * f.ntx)
-                return render_forward(f.packed, f.rgb_render, f.ranges, f.sorted_buf, f.keys_buf, background_rgb,
-                                      height, width, tile_rows, sort_prefix, segments=seg)
+                return render_forward(f.packed, f.rgb_render, f.ranges, f.sorted_buf, f.keys_buf, fr.background,
+                                      fr.height, fr.width, fr.tile_rows, fr.sort_prefix, segments=seg)
 
             # (only gs_render_tiles_prefix takes the capacity and skips segments beyond it)
-            pre = render(False) if (f.speculative and f.capacity > sort_prefix) else None
+            pre = render(False) if (f.speculative and f.capacity > fr.sort_prefix) else None
             if preprocess_finish(f) or pre is None:
                 pre = render(True)
-        else:
-            pre = ()
+            fr.rendered = pre
         V = f.V
+        fr.packed, fr.xyz_cam, fr.culling_mask, fr.ranges = f.packed, f.xyz_cam[:V], f.culling_mask, f.ranges
+        fr.sorted_g, fr.vis_idx, fr.keys, fr.cut = f.sorted_g, f.vis_idx[:V], f.keys, f.cut
         ctx.save_for_backward(xyz, quaternion, scale, camera_T_world, K)
-        ctx.set_materialize_grads(False)   # no zero tensors for the auxiliary outputs in backward
-        ctx.adam_plan = adam_plan
-        ctx.pose_grad = pose_grad
-        ctx.z_out = z_out
-        ctx.antialiased = bool(antialiased)
+        ctx.set_materialize_grads(False)   # no zero tensor for an output nobody consumed
+        ctx.fr = fr
         ctx.f = SimpleNamespace(N=f.N, V=V, n_sh=f.n_sh, center=f.center, rank=f.rank, opacity_act=f.opacity_act,
-                                vis_idx=f.vis_idx[:V])
-        uv_v, conic_v, opa_v, rgb_v = f.uv[:V], f.conic[:V], f.opacity_act[:V], f.rgb_render[:V]
-        aux = (f.packed, f.xyz_cam[:V], f.culling_mask, f.ranges, f.sorted_g, f.vis_idx[:V], f.keys) + tuple(pre)
-        ctx.mark_non_differentiable(*aux)
-        if z_out:
-            return (uv_v, conic_v, opa_v, rgb_v) + aux + (f.xyz_cam[:V, 2].contiguous(),)
-        return (uv_v, conic_v, opa_v, rgb_v) + aux
+                                vis_idx=fr.vis_idx)
+        out = (f.uv[:V], f.conic[:V], f.opacity_act[:V], f.rgb_render[:V])
+        return out + (f.xyz_cam[:V, 2].contiguous(),) if fr.z_out else out
 
     @staticmethod
-    def backward(ctx, g_uv, g_conic, g_opa, g_rgb, *unused):
+    def backward(ctx, g_uv, g_conic, g_opa, g_rgb, g_z=None):
         xyz, quaternion, scale, camera_T_world, K = ctx.saved_tensors
+        fr = ctx.fr
         slab = _as_slab(g_uv, g_conic, g_opa, g_rgb, ctx.f.V, xyz.device)
-        g_z = unused[-1].contiguous() if (ctx.z_out and unused[-1] is not None and ctx.f.V > 0) else None
+        g_z = g_z.contiguous() if (g_z is not None and ctx.f.V > 0) else None
         if _keep_slab:
             global _last_grad_z
             _note_slab(slab, ctx.f.V)
             _last_grad_z = g_z
         # (before the fused optimizer step, which overwrites the quaternion and scale the pose terms read)
         g_pose = None
-        if ctx.pose_grad and ctx.needs_input_grad[6]:
-            g_pose = pose_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab, antialiased=ctx.antialiased)
+        if fr.pose_grad and ctx.needs_input_grad[6]:
+            g_pose = pose_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab, antialiased=fr.antialiased)
             if g_z is not None:
                 # the direct term of z = T[2, 0:3] . xyz + T[2, 3] (the slab's terms above already hold the depth map's
                 # uv / conic columns): plumbing on the visible rows, not a hot path
                 gz64 = g_z.double()   # (float64 sums: V terms of mixed sign)
                 g_pose[2, :3] += (gz64 @ xyz.index_select(0, ctx.f.vis_idx.long()).double()).float()
                 g_pose[2, 3] += gz64.sum().float()
-        if ctx.adam_plan is not None:
-            grads = (preprocess_backward_adam(xyz, camera_T_world, K, ctx.f, slab, ctx.adam_plan),) + (None,) * 5
+        if fr.adam_plan is not None:
+            grads = (preprocess_backward_adam(xyz, camera_T_world, K, ctx.f, slab, fr.adam_plan),) + (None,) * 5
         else:
             grads = preprocess_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab,
-                                        antialiased=ctx.antialiased)
+                                        antialiased=fr.antialiased)
         if g_z is not None:
             _hip.call("gs_z_backward", _p(ctx.f.rank), _p(g_z), _p(camera_T_world), 0, ctx.f.N, _p(grads[0]), _stream())
-        return grads + (g_pose,) + (None,) * 15
+        return grads + (g_pose, None, None)   # (K, the record)
+
+
+class _DepthMap:
+    """_Render's map policy of rasterize_rgbd (DepthFwd / DepthBwd of csrc/render.hip): channel z [V] -> depth, alpha
+    [H, W] (gs_render_zalpha / gs_render_zalpha_backward); dL/dz is a tail behind the slab's rows, cleared with them"""
+    forward, backward = staticmethod(zalpha_forward), staticmethod(zalpha_backward)
+    # what the kernels read: the record's camera-frame positions; z is only the handle dL/dz goes back through
+    source = staticmethod(lambda fr, z: fr.xyz_cam)
+    tail = staticmethod(lambda V: max(V, 1))   # floats behind the slab's rows
+
+    @staticmethod
+    def channel_grad(xyz_cam, V, tail, grad_depth, wanted):
+        """-> (what the backward kernel adds dL/dz to, the gradient of z)"""
+        return tail, (tail[:V] if grad_depth is not None else None)   # (alpha alone leaves dL/dz None)
+
+
+class _FeatureMap:
+    """_Render's map policy of rasterize_features (FeaturesFwd / FeaturesBwd): channels feat [V, C], the visible
+    Gaussians' rows -> feature_map [H, W, C], alpha [H, W] (gs_render_features / gs_render_features_backward)"""
+    forward, backward = staticmethod(features_forward), staticmethod(features_backward)
+    source = staticmethod(lambda fr, feat: feat)
+    tail = staticmethod(lambda V: 0)
+
+    @staticmethod
+    def channel_grad(feat, V, tail, grad_map, wanted):
+        """-> (grad_features for the backward kernel, the gradient of feat): NULL unless feat requires a gradient and
+        feature_map has one"""
+        g_feat = torch.zeros_like(feat) if (grad_map is not None and wanted) else None
+        return g_feat, g_feat
 
 
 class _Render(torch.autograd.Function):
+    """uv, conic, opacity, rgb, the map policy's channels (None without one), the frame record, the policy -> image,
+    or (image, map, alpha) with a policy: its kernels run on the lists and the splat counts the colour forward left.
+    One backward for all outputs: the prologue clears the slab (and the policy's tail), the colour backward runs if
+    the image has a gradient, the policy's if its map or alpha has one, and _Preprocess gets the one slab plus the
+    channels' gradient.  An unused output costs no launch."""
+
     @staticmethod
-    def forward(ctx, uv, conic, opacity, rgb, packed, ranges, sorted_g, background_rgb, height, width, tile_rows,
-                slab_sync=None, keys=None, sort_prefix=0, rendered=None, cut=None):
-        # rendered: (image, nsp, fw, cost, seg) when _Preprocess.forward already enqueued this node's kernels
+    def forward(ctx, uv, conic, opacity, rgb, channels, fr, policy):
+        rendered, fr.rendered = fr.rendered, None
         image, nsp, fw, cost, seg = rendered if rendered else render_forward(
-            packed, rgb, ranges, sorted_g, keys, background_rgb, height, width, tile_rows, sort_prefix)
-        ctx.cut = cut   # depth-cut frame: flags, complete ranges and overflow lists for the backward
-        ctx.save_for_backward(packed, rgb, ranges, sorted_g, background_rgb, nsp, fw, cost, seg)
+            fr.packed, rgb, fr.ranges, fr.sorted_g, fr.keys, fr.background, fr.height, fr.width, fr.tile_rows,
+            fr.sort_prefix)
+        saved = (fr.packed, rgb, fr.ranges, fr.sorted_g, fr.background, nsp, fw, cost, seg)
+        out = image
+        if policy is not None:
+            source = policy.source(fr, channels)
+            fmap, alpha, t_end = policy.forward(fr.packed, source, fr.ranges, fr.sorted_g, nsp, fr.height, fr.width)
+            saved += (source, t_end)
+            out = (image, fmap, alpha)
+        ctx.save_for_backward(*saved)
         ctx.set_materialize_grads(False)
-        ctx.dims = (height, width, tile_rows, uv.shape[0])
-        ctx.slab_sync = slab_sync
+        ctx.fr, ctx.policy, ctx.V = fr, policy, uv.shape[0]   # (fr.cut: flags, complete ranges, overflow lists)
         # the gradient mode of THIS frame is the default at its forward: a later set_backward_mode() cannot
         # race the backward the autograd engine runs on its own thread
         ctx.backward_mode = _hip.get_backward_mode()
-        return image
+        return out
 
     @staticmethod
-    def backward(ctx, grad_image):
-        packed, rgb, ranges, sorted_g, background_rgb, nsp, fw, cost, seg = ctx.saved_tensors
-        height, width, tile_rows, V = ctx.dims
-        if grad_image is None:
-            return (None,) * 16
-        slab = render_backward(packed, rgb, ranges, sorted_g, background_rgb, nsp, fw, grad_image.contiguous(),
-                               height, width, tile_rows, V, cost, ctx.backward_mode, seg, cut=ctx.cut)
-        if ctx.slab_sync is not None:
-            ctx.slab_sync(slab.view(-1))   # multi-GPU: sum the partial gradients of all bands in place
-        # the four gradients are views of the one slab; _Preprocess.backward recognises that
-        return (slab[:, SLAB_UV], slab[:, SLAB_CONIC], slab[:, SLAB_OPACITY], slab[:, SLAB_RGB]) + (None,) * 12
-
-
-class _RenderRGBD(torch.autograd.Function):
-    """_Render with two more outputs, depth and alpha [H, W] (gs_render_zalpha on the lists and the splat counts the
-    colour forward left).  One backward for the three: the prologue clears the slab and the dL/dz tail, the colour
-    backward runs if the image has a gradient, gs_render_zalpha_backward if depth or alpha has one, and _Preprocess
-    gets the one slab plus dL/dz.  An unused output costs no launch."""
-
-    @staticmethod
-    def forward(ctx, uv, conic, opacity, rgb, z, packed, xyz_cam, ranges, sorted_g, background_rgb, height, width,
-                keys=None, sort_prefix=0, rendered=None):
-        image, nsp, fw, cost, seg = rendered if rendered else render_forward(
-            packed, rgb, ranges, sorted_g, keys, background_rgb, height, width, None, sort_prefix)
-        depth, alpha, t_end = zalpha_forward(packed, xyz_cam, ranges, sorted_g, nsp, height, width)
-        ctx.save_for_backward(packed, rgb, xyz_cam, ranges, sorted_g, background_rgb, nsp, fw, cost, seg, t_end)
-        ctx.set_materialize_grads(False)
-        ctx.dims = (height, width, uv.shape[0])
-        ctx.backward_mode = _hip.get_backward_mode()   # the frame's mode is the default at its forward
-        return image, depth, alpha
-
-    @staticmethod
-    def backward(ctx, grad_image, grad_depth, grad_alpha):
-        packed, rgb, xyz_cam, ranges, sorted_g, background_rgb, nsp, fw, cost, seg, t_end = ctx.saved_tensors
-        height, width, V = ctx.dims
-        if grad_image is None and grad_depth is None and grad_alpha is None:
-            return (None,) * 15
-        geometric = grad_depth is not None or grad_alpha is not None
-        slab, g_z = render_backward(packed, rgb, ranges, sorted_g, background_rgb, nsp, fw,
-                                    grad_image.contiguous() if grad_image is not None else None, height, width, None,
-                                    V, cost, ctx.backward_mode, seg, tail=max(V, 1))
-        if geometric and V > 0:   # (nothing visible: nothing to add, and an empty slab has no address)
-            zalpha_backward(packed, xyz_cam, ranges, sorted_g, nsp, t_end, grad_depth, grad_alpha, height, width,
-                            slab, g_z)
-        return (slab[:, SLAB_UV], slab[:, SLAB_CONIC], slab[:, SLAB_OPACITY], slab[:, SLAB_RGB],
-                g_z[:V] if grad_depth is not None else None) + (None,) * 10   # (alpha alone leaves dL/dz zero)
-
-
-class _RenderFeatures(torch.autograd.Function):
-    """_Render with two more outputs, feature_map [H, W, C] and alpha [H, W] (gs_render_features on the lists and the
-    splat counts the colour forward left, feat [V, C] the visible Gaussians' rows).  One backward for the three, as
-    _RenderRGBD's: the prologue clears the slab, the colour backward runs if the image has a gradient,
-    gs_render_features_backward if feature_map or alpha has one (grad_features NULL unless feat requires a gradient
-    and feature_map has one).  An unused output costs no launch."""
-
-    @staticmethod
-    def forward(ctx, uv, conic, opacity, rgb, feat, packed, ranges, sorted_g, background_rgb, height, width,
-                keys=None, sort_prefix=0, rendered=None):
-        image, nsp, fw, cost, seg = rendered if rendered else render_forward(
-            packed, rgb, ranges, sorted_g, keys, background_rgb, height, width, None, sort_prefix)
-        fmap, alpha, t_end = features_forward(packed, feat, ranges, sorted_g, nsp, height, width)
-        ctx.save_for_backward(packed, rgb, feat, ranges, sorted_g, background_rgb, nsp, fw, cost, seg, t_end)
-        ctx.set_materialize_grads(False)
-        ctx.dims = (height, width, uv.shape[0])
-        ctx.backward_mode = _hip.get_backward_mode()   # the frame's mode is the default at its forward
-        return image, fmap, alpha
-
-    @staticmethod
-    def backward(ctx, grad_image, grad_map, grad_alpha):
-        packed, rgb, feat, ranges, sorted_g, background_rgb, nsp, fw, cost, seg, t_end = ctx.saved_tensors
-        height, width, V = ctx.dims
+    def backward(ctx, grad_image, grad_map=None, grad_alpha=None):
+        packed, rgb, ranges, sorted_g, background_rgb, nsp, fw, cost, seg, *mapped = ctx.saved_tensors
+        fr, policy, V = ctx.fr, ctx.policy, ctx.V
         if grad_image is None and grad_map is None and grad_alpha is None:
-            return (None,) * 14
-        slab = render_backward(packed, rgb, ranges, sorted_g, background_rgb, nsp, fw,
-                               grad_image.contiguous() if grad_image is not None else None, height, width, None,
-                               V, cost, ctx.backward_mode, seg)
-        g_feat = None
-        if grad_map is not None and ctx.needs_input_grad[4]:
-            g_feat = torch.zeros_like(feat)
-        if (grad_map is not None or grad_alpha is not None) and V > 0:   # (nothing visible: nothing to add)
-            features_backward(packed, feat, ranges, sorted_g, nsp, t_end, grad_map, grad_alpha, height, width, slab,
-                              g_feat)
-        return (slab[:, SLAB_UV], slab[:, SLAB_CONIC], slab[:, SLAB_OPACITY], slab[:, SLAB_RGB], g_feat) + (None,) * 9
+            return (None,) * len(ctx.needs_input_grad)
+        n_tail = policy.tail(V) if policy is not None else 0
+        out = render_backward(packed, rgb, ranges, sorted_g, background_rgb, nsp, fw,
+                              grad_image.contiguous() if grad_image is not None else None, fr.height, fr.width,
+                              fr.tile_rows, V, cost, ctx.backward_mode, seg, cut=fr.cut, tail=n_tail)
+        slab, tail = out if n_tail else (out, None)
+        g_channels = None
+        if policy is not None:
+            source, t_end = mapped
+            into, g_channels = policy.channel_grad(source, V, tail, grad_map, ctx.needs_input_grad[4])
+            # (nothing visible: nothing to add, and an empty slab has no address)
+            if (grad_map is not None or grad_alpha is not None) and V > 0:
+                policy.backward(packed, source, ranges, sorted_g, nsp, t_end, grad_map, grad_alpha, fr.height, fr.width,
+                                slab, into)
+        if fr.slab_sync is not None:
+            fr.slab_sync(slab.view(-1))   # multi-GPU: sum the partial gradients of all bands in place
+        # the four gradients are views of the one slab; _Preprocess.backward recognises that
+        return slab[:, SLAB_UV], slab[:, SLAB_CONIC], slab[:, SLAB_OPACITY], slab[:, SLAB_RGB], g_channels, None, None
 
 
 class _GatherRows(torch.autograd.Function):
@@ -942,7 +938,7 @@ class _RenderSH(torch.autograd.Function):
     def forward(ctx, uv, conic, opacity, coeffs, packed, ranges, sorted_g, rays, background_rgb, height, width,
                 tile_rows):
         dev = packed.device
-        nty = (height + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX
+        nty = _tile_grid(width, height)[1]
         row0, row1 = tile_rows if tile_rows is not None else (0, nty)
         alloc = torch.empty if tile_rows is None else torch.zeros
         P = height * width
@@ -980,18 +976,17 @@ def _rasterize_per_pixel_sh(g, camera_T_world, camera, near_thresh, far_thresh, 
     (image, culling_mask, uv) contract and the same kernels as the reference-shaped path of this colour mode
     (which spends ~4 ms per frame of workload B in its host glue); against it the frame differs as the
     precompute mode's does: by the fused per-Gaussian stage's explicit fp32 world->camera transform."""
-    out = _Preprocess.apply(
-        g.xyz.contiguous(), g.quaternion.contiguous(), g.scale.contiguous(), g.opacity.contiguous(),
-        g.rgb.contiguous(), None, camera_T_world.contiguous(), camera.K.contiguous(), int(camera.width),
-        int(camera.height), near_thresh, far_thresh, cull_mask_padding, mh_dist, tile_rows, 0, None)
-    uv, conic, opacity, _rgb_unused, packed, _xyz_cam, culling_mask, ranges, sorted_g, vis_idx = out[:10]
-    index = vis_idx.long()
+    # (sh=None: the per-Gaussian stage computes no colour; full sort, no early render; the rays depend on the pose)
+    fr, (uv, conic, opacity, _rgb_unused) = _begin_frame(
+        g, None, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist, background_rgb,
+        tile_rows=tile_rows)
+    index = fr.vis_idx.long()
     # coefficient 0 is the rgb parameter (rasterize.py:103: cat of rgb and sh)
     coeffs = torch.cat((_GatherRows.apply(g.rgb, index).unsqueeze(2), _GatherRows.apply(g.sh, index)), dim=2)
     rays = compute_rays_in_world_frame(camera, camera_T_world)
-    image = _RenderSH.apply(uv, conic, opacity, coeffs.contiguous(), packed, ranges, sorted_g, rays,
-                            background_rgb.contiguous(), int(camera.height), int(camera.width), tile_rows)
-    return image, culling_mask, uv
+    image = _RenderSH.apply(uv, conic, opacity, coeffs.contiguous(), fr.packed, fr.ranges, fr.sorted_g, rays,
+                            fr.background, fr.height, fr.width, tile_rows)
+    return image, fr.culling_mask, uv
 
 
 def render_depth(gaussians, alpha_threshold, camera_T_world, camera, near_thresh, cull_mask_padding, mh_dist):
@@ -1048,6 +1043,51 @@ def supported(gaussians, camera_T_world, camera, use_sh_precompute):
     return True
 
 
+def _refuse(who, gaussians, camera_T_world, camera, use_sh_precompute, background_rgb, frame_options, adam_plan):
+    """what the antialiased frame and the map frames (`who`) are served on, checked before anything is enqueued: each
+    refusal names its reason"""
+    g = gaussians
+    _require(not any(frame_options),
+             f"{who} serves whole single-GPU frames: tile_rows, return_aux, grad_sync, slab_sync and "
+             "frame_hook are not supported")
+    _require(adam_plan is None, f"{who} does not take the fused optimizer step (adam_plan)")
+    _require(g.sh is None or use_sh_precompute,
+             f"{who} needs the SH-precompute colour mode: per-pixel SH (use_sh_precompute=False) is not supported")
+    tensors = [t for t in (g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
+                           background_rgb) if t is not None]
+    _require(all(t.is_cuda and t.dtype == torch.float32 for t in tensors),
+             f"{who} needs float32 tensors on the GPU (no fp64, no CPU path)")
+
+
+def _begin_frame(gaussians, sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+                 background_rgb, who=None, use_sh_precompute=True, frame_options=(), features=None, adam_plan=None,
+                 **options):
+    """What every entry point does before its render node.  who (rasterize_rgbd, rasterize_features,
+    rasterize_contributions): refuse what that frame kind does not serve and validate; None: rasterize() has done both
+    before it chose this orchestration.  Then make the inputs contiguous and run _Preprocess on a frame record with
+    `options` (_frame_record's; a `who` frame sorts as SORT_PREFIX says and gives the pose its gradient; without
+    may_cut the depth cut stays off -- a cut frame's flagged tiles keep their lists elsewhere).  `sh`: the
+    coefficients the per-Gaussian stage folds into the colour.
+    -> (the frame record, (uv, conic, opacity, rgb[, z]))"""
+    g = gaussians
+    if who is not None:
+        _refuse(who, g, camera_T_world, camera, use_sh_precompute, background_rgb, frame_options, adam_plan)
+        if features is not None:
+            _require(torch.is_tensor(features) and features.dim() == 2 and features.shape[0] == g.xyz.shape[0],
+                     f"{who}: features must be [N, C], one row per Gaussian")
+            _require(1 <= features.shape[1] <= 32,
+                     f"{who}: features must have 1 to 32 columns (callers with more split the channels)")
+            _require(features.dtype == torch.float32 and features.device == g.xyz.device,
+                     f"{who}: features must be float32 on the Gaussians' device (no fp64, no CPU path)")
+        validate(g, camera_T_world, camera, background_rgb)
+        options = dict(options, sort_prefix=_hip.GS_SORT_PREFIX if SORT_PREFIX else 0, pose_grad=True)
+    fr = _frame_record(int(camera.width), int(camera.height), near_thresh, far_thresh, cull_mask_padding, mh_dist,
+                       background=background_rgb.contiguous(), adam_plan=adam_plan, **options)
+    return fr, _Preprocess.apply(
+        g.xyz.contiguous(), g.quaternion.contiguous(), g.scale.contiguous(), g.opacity.contiguous(), g.rgb.contiguous(),
+        sh.contiguous() if sh is not None else None, camera_T_world.contiguous(), camera.K.contiguous(), fr)
+
+
 def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
               use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None, slab_sync=None,
               frame_hook=None, adam_plan=None, antialiased=False):
@@ -1063,8 +1103,8 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
     anything else raises RuntimeError before a kernel is enqueued."""
     hooks = return_aux or grad_sync or slab_sync or frame_hook
     if antialiased:
-        _require_antialias_frame("rasterize", gaussians, camera_T_world, camera, use_sh_precompute, background_rgb,
-                                 (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), adam_plan)
+        _refuse("rasterize(antialiased=True)", gaussians, camera_T_world, camera, use_sh_precompute, background_rgb,
+                (tile_rows is not None, hooks), adam_plan)
     if adam_plan is not None:
         _require(not hooks and tile_rows is None, "the fused optimizer step serves whole single-GPU frames without hooks")
         _require(supported(gaussians, camera_T_world, camera, use_sh_precompute),
@@ -1082,7 +1122,7 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
                                            tile_rows=tile_rows, grad_sync=grad_sync)
     g = gaussians
     validate(g, camera_T_world, camera, background_rgb)
-    nat = native() if not (return_aux or grad_sync or slab_sync or frame_hook) else None
+    nat = native() if not hooks else None
     if nat is not None:
         nat.set_modes(bool(SORT_PREFIX), bool(EARLY_RENDER))
         nat.set_segments(0 if SEGMENTS == "auto" else (1 if SEGMENTS else -1))
@@ -1092,86 +1132,22 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
             return nat.rasterize_adam(g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
                                       int(camera.width), int(camera.height), near_thresh, far_thresh, cull_mask_padding,
                                       mh_dist, background_rgb, adam_plan)
-        if antialiased:
-            return nat.rasterize(g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
-                                 int(camera.width), int(camera.height), near_thresh, far_thresh, cull_mask_padding,
-                                 mh_dist, background_rgb, row0, row1, True)
         return nat.rasterize(g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
                              int(camera.width), int(camera.height), near_thresh, far_thresh, cull_mask_padding, mh_dist,
-                             background_rgb, row0, row1)
-    sh = g.sh.contiguous() if g.sh is not None else None
-    sort_prefix = _hip.GS_SORT_PREFIX if (SORT_PREFIX and not return_aux) else 0
-    cut_box = [] if not (return_aux or grad_sync or slab_sync or frame_hook) else None
-    out = _Preprocess.apply(
-        g.xyz.contiguous(), g.quaternion.contiguous(), g.scale.contiguous(), g.opacity.contiguous(),
-        g.rgb.contiguous(), sh, camera_T_world.contiguous(), camera.K.contiguous(), int(camera.width),
-        int(camera.height), near_thresh, far_thresh, cull_mask_padding, mh_dist, tile_rows, sort_prefix,
-        background_rgb.contiguous(), cut_box, adam_plan, not (grad_sync or slab_sync), False, bool(antialiased))
-    uv, conic, opacity, rgb, packed, xyz_cam, culling_mask, ranges, sorted_g, vis_idx, keys = out[:11]
+                             background_rgb, row0, row1, bool(antialiased))
+    # (refused and validated above; the depth cut only without hooks; the pose a constant on multi-GPU frames)
+    fr, (uv, conic, opacity, rgb) = _begin_frame(
+        g, g.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist, background_rgb,
+        adam_plan=adam_plan, tile_rows=tile_rows, sort_prefix=_hip.GS_SORT_PREFIX if (SORT_PREFIX and not return_aux) else 0,
+        pose_grad=not (grad_sync or slab_sync), antialiased=antialiased, may_cut=not hooks, slab_sync=slab_sync)
     if frame_hook is not None:   # multi-GPU cost-balanced bands: the band's tile ranges
-        frame_hook(dict(ranges=ranges, ntx=(int(camera.width) + TILE_EDGE_LENGTH_PX - 1) // TILE_EDGE_LENGTH_PX))
-    image = _Render.apply(uv, conic, opacity, rgb, packed, ranges, sorted_g, background_rgb.contiguous(),
-                          int(camera.height), int(camera.width), tile_rows, slab_sync, keys, sort_prefix,
-                          tuple(out[11:]), cut_box[0] if cut_box else None)
+        frame_hook(dict(ranges=fr.ranges, ntx=_tile_grid(fr.width, fr.height)[0]))
+    image = _Render.apply(uv, conic, opacity, rgb, None, fr, None)
     if return_aux:
-        return image, culling_mask, uv, dict(conic=conic, opacity=opacity, rgb=rgb, packed=packed,
-                                             xyz_camera_frame=xyz_cam, tile_ranges=ranges,
-                                             sorted_gaussians=sorted_g, vis_idx=vis_idx)
-    return image, culling_mask, uv
-
-
-def _require_antialias_frame(name, gaussians, camera_T_world, camera, use_sh_precompute, background_rgb, frame_options,
-                             adam_plan):
-    """what antialiased=True is served on, checked before anything is enqueued: each refusal names its reason"""
-    g = gaussians
-    _require(adam_plan is None, f"{name}(antialiased=True) does not take the fused optimizer step (adam_plan)")
-    _require(not any(frame_options),
-             f"{name}(antialiased=True) serves whole single-GPU frames: tile_rows, return_aux, grad_sync, slab_sync and "
-             "frame_hook are not supported")
-    _require(g.sh is None or use_sh_precompute,
-             f"{name}(antialiased=True) needs the SH-precompute colour mode: per-pixel SH (use_sh_precompute=False) is "
-             "not supported")
-    tensors = [t for t in (g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
-                           background_rgb) if t is not None]
-    _require(all(t.is_cuda and t.dtype == torch.float32 for t in tensors),
-             f"{name}(antialiased=True) needs float32 tensors on the GPU (no fp64, no CPU path)")
-
-
-def _map_frame(name, gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
-               use_sh_precompute, background_rgb, frame_options, adam_plan, features=None, antialiased=False, z_out=None):
-    """What rasterize_rgbd, rasterize_features and rasterize_contributions (`name`) do before their render node: refuse
-    what they do not serve, then preprocess the frame -- with z as one more output when there are no features (z_out:
-    says so itself).
-    -> (_Preprocess's outputs, sort_prefix, height, width)"""
-    g = gaussians
-    _require(not any(frame_options),
-             f"{name} serves whole single-GPU frames: tile_rows, return_aux, grad_sync, slab_sync and "
-             "frame_hook are not supported")
-    _require(adam_plan is None, f"{name} does not take the fused optimizer step (adam_plan)")
-    _require(g.sh is None or use_sh_precompute,
-             f"{name} needs the SH-precompute colour mode: per-pixel SH (use_sh_precompute=False) is not supported")
-    tensors = [t for t in (g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
-                           background_rgb) if t is not None]
-    _require(all(t.is_cuda and t.dtype == torch.float32 for t in tensors),
-             f"{name} needs float32 tensors on the GPU (no fp64, no CPU path)")
-    if features is not None:
-        _require(torch.is_tensor(features) and features.dim() == 2 and features.shape[0] == g.xyz.shape[0],
-                 f"{name}: features must be [N, C], one row per Gaussian")
-        _require(1 <= features.shape[1] <= 32,
-                 f"{name}: features must have 1 to 32 columns (callers with more split the channels)")
-        _require(features.dtype == torch.float32 and features.device == g.xyz.device,
-                 f"{name}: features must be float32 on the Gaussians' device (no fp64, no CPU path)")
-    validate(g, camera_T_world, camera, background_rgb)
-    sh = g.sh.contiguous() if g.sh is not None else None
-    sort_prefix = _hip.GS_SORT_PREFIX if SORT_PREFIX else 0
-    height, width = int(camera.height), int(camera.width)
-    # (no cut_box: the depth cut stays off -- a cut frame's flagged tiles keep their lists elsewhere)
-    out = _Preprocess.apply(
-        g.xyz.contiguous(), g.quaternion.contiguous(), g.scale.contiguous(), g.opacity.contiguous(),
-        g.rgb.contiguous(), sh, camera_T_world.contiguous(), camera.K.contiguous(), width, height, near_thresh,
-        far_thresh, cull_mask_padding, mh_dist, None, sort_prefix, background_rgb.contiguous(), None, None, True,
-        features is None if z_out is None else bool(z_out), bool(antialiased))
-    return out, sort_prefix, height, width
+        return image, fr.culling_mask, uv, dict(conic=conic, opacity=opacity, rgb=rgb, packed=fr.packed,
+                                                xyz_camera_frame=fr.xyz_cam, tile_ranges=fr.ranges,
+                                                sorted_gaussians=fr.sorted_g, vis_idx=fr.vis_idx)
+    return image, fr.culling_mask, uv
 
 
 def rasterize_rgbd(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
@@ -1189,15 +1165,13 @@ def rasterize_rgbd(gaussians, camera_T_world, camera, near_thresh, far_thresh, c
     Whole single-GPU fp32 frames in the SH-precompute colour mode, Python orchestration, depth cut off: anything
     else raises RuntimeError (the trailing keyword arguments exist only to say so).  antialiased: as rasterize()'s --
     the maps' weights then carry the antialiased opacity too."""
-    out, sort_prefix, height, width = _map_frame(
-        "rasterize_rgbd", gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
-        use_sh_precompute, background_rgb, (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook),
-        adam_plan, antialiased=antialiased)
-    uv, conic, opacity, rgb, packed, xyz_cam, culling_mask, ranges, sorted_g, _vis_idx, keys = out[:11]
-    image, depth, alpha = _RenderRGBD.apply(uv, conic, opacity, rgb, out[-1], packed, xyz_cam, ranges, sorted_g,
-                                            background_rgb.contiguous(), height, width, keys, sort_prefix,
-                                            tuple(out[11:-1]))
-    return image, depth, alpha, culling_mask, uv
+    fr, (uv, conic, opacity, rgb, z) = _begin_frame(
+        gaussians, gaussians.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+        background_rgb, "rasterize_rgbd", use_sh_precompute,
+        (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), adam_plan=adam_plan,
+        antialiased=antialiased, z_out=True)
+    image, depth, alpha = _Render.apply(uv, conic, opacity, rgb, z, fr, _DepthMap)
+    return image, depth, alpha, fr.culling_mask, uv
 
 
 def rasterize_features(gaussians, features, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
@@ -1216,16 +1190,14 @@ def rasterize_features(gaussians, features, camera_T_world, camera, near_thresh,
     pose term); their backward is the true derivative (DESIGN.md "Feature maps").  Whole single-GPU fp32 frames in the
     SH-precompute colour mode, Python orchestration, depth cut off: anything else raises RuntimeError (the trailing
     keyword arguments exist only to say so).  antialiased: as rasterize()'s."""
-    out, sort_prefix, height, width = _map_frame(
-        "rasterize_features", gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
-        use_sh_precompute, background_rgb, (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook),
-        adam_plan, features, antialiased=antialiased)
-    uv, conic, opacity, rgb, packed, _xyz_cam, culling_mask, ranges, sorted_g, vis_idx, keys = out[:11]
-    feat = _GatherRows.apply(features, vis_idx.long()).contiguous()
-    image, feature_map, alpha = _RenderFeatures.apply(uv, conic, opacity, rgb, feat, packed, ranges, sorted_g,
-                                                      background_rgb.contiguous(), height, width, keys, sort_prefix,
-                                                      tuple(out[11:]))
-    return image, feature_map, alpha, culling_mask, uv
+    fr, (uv, conic, opacity, rgb) = _begin_frame(
+        gaussians, gaussians.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+        background_rgb, "rasterize_features", use_sh_precompute,
+        (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), features, adam_plan,
+        antialiased=antialiased)
+    feat = _GatherRows.apply(features, fr.vis_idx.long()).contiguous()
+    image, feature_map, alpha = _Render.apply(uv, conic, opacity, rgb, feat, fr, _FeatureMap)
+    return image, feature_map, alpha, fr.culling_mask, uv
 
 
 class ContributionStats:
@@ -1289,20 +1261,19 @@ def rasterize_contributions(gaussians, camera_T_world, camera, near_thresh, far_
         if stats is not None:
             _require(isinstance(stats, ContributionStats), "rasterize_contributions: stats must be a ContributionStats")
             stats.check(n)
-        out, sort_prefix, height, width = _map_frame(
-            "rasterize_contributions", gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding,
-            mh_dist, use_sh_precompute, background_rgb,
-            (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), adam_plan, antialiased=antialiased,
-            z_out=False)
+        fr, (_uv, _conic, _opacity, rgb) = _begin_frame(
+            gaussians, gaussians.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+            background_rgb, "rasterize_contributions", use_sh_precompute,
+            (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), adam_plan=adam_plan,
+            antialiased=antialiased)
         if stats is None:
             stats = ContributionStats.zeros(n, gaussians.xyz.device)
         else:
             stats.check(n, gaussians.xyz.device)
-        _uv, _conic, _opacity, rgb, packed, _xyz_cam, culling_mask, ranges, sorted_g, vis_idx, keys = out[:11]
-        image, nsp, _fw, _cost, _seg = out[11:] if len(out) > 11 else render_forward(
-            packed, rgb, ranges, sorted_g, keys, background_rgb.contiguous(), height, width, None, sort_prefix)
-        if vis_idx.shape[0] > 0:   # (nothing visible: nothing to add, and empty tensors have no address)
-            contributions_forward(packed, ranges, sorted_g, nsp, height, width, vis_idx, stats.weight_sum,
-                                  stats.weight_max, stats.pixel_count)
+        image, nsp, _fw, _cost, _seg = fr.rendered if fr.rendered else render_forward(
+            fr.packed, rgb, fr.ranges, fr.sorted_g, fr.keys, fr.background, fr.height, fr.width, None, fr.sort_prefix)
+        if fr.vis_idx.shape[0] > 0:   # (nothing visible: nothing to add, and empty tensors have no address)
+            contributions_forward(fr.packed, fr.ranges, fr.sorted_g, nsp, fr.height, fr.width, fr.vis_idx,
+                                  stats.weight_sum, stats.weight_max, stats.pixel_count)
         stats.frames += 1
-        return image.detach(), stats, culling_mask
+        return image.detach(), stats, fr.culling_mask

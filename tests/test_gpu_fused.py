@@ -386,6 +386,54 @@ def test_backward_hands_the_slab_through_without_a_copy(monkeypatch):
     assert uv.grad is not None and scaled_err(uv.grad, py_uv_grad) < 1e-5
 
 
+def test_python_frames_release_their_memory_by_reference_count():
+    """Every Python-orchestrated frame kind, with the cyclic collector off: once a frame's outputs are dropped its device
+    memory is back, so torch.cuda.memory_allocated() after the third and the fourth frame are equal (frames 1 and 2
+    fill the module's bounded per-shape caches: capacity hints, the pinned read ring, empties).  A frame record that
+    refers to itself would keep its two arenas until the collector runs."""
+    import gc
+    W, H = 128, 96
+    g, cam, T = make_scene(2000, W, H, 1, seed=3, device=DEV)
+    leaves = [getattr(g, k).requires_grad_(True) for k in PARAMS]
+    feat = torch.rand(2000, 3, generator=torch.Generator().manual_seed(1)).to(DEV).requires_grad_(True)
+    bg = torch.zeros(3, device=DEV)
+    gi = make_grad_image(W, H, seed=1, device=DEV)
+    args = (T, cam, 0.3, 500.0, 100, 3.0)
+
+    def backward(*outputs):
+        # image-like outputs [H, W, C] get gi's first C channels, maps [H, W] its first channel
+        torch.autograd.backward(outputs, [gi[..., :o.shape[2]] if o.dim() == 3 else gi[..., 0] for o in outputs])
+
+    kinds = {
+        "rasterize": lambda: backward(fused.rasterize(g, *args, True, bg)[0]),
+        "frame_hook": lambda: backward(fused.rasterize(g, *args, True, bg, frame_hook=lambda d: None)[0]),
+        "rgbd": lambda: backward(*fused.rasterize_rgbd(g, *args, True, bg)[:3]),
+        "features": lambda: backward(*fused.rasterize_features(g, feat, *args, True, bg)[:3]),
+        "per_pixel_sh": lambda: backward(fused.rasterize(g, *args, False, bg)[0]),
+        "contributions": lambda: fused.rasterize_contributions(g, *args, True, bg),
+    }
+    prev = fused.NATIVE
+    fused.NATIVE = False
+    gc.collect()
+    gc.disable()
+    try:
+        for name, frame in kinds.items():
+            seen = []
+            for _ in range(4):
+                frame()
+                for x in leaves + [feat]:
+                    x.grad = None
+                fused.reset_counters()
+                fused.last_flags(clear=True)
+                torch.cuda.synchronize()
+                seen.append(torch.cuda.memory_allocated())
+            print(f"[python frame memory] {name}: {seen}")
+            assert seen[2] == seen[3], (name, seen)
+    finally:
+        gc.enable()
+        fused.NATIVE = prev
+
+
 @pytest.mark.parametrize("deg,bgval", [(0, 0.0), (3, 0.5)])
 def test_native_orchestration_equals_python_orchestration(deg, bgval):
     """csrc/frame_hip.cpp against fused.py's own stages: same kernels in the same order -> image and

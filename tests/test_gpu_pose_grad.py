@@ -195,9 +195,8 @@ def test_leaf_gradients_do_not_depend_on_the_pose_gradient():
         g, cam, T = to_device(sc, DEV)
         leaves = [getattr(g, k).requires_grad_(True) for k in PARAMS]
         T.requires_grad_(want)
-        out = fused._Preprocess.apply(*leaves, T, cam.K, sc.W, sc.H, sc.near, sc.far, sc.pad, sc.mh, None, 0, None, None,
-                                      None, True)
-        uv, conic, opa, rgb = out[:4]
+        uv, conic, opa, rgb = fused._Preprocess.apply(
+            *leaves, T, cam.K, fused._frame_record(sc.W, sc.H, sc.near, sc.far, sc.pad, sc.mh, pose_grad=True))
         s = c.slab.to(DEV)
         torch.autograd.backward([uv, conic, opa, rgb], [s[:, fused.SLAB_UV], s[:, fused.SLAB_CONIC],
                                                         s[:, fused.SLAB_OPACITY], s[:, fused.SLAB_RGB]])
