@@ -5,7 +5,8 @@ The cut must be invisible in every result: the kept list of a tile is a depth PR
 reference's list), the image and num_splats are those of the complete lists bit for bit -- tiles that run out of
 their kept prefix are repaired on the device from the complete list -- and the gradients differ by summation order
 only.  Checked against the HIP path without the cut (itself bit-equal to the oracle at these sizes:
-tests/test_gpu_fullsize_parity.py, tests/test_gpu_wholeframe_parity.py) and, for the lists, entry by entry."""
+tests/test_gpu_fullsize_parity.py, tests/test_gpu_wholeframe_parity.py) and, for the lists, entry by entry.
+(Small scenes, every array of the stage and the repair lists against the CPU oracle: tests/test_gpu_cut_lists.py.)"""
 import ctypes
 
 import pytest
@@ -14,6 +15,7 @@ import torch
 from gaussian_splatting_amd import _hip, fused
 from gaussian_splatting_amd.synthetic import DEFAULTS, WORKLOADS, make_grad_image, make_scene
 
+from .cut_ref import sortable
 from .helpers import report, scaled_err
 
 pytestmark = pytest.mark.gpu
@@ -38,11 +40,6 @@ def cut_views(f):
     off = [(p.value - ws.data_ptr()) // 4 for p in ptrs]
     return (ws[off[0]:off[0] + f.T], ws[off[1]:off[1] + f.T], ws[off[2]:off[2] + 1024], ws[off[3]:off[3] + 1025],
             ws[off[4]:off[4] + 2])
-
-
-def sortable(z):
-    u = z.contiguous().view(torch.int32).long() & 0xffffffff
-    return torch.where(u >= 0x80000000, (~u) & 0xffffffff, u | 0x80000000)
 
 
 @pytest.mark.parametrize("name,N,W,H,deg,seed", [("dense", 400_000, 320, 240, 0, 3), ("D", *WORKLOADS["D"], 0)])

@@ -14,10 +14,12 @@ from gaussian_splatting_amd.sharded import band_of, owner_blocks
 from gaussian_splatting_amd.synthetic import make_grad_image
 from oracle import gs_oracle
 
+from .cut_ref import cut_reference, sortable
 from .helpers import report
 from .ref64 import (KINDS, general_camera_scene, oracle_stages, oracle_vjp, r_measure, random_slab, ref64_abs_vjp,
                     ref64_stage, to_device)
 from .test_gpu_band_frontend import run_new, run_old
+from .test_gpu_depth_cut import cut_views
 from .test_gpu_fused import cpu_expected_stages
 
 pytestmark = pytest.mark.gpu
@@ -139,6 +141,14 @@ def test_forward_of_every_entry_point_against_ref64(kind, deg):
         if cut:
             for k in got:
                 assert torch.equal(got[k], single[k]), k
+            # the cut's lists: depth prefixes of the oracle's complete lists, cut where tests/cut_ref.py cuts them
+            bstar, totals, bounds, _, ctrl = (x.cpu() for x in cut_views(f))
+            ref = cut_reference(exp["ranges"], exp["sorted"], sortable(exp["xyz_c"][:, 2]), bounds)
+            assert torch.equal(f.cut.full_ranges.cpu().long(), exp["ranges"].long()) and f.cut.S_full == int(exp["ranges"][-1])
+            assert torch.equal(totals.long(), ref.totals) and int(ctrl[0]) == ref.deepest
+            assert torch.equal(bstar.long()[ref.totals > 0], ref.bstar[ref.totals > 0])
+            assert torch.equal(f.ranges.cpu().long(), ref.kept_ranges)
+            assert torch.equal(f.sorted_g.cpu().long(), ref.kept_sorted)
         single = got
     # ---- the band paths: gs_band_project + gs_preprocess_forward_list, gs_band_frontend ---------------------------
     g, cam, T = to_device(sc, DEV)
