@@ -1094,6 +1094,14 @@ __global__ __launch_bounds__(RB) void k_render_fwd(
     static_assert(sizeof(T) == 4 && N_SH == 1, "the fused fp32 kernel; everything else goes to k_render_fwd_general");
     const int t_local = tile_of_block(blockIdx.x, nt);
     if (t_local >= nt) return;
+    // Launch position sets the wave priority: the last eighth of the grid runs at priority 1.  A SIMD arbitrates
+    // vector issue by priority, then age, so the workgroups dispatched last -- whose completion ends the kernel --
+    // would otherwise be the losers on every SIMD they share with older tiles (profiles/r15/render_wave_priority_ab.txt).
+    // Block index and a kernel argument only: a scalar compare and branch around one s_setprio, which ignores EXEC.
+    {
+        const int grid = (nt + 7) & ~7;   // render_grid(nt)
+        if ((int)blockIdx.x >= grid - (grid >> 3)) __builtin_amdgcn_s_setprio(1);
+    }
     render_tile_fwd_fused<false>(tile0 + t_local, packed, rgb, ranges, sorted, bg, W, H, ntx,
                                  nsp_out, fw_out, image, sort_prefix, tile_flags, false, cap, tile_cost, src_opacity,
                                  src_conic, SEG_NONE, full_ranges, flag_counter, touch_masks);
@@ -1343,7 +1351,8 @@ __device__ __forceinline__ void flush_sum_slots(float* s_acc, const float* s_geo
 // The fp32 kernels.  At most 7 waves per SIMD (no minimum: k_render_bwd_sh sits far below).  Squeezed into the 64
 // registers of 8 waves, k_render_bwd<float, 1> reloads a coefficient of the exponential in every visit; with the 72
 // of 7 it stays resident (104 -> 103 vector instructions per visit, 0.4506 -> 0.4466 ms at D alternating on one box),
-// and the kernel never held 8 waves anyway (5-7).
+// and the kernel never held 8 waves anyway (5-7).  Among those 5-7 waves the position in the list sets the
+// wave priority (the chunk loop of k_render_bwd<float, 1>): a wave deep in its list goes first.
 #ifdef GS_BWD_WAVES
 #define GS_BWD_OCC __attribute__((amdgpu_waves_per_eu(GS_BWD_WAVES, GS_BWD_WAVES)))
 #else
@@ -1491,10 +1500,19 @@ __global__ __launch_bounds__(RB) GS_BWD_OCC void k_render_bwd(
     // (9 scalar instructions) per visit; exact mode never wraps
     static_assert(RCHUNK <= REF_CH, "one wrap per chunk");
     const int q1_wrap = exact ? 0x7fffffff : REF_CH;
+    const int prio_from = seg_on ? 0x7fffffff : first_chunk + 2;   // (wave priority, below)
     for (int chunk = last_chunk; chunk >= first_chunk; chunk--) {
         const int base = chunk * RCHUNK;
         const int base_q = exact ? base : base % REF_CH;
         const int cnt = min(RCHUNK, seg_hi - base);
+        // Position in the walk sets the wave priority: 1 while more than two chunks of the list lie ahead, 0 for the last
+        // two.  Deep in the list few lanes contribute and a visit is a dependent chain that wants its issue slot at once;
+        // the last chunks (the front of the list, most lanes contributing) are dense vector work that fills the slots
+        // left over.  A SIMD arbitrates vector issue by priority, then age: without this the old waves -- the ones in
+        // their dense front chunks -- win (profiles/r15/render_wave_priority_ab.txt).  Loop counters only: one scalar
+        // compare per chunk around the s_setprio, nothing per visit.  (Depth segments, two chunks each, stay at 0.)
+        if (chunk >= prio_from) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
         GS_STAT(1, 1);
         __syncthreads();   // previous chunk fully flushed
         stage_chunk<float, 1, 1>(packed, rgb, sorted, s0 + base, cnt, tid, s_geom, nullptr, s_idx, src_opacity, src_conic);

@@ -6,7 +6,9 @@ libgsplat_hip_timeline.so).
 Every wave of k_render_fwd / k_render_bwd records its begin and end time (100 MHz constant clock), the
 compute unit it ran on and its visit count.  Printed per kernel: span, mean concurrency (waves in flight),
 the concurrency profile over 20 equal time slices, the share of the span during which fewer than half the
-peak number of waves were in flight (the tail), and the spread of per-wave durations and per-CU busy time.
+peak number of waves were in flight (the tail), the spread of per-wave durations and per-CU busy time, when the last
+workgroup started, and -- per tenth of the workgroups in launch order (the record's slot is block * 4 + wave) -- when
+they started, how long they lived and what a visit cost them.
 """
 import argparse
 import ctypes
@@ -27,7 +29,25 @@ from gaussian_splatting_amd.synthetic import DEFAULTS, WORKLOADS, make_grad_imag
 CAP = 1 << 16   # GS_TIMELINE_CAP of csrc/render.hip
 
 
+def launch_deciles(slots, rec, start):
+    """per tenth of the workgroups that ran, in launch order: mean start (us after the kernel's first wave), mean
+    lifetime of a wave (us), wave time per visit (ns) and visits per wave"""
+    order = np.argsort(slots // 4, kind="stable")
+    out = []
+    for part in np.array_split(order, 10):
+        r = rec[part]
+        dur = (r[:, 1].astype(np.int64) - r[:, 0].astype(np.int64)).astype(np.float64)
+        visits = r[:, 3].astype(np.float64)
+        out.append({"start_us": round(float((r[:, 0].astype(np.int64) - start).mean() / 100.0), 1),
+                    "wave_life_us": round(float(dur.mean() / 100.0), 1),
+                    "ns_per_visit": round(float(dur.sum() * 10.0 / max(visits.sum(), 1)), 1),
+                    "visits_per_wave": round(float(visits.mean()), 1)})
+    return out
+
+
 def analyse(rec, slices=20):
+    slots = np.nonzero(rec[:, 1] != 0)[0]   # (idle blocks of the grid and unused slots leave no record)
+    rec = rec[slots]
     t0, t1 = rec[:, 0].astype(np.int64), rec[:, 1].astype(np.int64)
     start, end = t0.min(), t1.max()
     span = max(int(end - start), 1)
@@ -56,6 +76,9 @@ def analyse(rec, slices=20):
         "waves": int(len(rec)), "span_us": span / 100.0, "wave_time_sum_us": float(dur.sum() / 100.0),
         "mean_waves_in_flight": float(dur.sum() / span), "peak_waves_in_flight": int(peak),
         "share_of_span_below_half_peak": tail,
+        "last_wave_start_us": float((t0.max() - start) / 100.0),
+        "last_start_to_end_us": float((end - t0.max()) / 100.0),
+        "by_launch_order_tenth": launch_deciles(slots, rec, start),
         "waves_in_flight_by_slice": [round(c, 1) for c in conc],
         "wave_duration_us": {"mean": float(dur.mean() / 100), "p50": float(np.percentile(dur, 50) / 100),
                              "p90": float(np.percentile(dur, 90) / 100), "max": float(dur.max() / 100)},
@@ -103,9 +126,9 @@ def main():
     frame()
     _hip.check(lib.gs_debug_render_timeline(buf, CAP))
     rec = np.ctypeslib.as_array(buf).reshape(2, CAP, 10).copy()
-    fwd, bwd = (r[r[:, 1] != 0] for r in rec)
+    fwd, bwd = rec
     out = {"workload": args.workload, "tile_rows": list(rows) if rows else None, "segments": args.segments,
-           "forward": analyse(fwd), "backward": analyse(bwd)}
+           "lib": os.path.basename(_hip.LIB_PATH), "forward": analyse(fwd), "backward": analyse(bwd)}
     text = json.dumps(out, indent=1)
     print(text)
     if args.out:
