@@ -55,6 +55,8 @@
 // (k_render_features_fwd / _bwd<CP>) composited with the weights of the entries the colour forward walked.  One
 // forward walk and one backward walk with its flush, render_map_fwd / render_map_bwd, templated on a channel policy
 // that holds what a family has of its own: where the channel values come from and where their sums and gradients go.
+// The depth distortion (k_render_distortion_fwd / _bwd) is the depth map's walk with two more sums: its forward is a
+// policy of render_map_fwd, its backward, whose c_k needs w_k, has a walk body of its own.
 //
 // Numerics.  The fp32 forward is bit-identical to the CPU restatement: same operation order and
 // operand precisions as render.cu (including its double-literal promotions), the IEEE quotient (formed
@@ -2599,6 +2601,182 @@ __global__ __launch_bounds__(RB) void k_render_zalpha_bwd(
 }
 
 // ---------------------------------------------------------------------------------------------------
+// depth distortion (no reference counterpart), fp32: the weight a pixel spreads over depth
+// ---------------------------------------------------------------------------------------------------
+// With alpha_k, the contribute decision, T_k and w_k of the depth kernels above (the same walk: depth, alpha and T_end
+// come out with k_render_zalpha_fwd's bits), A_<k = sum_{j<k} w_j and D_<k = sum_{j<k} w_j z_j over the contributors in
+// front of k:
+//   distortion[p] = 2 sum_k w_k (z_k A_<k - D_<k) = sum_{i != j} w_i w_j (z_later - z_earlier)
+// in LIST order, no |.|: on lists sorted by z (the frame's own) that is sum_{i,j} w_i w_j |z_i - z_j|, the distortion
+// loss of Mip-NeRF 360 without its normalisations.  The forward is render_map_fwd with three sums -- D, X and the
+// policy's own copy of A (the walk's A is not handed to add(); the copy sees the same additions, the same bits):
+//   X = fma(w, fma(z, A, -D), X)      D = fma(w, z, D)      A += w            the store is 2 X
+struct DistortionFwd : DepthChannel {
+    float* __restrict__ depth;
+    float* __restrict__ distortion;
+    static constexpr int N = 3;   // D | X | A
+    __device__ __forceinline__ void add(float (&M)[3], float w, const float* rec, int) const {
+        const float z = rec[9];
+        M[1] = __builtin_fmaf(w, __builtin_fmaf(z, M[2], -M[0]), M[1]);
+        M[0] = __builtin_fmaf(w, z, M[0]);
+        M[2] += w;
+    }
+    __device__ __forceinline__ void store(const float (&M)[3], size_t p) const {
+        depth[p] = M[0];
+        distortion[p] = 2.0f * M[1];
+    }
+};
+
+__global__ __launch_bounds__(RB) void k_render_distortion_fwd(
+    const float* __restrict__ packed, const float* __restrict__ xyz_cam, const int* __restrict__ ranges,
+    const int* __restrict__ sorted, const int* __restrict__ nsp_in, int W, int H, int ntx, int tile0, int nt,
+    float* __restrict__ distortion, float* __restrict__ depth, float* __restrict__ alpha_out,
+    float* __restrict__ t_out) {
+    __shared__ alignas(16) float s_geom[MAP_FWD_CHUNK * GS_PACKED_WIDTH];
+    __shared__ unsigned long long s_mask[4][MAP_FWD_CHUNK / 64];
+    __shared__ int s_max[4];
+    DistortionFwd ch{{xyz_cam}, depth, distortion};
+    render_map_fwd(ch, packed, ranges, sorted, nsp_in, W, H, ntx, tile0, nt, alpha_out, t_out, s_geom, s_mask, s_max);
+}
+
+// The true derivative of distortion, depth and alpha together (decisions held constant, alpha above 0.9999 as 0.9999,
+// no walk quirk), back to front like render_map_bwd.  c_k of the distortion needs w_k, which render_map_bwd's c() hook
+// is called before, so the kernel has its OWN walk body (render_map_bwd keeps its ISA); what differs from that walk is
+// marked.  The suffix sums A_>k = sum_{j>k} w_j and D_>k = sum_{j>k} w_j z_j are carried, the prefixes come from the
+// forward's totals alpha[p] and depth[p]:
+//   A_<k = alpha[p] - A_>k - w_k      D_<k = depth[p] - D_>k - w_k z_k
+//   e_k = 2 [z_k (A_<k - A_>k) - D_<k + D_>k]                        (d distortion / d w_k)
+//   c_k = fma(g_dist, e_k, fma(g_depth, z_k, g_alpha))               (g_dist = 0: the depth kernel's c_k, bit for bit)
+//   dL/dz_k = g_depth w_k + g_dist 2 w_k (A_<k - A_>k)               (sum 0 of the slot, to grad_z)
+// then dL/dalpha_k = T_k c_k - S / (1 - alpha_k), S = fma(w_k, c_k, S) and the chain to opacity, u, v, conic, the nine
+// sums, the slots and the flush exactly as render_map_bwd has them.
+__global__ __launch_bounds__(RB) void k_render_distortion_bwd(
+    const float* __restrict__ packed, const float* __restrict__ xyz_cam, const int* __restrict__ ranges,
+    const int* __restrict__ sorted, const int* __restrict__ nsp_in, const float* __restrict__ t_in,
+    const float* __restrict__ depth_in, const float* __restrict__ alpha_in, const float* __restrict__ g_dist,
+    const float* __restrict__ g_depth, const float* __restrict__ g_alpha, int W, int H, int ntx, int tile0, int nt,
+    float* __restrict__ slab, float* __restrict__ grad_z) {
+    __shared__ alignas(16) float s_geom[MAP_BWD_CHUNK * GS_PACKED_WIDTH];
+    __shared__ int s_idx[MAP_BWD_CHUNK];
+    __shared__ float s_acc[4 * MAP_BWD_CHUNK * 9];   // [wave][entry][9]
+    __shared__ int s_max[4];
+    __shared__ unsigned long long s_mask[4][1];
+    __shared__ unsigned long long s_hit[4][1];       // slots written by each wave
+    constexpr int SV = 9;
+    constexpr int RCHUNK = MAP_BWD_CHUNK;
+    const int t_local = tile_of_block(blockIdx.x, nt);
+    if (t_local >= nt) return;
+    const int tile = tile0 + t_local;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const PixelMap px = pixel_of_thread(tile % ntx, tile / ntx, tid);
+    const bool valid = px.u < W && px.v < H;
+    const int s0 = ranges[tile];
+    const int n_tile = ranges[tile + 1] - s0;
+    if (n_tile <= 0) return;
+    int nsp = 0;
+    float T = 1.0f, ga = 0.0f, gd = 0.0f, gx = 0.0f;
+    float A_tot = 0.0f, D_tot = 0.0f;   // the forward's totals of the pixel
+    if (valid) {
+        const size_t p = (size_t)px.v * W + px.u;
+        nsp = nsp_in[p];
+        T = t_in[p];
+        A_tot = alpha_in[p];
+        D_tot = depth_in[p];
+        if (g_dist != nullptr) gx = g_dist[p];
+        if (g_depth != nullptr) gd = g_depth[p];
+        if (g_alpha != nullptr) ga = g_alpha[p];
+    }
+    int n_used, wave_used;
+    zalpha_reach(nsp, n_tile, tid, s_max, n_used, wave_used);
+    if (n_used <= 0) return;
+    const float pu = float(px.u), pv = float(px.v);
+    const int slot_off = slot_lane_offset(lane);
+    const bool slot_stores = slot_off >= 0;
+    const int slot_lane_base = wave * RCHUNK * SV + (slot_stores ? slot_off : 0);
+    const DepthChannel ch{xyz_cam};
+    float S = 0.0f;                   // sum of alpha_j T_j c_j over the contributors behind the current entry
+    float A_gt = 0.0f, D_gt = 0.0f;   // sums of w_j and of w_j z_j over them
+    for (int chunk = (n_used - 1) / RCHUNK; chunk >= 0; chunk--) {
+        const int base = chunk * RCHUNK;
+        const int cnt = min(RCHUNK, n_used - base);
+        __syncthreads();   // previous chunk fully flushed
+        stage_chunk<float, 1>(packed, nullptr, sorted, s0 + base, cnt, tid, s_geom, nullptr, s_idx);
+        ch.stage(sorted, s0 + base, cnt, tid, s_geom, s_idx);
+        // (no barrier in between: thread t tests the record thread t staged)
+        build_touch_masks<float, RCHUNK>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
+        __syncthreads();
+        unsigned long long m = wave_uniform(s_mask[wave][0]);
+        unsigned long long hit = 0;   // the entries of this chunk whose slot the wave wrote
+        while (m) {
+            const int i = 63 - __builtin_clzll(m);
+            m &= ~(1ull << i);
+            const int k = base + i;
+            if (k >= wave_used) continue;   // wave-uniform: no pixel of the patch walked this far
+            const float* rec = s_geom + i * GS_PACKED_WIDTH;
+            const Vec4<float> g0 = *reinterpret_cast<const Vec4<float>*>(rec);       // u v r2 opacity
+            const Vec4<float> g1 = *reinterpret_cast<const Vec4<float>*>(rec + 4);   // a b c det
+            const Vec4<float> g2 = *reinterpret_cast<const Vec4<float>*>(rec + 8);   // 1/det, z (depth)
+            const ZalphaVisit v = zalpha_alpha(g0, g1, g2.x, pu, pv, k < nsp);
+            if (ballot(v.contrib) == 0) continue;   // every reaching lane skipped the entry
+            float v0 = 0.0f, w = 0.0f;
+            if (v.contrib) {
+                float alpha = v.alpha;
+                if (alpha > Thr<float>::sat_gt()) alpha = Thr<float>::alpha_cap();   // min(0.9999, .)
+                const float r1ma = fast_rcp(1.0f - alpha);
+                const float z = g2.y;
+                T = T * r1ma;                        // T_k: the transmittance in front of the entry
+                const float aT = alpha * T;          // w_k
+                // (the distortion's part: prefixes from the totals, e_k, and the z column)
+                const float wz = aT * z;
+                const float A_lt = A_tot - A_gt - aT;
+                const float D_lt = D_tot - D_gt - wz;
+                const float dA = A_lt - A_gt;
+                const float e = 2.0f * (z * dA - D_lt + D_gt);
+                const float c = __builtin_fmaf(gx, e, __builtin_fmaf(gd, z, ga));
+                const float dalpha = T * c - S * r1ma;
+                S = __builtin_fmaf(aT, c, S);
+                v0 = __builtin_fmaf(gx, 2.0f * aT * dA, gd * aT);
+                A_gt += aT;
+                D_gt += wz;
+                w = v.norm_prob * dalpha;
+            }
+            float val[9];
+            const float du2 = v.du * v.du, dv2 = v.dv * v.dv, duv = v.du * v.dv;
+            val[0] = v0; val[1] = 0.0f; val[2] = 0.0f;
+            val[3] = w; val[4] = w * v.du; val[5] = w * v.dv;
+            val[6] = (dv2 - g1.z * v.mh) * w;
+            val[7] = (g1.y * v.mh - duv) * w;
+            val[8] = (du2 - g1.x * v.mh) * w;
+            int slot_i = i * SV;
+            asm volatile("" : "+s"(slot_i));
+            reduce9_to_slot(val, slot_stores, s_acc, slot_lane_base + slot_i);
+            hit |= 1ull << i;
+        }
+        if (lane == 0) s_hit[wave][0] = hit;
+        __syncthreads();
+        // (the flush's thread index is formed inside the chunk loop, as in render_map_bwd)
+        int row_tid = tid;
+        asm volatile("" : "+v"(row_tid));
+        flush_sum_slots<RCHUNK, SV>(s_acc, s_geom, s_hit, row_tid, cnt);
+        __syncthreads();
+        // nine lanes = one row (seven rows per wave instruction, see k_render_bwd)
+        const int sub = lane / SV, col = lane - sub * SV;   // lane 63: idle
+        for (int r0 = wave * 7; r0 < cnt; r0 += 28) {
+            const int r = r0 + sub;
+            const bool in = lane < 63 && r < cnt;
+            const float x = in ? s_acc[r * SV + col] : 0.0f;
+            const unsigned long long nz = ballot(x != 0.0f);
+            const bool any = in && ((nz >> (sub * SV)) & 0x1ffull) != 0;
+            if (any) {
+                const int g = s_idx[r];
+                if (col >= 3) global_add(slab + (size_t)g * SV + col, x);
+                else if (col == 0) global_add(grad_z + g, x);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // per-Gaussian feature vectors composited with the frame's weights (no reference counterpart), fp32
 // ---------------------------------------------------------------------------------------------------
 // render_map_fwd / render_map_bwd with C <= 32 caller-supplied channels in place of the one channel z:
@@ -3544,6 +3722,43 @@ int gs_render_zalpha_backward(const void* packed, const void* xyz_camera_frame, 
         (const float*)transmittance, (const float*)grad_depth, (const float*)grad_alpha, W, H, t.ntx, t.tile0, t.nt,
         (float*)grad_slab, (float*)grad_z);
     return check_launch("render_zalpha_backward");
+}
+
+int gs_render_distortion(const void* packed, const void* xyz_camera_frame, const int32_t* tile_ranges,
+                         const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel, int W, int H,
+                         int tile_row0, int tile_row1, void* distortion, void* depth, void* alpha, void* transmittance,
+                         void* stream) {
+    MapTiles t;
+    if (int e = map_entry_tiles("render_distortion", false, 1, packed, tile_ranges, num_splats_per_pixel, transmittance,
+                                depth, alpha, W, H, tile_row0, tile_row1, &t))
+        return e;
+    GS_REQUIRE(distortion != nullptr, "render_distortion: an output is NULL");
+    if (t.nt == 0) return GS_OK;
+    k_render_distortion_fwd<<<render_grid(t.nt), RB, 0, (hipStream_t)stream>>>(
+        (const float*)packed, (const float*)xyz_camera_frame, tile_ranges, sorted_gaussians, num_splats_per_pixel, W, H,
+        t.ntx, t.tile0, t.nt, (float*)distortion, (float*)depth, (float*)alpha, (float*)transmittance);
+    return check_launch("render_distortion");
+}
+
+int gs_render_distortion_backward(const void* packed, const void* xyz_camera_frame, const int32_t* tile_ranges,
+                                  const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel,
+                                  const void* transmittance, const void* depth, const void* alpha,
+                                  const void* grad_distortion, const void* grad_depth, const void* grad_alpha, int W,
+                                  int H, int tile_row0, int tile_row1, void* grad_slab, void* grad_z, void* stream) {
+    MapTiles t;
+    if (int e = map_entry_tiles("render_distortion_backward", true, 1, packed, tile_ranges, num_splats_per_pixel,
+                                transmittance, nullptr, nullptr, W, H, tile_row0, tile_row1, &t))
+        return e;
+    GS_REQUIRE(depth != nullptr && alpha != nullptr, "render_distortion_backward: depth or alpha is NULL");
+    if (t.nt == 0 || (grad_distortion == nullptr && grad_depth == nullptr && grad_alpha == nullptr))
+        return GS_OK;   // nothing to add
+    GS_REQUIRE(grad_slab != nullptr && grad_z != nullptr, "render_distortion_backward: grad_slab or grad_z is NULL");
+    k_render_distortion_bwd<<<render_grid(t.nt), RB, 0, (hipStream_t)stream>>>(
+        (const float*)packed, (const float*)xyz_camera_frame, tile_ranges, sorted_gaussians, num_splats_per_pixel,
+        (const float*)transmittance, (const float*)depth, (const float*)alpha, (const float*)grad_distortion,
+        (const float*)grad_depth, (const float*)grad_alpha, W, H, t.ntx, t.tile0, t.nt, (float*)grad_slab,
+        (float*)grad_z);
+    return check_launch("render_distortion_backward");
 }
 
 int gs_render_features(const void* packed, const void* features, int n_channels, const int32_t* tile_ranges,

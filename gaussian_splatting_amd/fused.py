@@ -22,7 +22,9 @@ preprocess_backward) that gaussian_splatting_amd.sharded composes differently fo
 
 rasterize_rgbd is the same frame with two more differentiable outputs, depth and accumulated opacity [H, W]
 (_Render with the map policy _DepthMap: gs_render_zalpha / gs_render_zalpha_backward next to the colour kernels,
-gs_z_backward behind the per-Gaussian backward).
+gs_z_backward behind the per-Gaussian backward).  rasterize_distortion adds the depth-distortion map of
+the same walk as a fourth output (_DistortionMap: gs_render_distortion / gs_render_distortion_backward in place of the
+depth kernels).
 
 rasterize_features composites caller-supplied per-Gaussian feature vectors [N, C <= 32] with the frame's weights into a
 differentiable [H, W, C] map next to the image and the accumulated opacity (_Render with the map policy _FeatureMap:
@@ -677,6 +679,26 @@ def zalpha_backward(packed, xyz_cam, ranges, sorted_g, nsp, t_end, grad_depth, g
               _p(gd), _p(ga), width, height, 0, nty, _p(slab), _p(grad_z), _stream())
 
 
+def distortion_forward(packed, xyz_cam, ranges, sorted_g, nsp, height, width):
+    """-> (depth, distortion), alpha, T_end, each [H, W] (gs_render_distortion): zalpha_forward's three maps, bit for
+    bit, and the depth distortion 2 sum_k w_k (z_k A_<k - D_<k) of the same walk; one allocation"""
+    nty = _tile_grid(width, height)[1]
+    buf = torch.empty(4, height, width, dtype=torch.float32, device=packed.device)
+    _hip.call("gs_render_distortion", _p(packed), _p(xyz_cam), _p(ranges), _p(sorted_g), _p(nsp), width, height, 0, nty,
+              _p(buf[3]), _p(buf[0]), _p(buf[1]), _p(buf[2]), _stream())
+    return (buf[0], buf[3]), buf[1], buf[2]
+
+
+def distortion_backward(packed, xyz_cam, ranges, sorted_g, nsp, t_end, depth, alpha, grad_distortion, grad_depth,
+                        grad_alpha, height, width, slab, grad_z):
+    """adds the distortion / depth / alpha maps' gradients to columns 3..8 of the (cleared or colour-filled) slab and
+    to grad_z (gs_render_distortion_backward); depth, alpha: the forward's totals; any grad may be None"""
+    nty = _tile_grid(width, height)[1]
+    gx, gd, ga = (g.contiguous() if g is not None else None for g in (grad_distortion, grad_depth, grad_alpha))
+    _hip.call("gs_render_distortion_backward", _p(packed), _p(xyz_cam), _p(ranges), _p(sorted_g), _p(nsp), _p(t_end),
+              _p(depth), _p(alpha), _p(gx), _p(gd), _p(ga), width, height, 0, nty, _p(slab), _p(grad_z), _stream())
+
+
 def features_forward(packed, feat, ranges, sorted_g, nsp, height, width):
     """-> feature_map [H, W, C], alpha, T_end [H, W] (gs_render_features) for the visible Gaussians' feature rows
     feat [V, C] on the lists of the frame whose colour forward left nsp; one allocation"""
@@ -740,7 +762,7 @@ def _frame_record(width, height, near_thresh, far_thresh, cull_mask_padding, mh_
     sh itself (preprocess_backward_adam) and returns a gradient for xyz only
     pose_grad: the frame gives camera_T_world its gradient when it requires one (pose_backward); False keeps the pose a
     constant (multi-GPU frames: the sum would need an all-reduce; per-pixel SH: its rays depend on it)
-    z_out (rasterize_rgbd only): _Preprocess has one more output, z = xyz_camera_frame[:V, 2] as a differentiable
+    z_out (rasterize_rgbd, rasterize_distortion): _Preprocess has one more output, z = xyz_camera_frame[:V, 2] as a differentiable
     tensor -- the handle through which the depth map's dL/dz comes back to that node
     antialiased: the packed record's opacity is sigmoid * comp; the opacity OUTPUT stays the sigmoid (the render reads
     the record), so the gradient that comes back for it is dL/d(sigmoid * comp) and the backward folds it
@@ -835,6 +857,7 @@ class _DepthMap:
     """_Render's map policy of rasterize_rgbd (DepthFwd / DepthBwd of csrc/render.hip): channel z [V] -> depth, alpha
     [H, W] (gs_render_zalpha / gs_render_zalpha_backward); dL/dz is a tail behind the slab's rows, cleared with them"""
     forward, backward = staticmethod(zalpha_forward), staticmethod(zalpha_backward)
+    extra = False   # no fourth output
     # what the kernels read: the record's camera-frame positions; z is only the handle dL/dz goes back through
     source = staticmethod(lambda fr, z: fr.xyz_cam)
     tail = staticmethod(lambda V: max(V, 1))   # floats behind the slab's rows
@@ -845,10 +868,20 @@ class _DepthMap:
         return tail, (tail[:V] if grad_depth is not None else None)   # (alpha alone leaves dL/dz None)
 
 
+class _DistortionMap(_DepthMap):
+    """_Render's map policy of rasterize_distortion (DistortionFwd, k_render_distortion_bwd): _DepthMap with one more
+    output, the depth distortion [H, W], from gs_render_distortion / gs_render_distortion_backward IN PLACE of the depth
+    kernels; the backward reads the forward's depth and alpha, and dL/dz (from depth's or distortion's gradient) takes
+    _DepthMap's way"""
+    forward, backward = staticmethod(distortion_forward), staticmethod(distortion_backward)
+    extra = True    # forward -> ((depth, distortion), alpha, T_end); backward(..., t_end, depth, alpha, g_dist, g_depth, ...)
+
+
 class _FeatureMap:
     """_Render's map policy of rasterize_features (FeaturesFwd / FeaturesBwd): channels feat [V, C], the visible
     Gaussians' rows -> feature_map [H, W, C], alpha [H, W] (gs_render_features / gs_render_features_backward)"""
     forward, backward = staticmethod(features_forward), staticmethod(features_backward)
+    extra = False
     source = staticmethod(lambda fr, feat: feat)
     tail = staticmethod(lambda V: 0)
 
@@ -862,7 +895,8 @@ class _FeatureMap:
 
 class _Render(torch.autograd.Function):
     """uv, conic, opacity, rgb, the map policy's channels (None without one), the frame record, the policy -> image,
-    or (image, map, alpha) with a policy: its kernels run on the lists and the splat counts the colour forward left.
+    or (image, map, alpha) with a policy (+ its extra map when it declares one): its kernels run on the lists and the
+    splat counts the colour forward left.
     One backward for all outputs: the prologue clears the slab (and the policy's tail), the colour backward runs if
     the image has a gradient, the policy's if its map or alpha has one, and _Preprocess gets the one slab plus the
     channels' gradient.  An unused output costs no launch."""
@@ -880,6 +914,10 @@ class _Render(torch.autograd.Function):
             fmap, alpha, t_end = policy.forward(fr.packed, source, fr.ranges, fr.sorted_g, nsp, fr.height, fr.width)
             saved += (source, t_end)
             out = (image, fmap, alpha)
+            if policy.extra:   # (map, extra map): a fourth output, and a backward that reads the forward's totals
+                fmap, extra = fmap
+                saved += (fmap, alpha)
+                out = (image, fmap, alpha, extra)
         ctx.save_for_backward(*saved)
         ctx.set_materialize_grads(False)
         ctx.fr, ctx.policy, ctx.V = fr, policy, uv.shape[0]   # (fr.cut: flags, complete ranges, overflow lists)
@@ -889,10 +927,10 @@ class _Render(torch.autograd.Function):
         return out
 
     @staticmethod
-    def backward(ctx, grad_image, grad_map=None, grad_alpha=None):
+    def backward(ctx, grad_image, grad_map=None, grad_alpha=None, grad_extra=None):
         packed, rgb, ranges, sorted_g, background_rgb, nsp, fw, cost, seg, *mapped = ctx.saved_tensors
         fr, policy, V = ctx.fr, ctx.policy, ctx.V
-        if grad_image is None and grad_map is None and grad_alpha is None:
+        if grad_image is None and grad_map is None and grad_alpha is None and grad_extra is None:
             return (None,) * len(ctx.needs_input_grad)
         n_tail = policy.tail(V) if policy is not None else 0
         out = render_backward(packed, rgb, ranges, sorted_g, background_rgb, nsp, fw,
@@ -901,12 +939,14 @@ class _Render(torch.autograd.Function):
         slab, tail = out if n_tail else (out, None)
         g_channels = None
         if policy is not None:
-            source, t_end = mapped
-            into, g_channels = policy.channel_grad(source, V, tail, grad_map, ctx.needs_input_grad[4])
+            source, t_end, *totals = mapped   # (totals: the map and alpha of the forward, for a policy with an extra map)
+            maps = (grad_extra, grad_map) if policy.extra else (grad_map,)
+            into, g_channels = policy.channel_grad(source, V, tail, next((m for m in maps if m is not None), None),
+                                                   ctx.needs_input_grad[4])
             # (nothing visible: nothing to add, and an empty slab has no address)
-            if (grad_map is not None or grad_alpha is not None) and V > 0:
-                policy.backward(packed, source, ranges, sorted_g, nsp, t_end, grad_map, grad_alpha, fr.height, fr.width,
-                                slab, into)
+            if (any(m is not None for m in maps) or grad_alpha is not None) and V > 0:
+                policy.backward(packed, source, ranges, sorted_g, nsp, t_end, *totals, *maps, grad_alpha, fr.height,
+                                fr.width, slab, into)
         if fr.slab_sync is not None:
             fr.slab_sync(slab.view(-1))   # multi-GPU: sum the partial gradients of all bands in place
         # the four gradients are views of the one slab; _Preprocess.backward recognises that
@@ -1172,6 +1212,32 @@ def rasterize_rgbd(gaussians, camera_T_world, camera, near_thresh, far_thresh, c
         antialiased=antialiased, z_out=True)
     image, depth, alpha = _Render.apply(uv, conic, opacity, rgb, z, fr, _DepthMap)
     return image, depth, alpha, fr.culling_mask, uv
+
+
+def rasterize_distortion(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+                         use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None,
+                         slab_sync=None, frame_hook=None, adam_plan=None, antialiased=False):
+    """rasterize_rgbd() with the depth-distortion map of the same walk:
+
+        image, depth, alpha, distortion, culling_mask, uv = rasterize_distortion(...)
+
+    image, culling_mask and uv are those of rasterize(), depth and alpha those of rasterize_rgbd() on the same inputs,
+    bit for bit.  distortion [H, W] = 2 sum_k w_k (z_k A_<k - D_<k) with A_<k, D_<k the sums of w_j and w_j z_j over
+    the contributors in front of entry k: on the frame's lists, which are sorted by z, sum_{i,j} w_i w_j |z_i - z_j|,
+    the distortion loss of Mip-NeRF 360 / 2DGS.  No background term, no normalisation by alpha, no depth warp: the
+    value is in units of z (callers scale z, or divide by alpha^2).  All four outputs carry gradients to the Gaussians'
+    parameters and, when it requires one, to camera_T_world; the maps' backward is their true derivative, one kernel
+    for the three of them in place of rasterize_rgbd's (DESIGN.md "Depth distortion").  An output without a gradient
+    costs nothing.  Whole single-GPU fp32 frames in the SH-precompute colour mode, Python orchestration, depth cut off:
+    anything else raises RuntimeError (the trailing keyword arguments exist only to say so).  antialiased: as
+    rasterize()'s."""
+    fr, (uv, conic, opacity, rgb, z) = _begin_frame(
+        gaussians, gaussians.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+        background_rgb, "rasterize_distortion", use_sh_precompute,
+        (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), adam_plan=adam_plan,
+        antialiased=antialiased, z_out=True)
+    image, depth, alpha, distortion = _Render.apply(uv, conic, opacity, rgb, z, fr, _DistortionMap)
+    return image, depth, alpha, distortion, fr.culling_mask, uv
 
 
 def rasterize_features(gaussians, features, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,

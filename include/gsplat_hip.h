@@ -541,6 +541,43 @@ int gs_render_zalpha_backward(const void* packed, const void* xyz_camera_frame, 
 int gs_z_backward(const int32_t* rank, const void* grad_z, const void* camera_T_world, int v_base, int N,
                   void* grad_xyz, void* stream);
 
+/* Depth distortion of a rendered frame (ABI 16; no reference counterpart), fp32: the regulariser of Mip-NeRF 360 /
+ * 2DGS without its normalisations, together with the depth and alpha maps.  With alpha_k, the contribute decision, T_k
+ * and w_k = alpha_k T_k exactly as gs_render_zalpha forms them (the same code), z = xyz_camera_frame[:, 2], and for the
+ * contributors in front of entry k  A_<k = sum_{j<k} w_j,  D_<k = sum_{j<k} w_j z_j:
+ *   distortion[p] = 2 sum_k w_k (z_k A_<k - D_<k) = sum_{i != j} w_i w_j (z_later - z_earlier)
+ * over the entries k < num_splats_per_pixel[p] in LIST order: no |.| is taken.  On lists sorted by z (the fused
+ * frame's own, sorted by the bits of this z) that is sum_{i,j} w_i w_j |z_i - z_j|.  No background term, no
+ * normalisation by alpha, no depth warp: the value is in units of z, callers scale z.  Per contributing visit
+ *   X = fma(w, fma(z, A, -D), X),  D = fma(w, z, D),  A += w,  T = fma(-alpha, T, T),   the store is 2 X,
+ * so depth, alpha and transmittance are bit-equal to gs_render_zalpha's.
+ *   outputs   distortion[H,W], depth[H,W], alpha[H,W], transmittance[H,W]: written for every pixel of the tile rows
+ *             [tile_row0, tile_row1), untouched elsewhere.  Empty lists (V == 0) give 0, 0, 0, 1. */
+int gs_render_distortion(const void* packed, const void* xyz_camera_frame, const int32_t* tile_ranges,
+                         const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel, int W, int H,
+                         int tile_row0, int tile_row1, void* distortion, void* depth, void* alpha, void* transmittance,
+                         void* stream);
+/* Backward of the above for all three maps at once: the TRUE derivative, decisions held constant, as
+ * gs_render_zalpha_backward (no walk quirk; alpha above 0.9999 enters as 0.9999).  Back to front from transmittance
+ * with the suffix sums A_>k, D_>k; the prefixes come from the forward's totals,
+ *   A_<k = alpha[p] - A_>k - w_k,  D_<k = depth[p] - D_>k - w_k z_k,
+ *   e_k = 2 [z_k (A_<k - A_>k) - D_<k + D_>k]   (d distortion / d w_k),
+ *   c_k = fma(grad_distortion, e_k, fma(grad_depth, z_k, grad_alpha)),
+ *   dL/dz_k = grad_depth w_k + grad_distortion 2 w_k (A_<k - A_>k),
+ * then dL/dalpha_k = T_k c_k - S / (1 - alpha_k), S = fma(w_k, c_k, S) and alpha -> opacity, u, v, conic as
+ * gs_render_zalpha_backward: with grad_distortion NULL the result is that call's.
+ *   transmittance, depth, alpha                [H,W], what gs_render_distortion wrote
+ *   grad_distortion, grad_depth, grad_alpha    [H,W]; any may be NULL = all zeros (all NULL: nothing is launched)
+ *   grad_slab   [V,9]: columns 3..8 accumulated, columns 0..2 untouched
+ *   grad_z      float[V], accumulated: dL/dz of each visible Gaussian (gs_z_backward takes it on)
+ * Both are added into (one atomic per value per (list entry, tile)); the caller zeroes them.  Rows of Gaussians no
+ * pixel uses are not touched.  Empty lists (V == 0) touch nothing. */
+int gs_render_distortion_backward(const void* packed, const void* xyz_camera_frame, const int32_t* tile_ranges,
+                                  const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel,
+                                  const void* transmittance, const void* depth, const void* alpha,
+                                  const void* grad_distortion, const void* grad_depth, const void* grad_alpha, int W,
+                                  int H, int tile_row0, int tile_row1, void* grad_slab, void* grad_z, void* stream);
+
 /* Per-Gaussian feature vectors composited with the frame's weights (ABI 12; no reference counterpart), fp32.  With
  * alpha_k, the contribute decision, T_k and w_k = alpha_k T_k exactly as gs_render_zalpha forms them (the same code),
  * for pixel p and the list entries k < num_splats_per_pixel[p]:

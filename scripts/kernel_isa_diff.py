@@ -24,6 +24,8 @@ import sys
 
 LABEL = re.compile(r"\.(LBB|Lfunc_end|Lfunc_begin)\d+")
 LOOP_NOTE = re.compile(r"\bBB\d+_")   # the same index in the "; in Loop: Header=BB<n>_<m>" comments
+LABEL_PAD = re.compile(r"^(\.LBBN_\d+):\s+;")
+# (the blanks between a label and its comment: the comment's column is fixed, so they change when the index gains a digit)
 
 
 def kernels(path):
@@ -36,7 +38,8 @@ def kernels(path):
         d0 = lines.index("\t.amdhsa_kernel " + name)
         d1 = lines.index("\t.end_amdhsa_kernel", d0)
         sets = [l for l in lines[d1:] if l.startswith("\t.set " + name + ".")]   # the resource counts
-        text = [LOOP_NOTE.sub("BBN_", LABEL.sub(r".\1N", l)) for l in lines[start:end + 1] + lines[d0:d1 + 1] + sets]
+        text = [LABEL_PAD.sub(r"\1: ;", LOOP_NOTE.sub("BBN_", LABEL.sub(r".\1N", l)))
+                for l in lines[start:end + 1] + lines[d0:d1 + 1] + sets]
         mnem = [l.split()[0] for l in lines[start:end] if l.startswith("\t") and not l.lstrip().startswith((".", ";"))]
         out[name] = (text, len(mnem), mnem)
     return out
