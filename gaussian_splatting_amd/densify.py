@@ -316,3 +316,207 @@ class DensityController:
                                f"has {n} (sweep the views again after N changed)")
         # (a positive threshold implies pixel_count > 0; at 0 the count alone decides)
         return self.prune((stats.weight_max >= min_weight_max) & (stats.pixel_count > 0))
+
+
+# ---- MCMC densification (no reference counterpart) ------------------------------------------------------
+@dataclass
+class MCMCConfig:
+    """3DGS-MCMC ("3D Gaussian Splatting as Markov Chain Monte Carlo") with the defaults in wide use"""
+    cap_max: int = 1_000_000        # the budget: add_new never grows the set beyond it
+    min_opacity: float = 0.005      # a Gaussian at or below it is dead
+    grow_factor: float = 1.05       # growth per refinement step
+    noise_lr: float = 5e5           # position noise = noise_lr * xyz_lr * gate(opacity) * Sigma_world * N(0, 1)
+    gate_k: float = 100.0
+    gate_x0: float = 0.995
+    refine_start: int = 500
+    refine_stop: int = 25_000
+    refine_every: int = 100
+    opacity_reg: float = 0.01
+    scale_reg: float = 0.01
+
+
+_MCMC_KIND = {"scale": 2, "opacity": 4}   # gs_mcmc_relocate: the two tensors the relocation rewrites
+_MCMC_MAX_ROWS = 1 << 24                  # torch.multinomial takes at most 2^24 categories
+
+
+class MCMCController(DensityController):
+    """Training at a fixed budget of Gaussians, without opacity resets:
+
+        ctrl = MCMCController(gaussians, optimizer, MCMCConfig(cap_max=...))
+        ... per iteration:  (loss + ctrl.regularizer()).backward(); optimizer.step(); ctrl.step(it, xyz_lr)
+
+    step() relocates the dead Gaussians onto live ones and grows the set by 5 % on the refinement schedule, and adds
+    covariance-shaped noise to the positions on every call.  The optimizer is the one DensityController takes; its
+    groups and state are kept as that class keeps them (_names, _state, _swap).  Only the methods below are served:
+    the clone / split / delete step of the base class reads a DensifyConfig."""
+
+    def __init__(self, gaussians, optimizer, config=None):
+        super().__init__(gaussians, optimizer, config if config is not None else MCMCConfig())
+
+    def _guard(self, what):
+        """raises before anything is enqueued; -> the row count"""
+        g = self.gaussians
+        N = g.xyz.shape[0]
+        if N > _MCMC_MAX_ROWS:
+            raise RuntimeError(f"{what}: {N} Gaussians are more than 2^24, the limit of torch.multinomial")
+        if self.config.cap_max < N:
+            raise RuntimeError(f"{what}: cap_max {self.config.cap_max} is below the current count {N}")
+        for k in self._names():
+            t = getattr(g, k)
+            if t.dtype != torch.float32 or not t.is_cuda:
+                raise RuntimeError(f"{what} needs float32 tensors on the GPU: {k} is {t.dtype} on {t.device}")
+            if not t.is_contiguous() or t.shape[0] != N:
+                raise RuntimeError(f"{what} needs contiguous tensors of {N} rows: {k} is not")
+        return N
+
+    @staticmethod
+    def _draw(sample, probs, n):
+        rows = sample(probs, n) if sample is not None else torch.multinomial(probs, n, replacement=True)
+        if rows.dtype != torch.int64 or tuple(rows.shape) != (n,) or rows.device != probs.device:
+            raise RuntimeError(f"sample(probs, n) must return int64[{n}] on {probs.device}")
+        return rows
+
+    def opacity_floor(self):
+        """the smallest opacity a relocated Gaussian gets (gs_mcmc_relocate's min_opacity): min_opacity raised by two
+        fp32 steps of its logit, so that the stored logit lies above the dead threshold and a relocated row is alive by
+        relocate's own `<=` (at min_opacity itself it would be dead again at once).  The c_float of the C ABI moves
+        the logit by 0.13 of a step at most."""
+        dead_logit = torch.tensor(inverse_sigmoid(self.config.min_opacity), dtype=torch.float32)
+        step = torch.tensor(math.inf, dtype=torch.float32)
+        above = torch.nextafter(torch.nextafter(dead_logit, step), step)
+        return 1.0 / (1.0 + math.exp(-float(above)))
+
+    def _relocate_call(self, names, params, exp_avg, exp_avg_sq, ratio, dst_rows, src_rows):
+        n = len(names)
+        arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in ts])
+        widths = (ctypes.c_int32 * n)(*[int(math.prod(t.shape[1:])) for t in params])
+        kinds = (ctypes.c_int32 * n)(*[_MCMC_KIND.get(k, 0) for k in names])
+        _hip.call("gs_mcmc_relocate", n, arr(params), arr(exp_avg), arr(exp_avg_sq), widths, kinds, params[0].shape[0],
+                  _p(ratio), _p(dst_rows), _p(src_rows), dst_rows.shape[0], self.opacity_floor(),
+                  _hip.current_stream())
+
+    def _moments(self, name):
+        st = self._state(name)
+        if not (bool(st) and "exp_avg" in st):
+            return None, None
+        if not (st["exp_avg"].is_contiguous() and st["exp_avg_sq"].is_contiguous()):
+            raise RuntimeError(f"MCMC densification needs contiguous optimizer moments: those of {name} are not")
+        return st["exp_avg"], st["exp_avg_sq"]
+
+    @staticmethod
+    def _ratio(n_rows, src_rows):
+        """1 + how often each row was drawn: torch.bincount(src_rows, minlength=n_rows) + 1 as int32, formed without
+        bincount's host read"""
+        ratio = torch.ones(n_rows, dtype=torch.int32, device=src_rows.device)
+        return ratio.index_add_(0, src_rows, torch.ones_like(src_rows, dtype=torch.int32))
+
+    @torch.no_grad()
+    def relocate(self, sample=None):
+        """Moves every dead Gaussian (opacity <= min_opacity, compared as logits) onto a live one drawn with probability
+        proportional to its opacity, with replacement; a Gaussian drawn n - 1 times and its n - 1 copies get the
+        opacity and scale that leave the image unchanged (gs_mcmc_relocate).  In place: parameter objects, optimizer
+        keys and step counts stay; the moments of sources and destinations become 0 (other
+        implementations keep the dead row's moments); the gradient accumulators are reset.  One host read (the dead
+        count).  sample(probs, n) -> int64[n] with entries in [0, len(probs)), not checked, replaces
+        torch.multinomial (tests).  -> {"relocated", "n_before", "n_after"}"""
+        g, cfg = self.gaussians, self.config
+        N = self._guard("relocate")
+        info = self.last_info = dict(relocated=0, n_before=N, n_after=N)
+        logit = g.opacity.detach().reshape(N)
+        dead = logit <= inverse_sigmoid(cfg.min_opacity)
+        n_dead = int(dead.sum().item())   # the host read
+        if n_dead == 0 or n_dead == N:
+            return info
+        order = torch.argsort(dead.to(torch.uint8), descending=True, stable=True)   # dead rows first, each part in order
+        dst_rows, alive_rows = order[:n_dead], order[n_dead:]
+        src_rows = alive_rows[self._draw(sample, torch.sigmoid(logit[alive_rows]), n_dead)]
+        names = self._names()
+        moments = [self._moments(k) for k in names]
+        self._relocate_call(names, [getattr(g, k).detach() for k in names], [m for m, _ in moments],
+                            [v for _, v in moments], self._ratio(N, src_rows), dst_rows.to(torch.int32),
+                            src_rows.to(torch.int32))
+        self.reset_grad_accum()
+        info["relocated"] = n_dead
+        return info
+
+    @torch.no_grad()
+    def add_new(self, sample=None):
+        """Grows the set to min(cap_max, int(grow_factor * N)) rows: the new rows are copies of Gaussians drawn as in
+        relocate (from all rows), corrected the same way.  One gs_densify_move with the identity as destination fills
+        the first N rows of the new tensors and moments, one gs_mcmc_relocate the appended ones; the optimizer groups
+        are re-keyed, the step counts kept, the gradient accumulators reset.  No host read.  -> {"added", "n_before",
+        "n_after"}"""
+        g, cfg = self.gaussians, self.config
+        N = self._guard("add_new")
+        n_add = max(0, min(cfg.cap_max, int(cfg.grow_factor * N)) - N)
+        info = self.last_info = dict(added=n_add, n_before=N, n_after=N + n_add)
+        if n_add == 0:
+            return info
+        dev = g.xyz.device
+        src_rows = self._draw(sample, torch.sigmoid(g.opacity.detach().reshape(N)), n_add)
+        names = self._names()
+        src, dst, src_m, dst_m, src_v, dst_v = [], [], [], [], [], []
+        for k in names:
+            t = getattr(g, k).detach()
+            m, v = self._moments(k)
+            src.append(t)
+            dst.append(torch.empty((N + n_add,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev))
+            src_m.append(m)
+            src_v.append(v)
+            dst_m.append(torch.empty_like(dst[-1]) if m is not None else None)
+            dst_v.append(torch.empty_like(dst[-1]) if m is not None else None)
+        n = len(names)
+        arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in ts])
+        widths = (ctypes.c_int32 * n)(*[int(math.prod(t.shape[1:])) for t in src])
+        kinds = (ctypes.c_int32 * n)(*[_KIND.get(k, 0) for k in names])
+        xyz_s, scale_s, quat_s = (src[names.index(k)] for k in ("xyz", "scale", "quaternion"))
+        identity = torch.arange(N, dtype=torch.int32, device=dev)
+        minus = torch.full((N,), -1, dtype=torch.int32, device=dev)
+        no_samples = torch.zeros(1, 3, device=dev)   # (n_split == 0: never read)
+        _hip.call("gs_densify_move", n, arr(src), arr(dst), arr(src_m), arr(dst_m), arr(src_v), arr(dst_v), widths,
+                  kinds, N, _p(identity), _p(minus), _p(minus), _p(minus), _p(xyz_s), _p(scale_s), _p(quat_s),
+                  _p(self.xyz_grad_accum), _p(self.grad_accum_count), _p(no_samples), 0, 0, N, 1.0,
+                  _hip.current_stream())
+        new_rows = torch.arange(N, N + n_add, dtype=torch.int32, device=dev)
+        self._relocate_call(names, dst, dst_m, dst_v, self._ratio(N + n_add, src_rows), new_rows,
+                            src_rows.to(torch.int32))
+        for k, d, m, v in zip(names, dst, dst_m, dst_v):
+            self._swap(k, d, m, v)
+        self.reset_grad_accum()
+        return info
+
+    @torch.no_grad()
+    def inject_noise(self, xyz_lr, noise=None):
+        """xyz += Sigma_world (noise * gate(opacity) * noise_lr * xyz_lr) in place, one launch (gs_mcmc_add_noise).
+        noise: [N, 3] standard normal samples (default: torch.randn_like(xyz))"""
+        g, cfg = self.gaussians, self.config
+        N = self._guard("inject_noise")
+        xyz = g.xyz.detach()
+        if noise is None:
+            noise = torch.randn_like(xyz)
+        elif not (torch.is_tensor(noise) and noise.dtype == torch.float32 and tuple(noise.shape) == (N, 3)
+                  and noise.device == xyz.device and noise.is_contiguous()):
+            raise RuntimeError(f"inject_noise: noise must be a contiguous float32 [{N}, 3] tensor on {xyz.device}")
+        _hip.call("gs_mcmc_add_noise", _p(xyz), _p(g.quaternion.detach()), _p(g.scale.detach()), _p(g.opacity.detach()),
+                  _p(noise), N, cfg.noise_lr * xyz_lr, cfg.gate_k, cfg.gate_x0, _hip.current_stream())
+
+    def regularizer(self):
+        """opacity_reg * mean(sigmoid(opacity)) + scale_reg * mean(exp(scale)): differentiable, to be added to the loss
+        (it is what makes Gaussians die, so that relocate has something to move)"""
+        g, cfg = self.gaussians, self.config
+        return cfg.opacity_reg * torch.sigmoid(g.opacity).mean() + cfg.scale_reg * torch.exp(g.scale).mean()
+
+    @torch.no_grad()
+    def step(self, it, xyz_lr):
+        """The schedule, after optimizer.step() of iteration `it`: relocate() then add_new() when refine_start < it <
+        refine_stop and it % refine_every == 0, inject_noise(xyz_lr) on every call.  -> {"refined", "relocated",
+        "added", "n_before", "n_after"}"""
+        cfg = self.config
+        N = self.gaussians.xyz.shape[0]
+        info = dict(refined=False, relocated=0, added=0, n_before=N, n_after=N)
+        if cfg.refine_start < it < cfg.refine_stop and it % cfg.refine_every == 0:
+            moved, grown = self.relocate(), self.add_new()
+            info.update(refined=True, relocated=moved["relocated"], added=grown["added"], n_after=grown["n_after"])
+        self.inject_noise(xyz_lr)
+        self.last_info = info
+        return info

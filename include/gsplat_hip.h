@@ -860,6 +860,47 @@ int gs_densify_move(int n_tensors, const void* const* src, void* const* dst, con
                     const int32_t* grad_accum_count, const void* random_samples, int n_split, int samples,
                     int sample_base, float split_scale_factor, void* stream);
 
+/* ---- MCMC densification (ABI 17; no reference counterpart) --------------------------------------------------------
+ * The device side of "3D Gaussian Splatting as Markov Chain Monte Carlo" (gaussian_splatting_amd/densify.py:
+ * MCMCController): training at a fixed budget of Gaussians, dead ones relocated onto live ones, positions perturbed by
+ * covariance-shaped noise every iteration.  All tensors fp32. */
+#define GS_MCMC_MAX_RATIO 51   /* a Gaussian sampled more often is corrected as one of 51 copies */
+/* Relocation, IN PLACE and many-to-one: up to 8 tensors params[k] of [n_rows, width[k]] floats with their Adam moments
+ * (exp_avg[k] / exp_avg_sq[k]: both NULL when the tensor has no state yet).  kind[k]: 0 plain, 2 scale (log, width 3)
+ * as in gs_densify_move, 4 opacity (logit, width 1); exactly one opacity and one scale tensor, else GS_EINVAL with a
+ * gs_last_error() text.  ratio[r] = 1 + the number of times row r was drawn as a source.  Two launches, one after the
+ * other on `stream`, no temporary buffer, no address written by two threads:
+ *   A  every row r with ratio[r] > 1, n = min(ratio[r], GS_MCMC_MAX_RATIO), x its opacity logit:
+ *        o         = min(1 / (1 + exp(-x)), 1 - 2^-24)
+ *        o_new     = 1 - (1 - o)^(1/n)
+ *        denom     = sum_{i=1..n} sum_{k=0..i-1} C(i-1,k) (-1)^k o_new^(k+1) / sqrt(k+1)
+ *        scale[c] += log(o / denom)                                          c = 0..2
+ *        opacity   = logit(min(max(o_new, min_opacity), 1 - 2^-24))
+ *      evaluated in double and rounded once to fp32 (fp32 loses up to four digits of the alternating sum); both
+ *      moments of the row become 0 in every tensor that has them.  A row with ratio[r] <= 1 is neither read nor
+ *      written: every bit of it stays, NaN payloads included.
+ *   B  for every m < M, row src_rows[m] (as A left it) is copied to row dst_rows[m] in every tensor and the moments of
+ *      the destination row become 0.
+ * Preconditions, documented and not checked: the dst_rows are distinct, no destination row is a source, every
+ * src_rows[m] has ratio > 1, all rows are in [0, n_rows).  M == 0 or n_rows == 0 returns GS_OK without a launch;
+ * ratio, dst_rows and src_rows may be NULL only then. */
+int gs_mcmc_relocate(int n_tensors, void* const* params, void* const* exp_avg, void* const* exp_avg_sq,
+                     const int32_t* width, const int32_t* kind, int n_rows, const int32_t* ratio /*[n_rows]*/,
+                     const int32_t* dst_rows /*[M]*/, const int32_t* src_rows /*[M]*/, int M,
+                     float min_opacity, void* stream);
+/* The position noise of every iteration, one launch, xyz[N,3] modified in place:
+ *   o    = 1 / (1 + expf(-opacity))                           opacity[N,1] logits
+ *   gate = 1 / (1 + expf(-gate_k * ((1 - o) - gate_x0)))      ~1 for a nearly transparent Gaussian, ~0 for a solid one
+ *   S    = Sigma_world(quaternion, scale)                     as gs_compute_sigma_world: q normalised, exp(scale)
+ *   e    = noise * (gate * step)                              noise[N,3]: the caller's standard normal samples
+ *   xyz[r] += (S[3r] * e0 + S[3r+1] * e1) + S[3r+2] * e2      r = 0..2
+ * in fp32 with the roundings as written (no contraction); expf is the library's IEEE-only exponential, so the result
+ * is a function of the inputs' bits.  68 bytes per Gaussian, 56 read and 12 written.  quaternion must be 16-byte
+ * aligned.  N == 0 launches nothing. */
+int gs_mcmc_add_noise(void* xyz, const void* quaternion, const void* scale, const void* opacity,
+                      const void* noise /*[N,3]*/, int N, float step, float gate_k, float gate_x0,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
