@@ -82,7 +82,11 @@ class DensityController:
         self.grad_accum_count = torch.zeros(n, dtype=torch.int32, device=xyz.device)
 
     def accumulate(self, uv_grad, culling_mask, camera):
-        """the densification statistics of one training iteration (call after backward)"""
+        """the densification statistics of one training iteration (call after backward).
+        uv_grad: any [V, 2] tensor of the frame's visible Gaussians -- uv.grad, or in its place the uv_absgrad of
+        fused.rasterize(..., absgrad=True) (AbsGS: the per-pixel magnitudes, which do not cancel for a large Gaussian
+        with detail on both sides of its centre).  Either way |K-scaled value| is accumulated; a fixed
+        uv_grad_threshold has to be raised for absgrad, the percentile mode adapts by itself."""
         accumulate_grad_stats(uv_grad, culling_mask, self.gaussians.xyz.grad, camera, self.uv_grad_accum,
                               self.xyz_grad_accum, self.grad_accum_count)
 

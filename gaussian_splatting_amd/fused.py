@@ -7,7 +7,7 @@ Two autograd nodes instead of six-plus-glue:
 
     _Preprocess   gs_preprocess_forward + tile binning + per-tile sort   (parameters -> uv, conic,
                   opacity, colour)
-    _Render       gs_render_tiles_prefix (_packed) / gs_render_tiles_backward_slab
+    _Render       gs_render_tiles_prefix (_packed) / gs_render_tiles_backward_slab (_abs: rasterize(absgrad=True))
 
 Both get the frame record (_frame_record) as a non-tensor argument: the frame's options from the entry point and, after
 _Preprocess.forward, what is not differentiable (packed records, tile lists, culling mask, an early render).  Every entry
@@ -625,13 +625,16 @@ def render_forward(packed, rgb, ranges, sorted_g, keys, background_rgb, height, 
 
 
 def render_backward(packed, rgb, ranges, sorted_g, background_rgb, nsp, fw, grad_image, height, width, tile_rows,
-                    V, tile_cost=None, backward_mode=None, seg_state=None, cut=None, tail=0):
+                    V, tile_cost=None, backward_mode=None, seg_state=None, cut=None, tail=0, uv_absgrad=None):
     """-> the slab [V, 9] of accumulated render gradients (rgb 3 | opacity 1 | uv 2 | conic 3).
     tail > 0 (rasterize_rgbd): -> (slab, float[tail]); the tail lies behind the slab's rows in the same allocation and
     is cleared by the same prologue launch.  grad_image None: the slab is cleared and no colour backward runs.
     tile_cost: render_forward's fourth output (the tiles are then started longest-first).
     seg_state: render_forward's fifth output; non-empty -> one workgroup per (tile, depth segment).
-    backward_mode: _hip.GS_BACKWARD_COMPAT / _EXACT, per call (ABI 5); None = the process default at the call"""
+    backward_mode: _hip.GS_BACKWARD_COMPAT / _EXACT, per call (ABI 5); None = the process default at the call
+    uv_absgrad: float32 [max(V, 1), 2] -> cleared here, and the colour backward is gs_render_tiles_backward_slab_abs
+    (ABI 18), which next to the slab leaves there the per-pixel magnitudes of the uv gradient's terms (AbsGS); the same
+    walk under the same order / segment / cut arguments"""
     nty = _tile_grid(width, height)[1]
     row0, row1 = tile_rows if tile_rows is not None else (0, nty)
     # (cleared by the call itself, in the launch that also orders the tiles: zero_slab_rows)
@@ -648,12 +651,18 @@ def render_backward(packed, rgb, ranges, sorted_g, background_rgb, nsp, fw, grad
     # one prologue launch (clear the slab + order the tiles), then the render kernel alone in its entry
     _hip.call("gs_render_backward_prologue", _p(slab), slab.shape[0], _p(cost), _p(order), width, height, row0, row1,
               _stream())
+    if uv_absgrad is not None:
+        uv_absgrad.zero_()   # the sums of THIS backward (the entry accumulates)
     if grad_image is not None:
-        _hip.call("gs_render_tiles_backward_slab", _p(packed), _p(rgb), _p(ranges), _p(sorted_g), _p(background_rgb),
-                  _p(nsp), _p(fw), _p(grad_image), width, height, row0, row1, _p(slab), 0, None, _p(order),
-                  _p(seg_state) if seg_on else None, _p(cut.flags) if cut is not None else None,
-                  _p(cut.full_ranges) if cut is not None else None, _p(cut.overflow_sorted) if cut is not None else None,
-                  _hip.GS_BACKWARD_DEFAULT if backward_mode is None else int(backward_mode), _stream())
+        walk = (_p(packed), _p(rgb), _p(ranges), _p(sorted_g), _p(background_rgb),
+                _p(nsp), _p(fw), _p(grad_image), width, height, row0, row1, _p(slab), 0, None, _p(order),
+                _p(seg_state) if seg_on else None, _p(cut.flags) if cut is not None else None,
+                _p(cut.full_ranges) if cut is not None else None, _p(cut.overflow_sorted) if cut is not None else None,
+                _hip.GS_BACKWARD_DEFAULT if backward_mode is None else int(backward_mode))
+        if uv_absgrad is None:
+            _hip.call("gs_render_tiles_backward_slab", *walk, _stream())
+        else:
+            _hip.call("gs_render_tiles_backward_slab_abs", *walk, None, _p(uv_absgrad), _stream())
     if tail:
         return slab[:V], slab.view(-1)[rows * SLAB_WIDTH:rows * SLAB_WIDTH + tail]
     return slab[:V]
@@ -753,7 +762,7 @@ def _as_slab(g_uv, g_conic, g_opa, g_rgb, V, dev):
 # ---------------------------------------------------------------------------------------------------
 def _frame_record(width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, tile_rows=None, sort_prefix=0,
                   background=None, pose_grad=False, adam_plan=None, antialiased=False, z_out=False, may_cut=False,
-                  slab_sync=None):
+                  slab_sync=None, absgrad=False):
     """What one frame's two nodes share and autograd does not differentiate: the frame's options, set here by the entry
     point, and -- filled by _Preprocess.forward -- the stage record's tensors the render and the caller read.  Handed
     to both nodes as a non-tensor argument.  The differentiable outputs are not kept on it (that would tie the record to
@@ -768,11 +777,14 @@ def _frame_record(width, height, near_thresh, far_thresh, cull_mask_padding, mh_
     the record), so the gradient that comes back for it is dL/d(sigmoid * comp) and the backward folds it
     may_cut: the frame may take the depth cut (want_depth_cut decides); its record, what _Render's two passes need,
     is then left in `cut`
-    slab_sync: see rasterize()"""
+    slab_sync: see rasterize()
+    absgrad: rasterize(absgrad=True) -- the entry point leaves a float32 [max(V, 1), 2] buffer in `uv_absgrad` and
+    _Render's colour backward fills it (render_backward)"""
     return SimpleNamespace(
         width=width, height=height, near_thresh=near_thresh, far_thresh=far_thresh, cull_mask_padding=cull_mask_padding,
         mh_dist=mh_dist, tile_rows=tile_rows, sort_prefix=sort_prefix, background=background, pose_grad=pose_grad,
         adam_plan=adam_plan, antialiased=bool(antialiased), z_out=z_out, may_cut=may_cut, slab_sync=slab_sync,
+        absgrad=bool(absgrad), uv_absgrad=None,
         # after _Preprocess.forward (xyz_cam and vis_idx: the V visible rows)
         packed=None, xyz_cam=None, culling_mask=None, ranges=None, sorted_g=None, vis_idx=None, keys=None, cut=None,
         rendered=None)   # (image, nsp, fw, cost, seg) when _Preprocess.forward already enqueued _Render's kernels
@@ -935,7 +947,8 @@ class _Render(torch.autograd.Function):
         n_tail = policy.tail(V) if policy is not None else 0
         out = render_backward(packed, rgb, ranges, sorted_g, background_rgb, nsp, fw,
                               grad_image.contiguous() if grad_image is not None else None, fr.height, fr.width,
-                              fr.tile_rows, V, cost, ctx.backward_mode, seg, cut=fr.cut, tail=n_tail)
+                              fr.tile_rows, V, cost, ctx.backward_mode, seg, cut=fr.cut, tail=n_tail,
+                              uv_absgrad=fr.uv_absgrad)
         slab, tail = out if n_tail else (out, None)
         g_channels = None
         if policy is not None:
@@ -1130,7 +1143,7 @@ def _begin_frame(gaussians, sh, camera_T_world, camera, near_thresh, far_thresh,
 
 def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
               use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None, slab_sync=None,
-              frame_hook=None, adam_plan=None, antialiased=False):
+              frame_hook=None, adam_plan=None, antialiased=False, absgrad=False):
     """tile_rows=(row0, row1) restricts binning and rendering to those tile rows; slab_sync(flat) is
     called on the flat [9 V] render-gradient slab in the backward (grad_sync is the generic
     per-tensor form used by the reference-shaped path): the hooks gaussian_splatting_amd.sharded
@@ -1140,8 +1153,23 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
     antialiased=True multiplies every splat's opacity by sqrt(det Sigma_2D / det(Sigma_2D + 0.25 I)), so that the 0.25 px^2
     dilation of the fp32 record no longer adds light to splats smaller than a pixel, and differentiates through the
     factor: whole single-GPU fp32 frames without hooks or adam_plan in the SH-precompute colour mode,
-    anything else raises RuntimeError before a kernel is enqueued."""
+    anything else raises RuntimeError before a kernel is enqueued.
+    absgrad=True (AbsGS, gsplat's absgrad) returns a fourth value,
+
+        image, culling_mask, uv, uv_absgrad = rasterize(..., absgrad=True)
+
+    with image, culling_mask and uv those of the plain call, bit for bit.  uv_absgrad is float32 [V, 2] without a
+    gradient: zero until the image's backward has run, then for every visible Gaussian the sum over pixels and list
+    entries of |dL/du|, |dL/dv| of that pixel's visit -- the magnitudes of the very terms whose signed sum is uv.grad --
+    of the MOST RECENT backward (a second backward over a retained graph overwrites).  Hand it to
+    densify.DensityController.accumulate in place of uv.grad: per-pixel gradients of opposite sign cancel in uv.grad
+    for exactly the large Gaussians that need splitting, and add here.  Served like antialiased=True (which combines
+    freely), on the Python orchestration -- the native frame has no such node -- with the depth cut, depth segments and
+    longest-first order under their usual policies; anything else raises RuntimeError before a kernel is enqueued."""
     hooks = return_aux or grad_sync or slab_sync or frame_hook
+    if absgrad:
+        _refuse("rasterize(absgrad=True)", gaussians, camera_T_world, camera, use_sh_precompute, background_rgb,
+                (tile_rows is not None, hooks), adam_plan)
     if antialiased:
         _refuse("rasterize(antialiased=True)", gaussians, camera_T_world, camera, use_sh_precompute, background_rgb,
                 (tile_rows is not None, hooks), adam_plan)
@@ -1162,7 +1190,7 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
                                            tile_rows=tile_rows, grad_sync=grad_sync)
     g = gaussians
     validate(g, camera_T_world, camera, background_rgb)
-    nat = native() if not hooks else None
+    nat = native() if not (hooks or absgrad) else None
     if nat is not None:
         nat.set_modes(bool(SORT_PREFIX), bool(EARLY_RENDER))
         nat.set_segments(0 if SEGMENTS == "auto" else (1 if SEGMENTS else -1))
@@ -1179,7 +1207,10 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
     fr, (uv, conic, opacity, rgb) = _begin_frame(
         g, g.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist, background_rgb,
         adam_plan=adam_plan, tile_rows=tile_rows, sort_prefix=_hip.GS_SORT_PREFIX if (SORT_PREFIX and not return_aux) else 0,
-        pose_grad=not (grad_sync or slab_sync), antialiased=antialiased, may_cut=not hooks, slab_sync=slab_sync)
+        pose_grad=not (grad_sync or slab_sync), antialiased=antialiased, may_cut=not hooks, slab_sync=slab_sync,
+        absgrad=absgrad)
+    if absgrad:   # (a row even when nothing is visible: an empty tensor has no address to hand to the entry)
+        fr.uv_absgrad = torch.zeros(max(uv.shape[0], 1), 2, dtype=torch.float32, device=uv.device)
     if frame_hook is not None:   # multi-GPU cost-balanced bands: the band's tile ranges
         frame_hook(dict(ranges=fr.ranges, ntx=_tile_grid(fr.width, fr.height)[0]))
     image = _Render.apply(uv, conic, opacity, rgb, None, fr, None)
@@ -1187,6 +1218,8 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
         return image, fr.culling_mask, uv, dict(conic=conic, opacity=opacity, rgb=rgb, packed=fr.packed,
                                                 xyz_camera_frame=fr.xyz_cam, tile_ranges=fr.ranges,
                                                 sorted_gaussians=fr.sorted_g, vis_idx=fr.vis_idx)
+    if absgrad:
+        return image, fr.culling_mask, uv, fr.uv_absgrad[:uv.shape[0]]
     return image, fr.culling_mask, uv
 
 

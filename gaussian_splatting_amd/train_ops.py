@@ -361,7 +361,9 @@ def accumulate_grad_stats(uv_grad, culling_mask, xyz_grad, camera, uv_grad_accum
         uv_grad_accum[~culling_mask] += |uv_grad|; xyz_grad_accum += |xyz.grad|
         grad_accum_count += (~culling_mask).int()
 
-    uv_grad: [V, 2] (any row stride, e.g. the view of the fused path's slab); it is NOT modified.
+    uv_grad: [V, 2] (any row stride, e.g. the view of the fused path's slab); it is NOT modified.  The uv_absgrad of
+    fused.rasterize(..., absgrad=True) goes here in place of uv.grad unchanged: it is already >= 0, the same scaling
+    and sums apply.
     The focal lengths are read from camera.K on the device (no host sync)."""
     N = culling_mask.shape[0]
     keep = ~culling_mask

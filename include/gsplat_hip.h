@@ -744,6 +744,26 @@ int gs_render_tiles_backward_slab_m(const void* packed, const void* rgb, const i
                                     const void* segment_state, const int32_t* cut_flags, const int32_t* full_ranges,
                                     const int32_t* overflow_sorted, int backward_mode, const uint64_t* touch_masks,
                                     void* stream);
+/* The absgrad form of gs_render_tiles_backward_slab_m (ABI 18; AbsGS, gsplat's absgrad=True): the same walk in every
+ * mode -- tile order, depth segments, depth-cut overflow lists, handed-over touch masks, compat and exact backward
+ * modes, the prologue conventions of zero_slab_rows / tile_cost / tile_order -- and the same nine sums into
+ * grad_slab[V, 9].  Next to them it accumulates, per Gaussian, the per-pixel MAGNITUDES of the terms whose signed sum is
+ * the slab's uv pair: with g_u(p, k), g_v(p, k) the contribution of pixel p's visit of list entry k to grad_u, grad_v,
+ *   grad_uv_abs[g, 0] += sum |g_u(p, k)|,   grad_uv_abs[g, 1] += sum |g_v(p, k)|
+ * over the (pixel, entry) pairs the colour backward adds up (same contribute / stop / background decisions, alpha
+ * capped at 0.9999 the same way, the reference's Q1 weight quirk in compat mode the same way), so that
+ * grad_uv_abs[g, j] >= |grad_slab[g, 4 + j]| up to rounding.  Opposite-signed terms of a large Gaussian cancel in the
+ * slab and add here: the densification signal that does not miss such Gaussians.
+ * grad_uv_abs: float32 [V, 2], ACCUMULATED onto -- the caller clears it (zero_slab_rows covers the slab only); rows of
+ * Gaussians no pixel used are not touched.  NULL returns GS_EINVAL.  fp32, one colour coefficient per channel. */
+int gs_render_tiles_backward_slab_abs(const void* packed, const void* rgb, const int32_t* tile_ranges,
+                                      const int32_t* sorted_gaussians, const void* background_rgb,
+                                      const int32_t* num_splats_per_pixel, const void* final_weight_per_pixel,
+                                      const void* grad_image, int W, int H, int tile_row0, int tile_row1, void* grad_slab,
+                                      int64_t zero_slab_rows, const int32_t* tile_cost, int32_t* tile_order,
+                                      const void* segment_state, const int32_t* cut_flags, const int32_t* full_ranges,
+                                      const int32_t* overflow_sorted, int backward_mode, const uint64_t* touch_masks,
+                                      void* grad_uv_abs, void* stream);
 
 /* ---- multi-GPU: the fused band frontend (ABI 8; no reference counterpart) --------------------------------------
  * gs_band_frontend = gs_band_project + gs_halo_plan_masked + gs_preprocess_forward_list in four launches instead of
