@@ -56,7 +56,8 @@
 // forward walk and one backward walk with its flush, render_map_fwd / render_map_bwd, templated on a channel policy
 // that holds what a family has of its own: where the channel values come from and where their sums and gradients go.
 // The depth distortion (k_render_distortion_fwd / _bwd) is the depth map's walk with two more sums: its forward is a
-// policy of render_map_fwd, its backward, whose c_k needs w_k, has a walk body of its own.
+// policy of render_map_fwd, its backward a policy of render_map_bwd (DistortionBwd, whose c_k needs w_k: the c() hook
+// is handed what forms it).
 //
 // Numerics.  The fp32 forward is bit-identical to the CPU restatement: same operation order and
 // operand precisions as render.cu (including its double-literal promotions), the IEEE quotient (formed
@@ -2156,8 +2157,14 @@ __device__ __forceinline__ void render_map_fwd(
 //   stage(sorted, first, cnt, tid, s_geom, s_idx)   as the forward's
 //   load(p)                                         the pixel's incoming map gradient (pixels outside the image: zeros)
 //   begin(lane, wave)                               once the tile is known to have work
-//   c(ga, g2, i)                                    c_k of staged entry i (g2: words 8..11 of its record)
-//   column0(aT)                                     the contributing lane's input to sum 0, from w_k = alpha_k T_k
+//   c(ga, g2, i, alpha, T, r1ma)                    c_k of staged entry i (g2: words 8..11 of its record).  alpha: the
+//                                                   capped alpha_k, T: the transmittance BEHIND the entry, r1ma:
+//                                                   1 / (1 - alpha_k) -- a policy whose c_k depends on w_k forms it as
+//                                                   alpha * (T * r1ma), the expression of the walk's own w_k, which
+//                                                   is formed after the call (moving the call below it reorders
+//                                                   every instantiation; profiles/r17/map_bwd_isa.txt)
+//   column0(aT)                                     the contributing lane's input to sum 0, from w_k = alpha_k T_k;
+//                                                   called after c() of the same entry
 //   visited(aT, g)                                  after the slot of an entry (Gaussian g) is written; aT = 0 in lanes
 //                                                   that did not contribute
 //   send(g, col, x)                                 the sum x of column col < 3 of Gaussian g's row, to where it belongs
@@ -2224,7 +2231,7 @@ __device__ __forceinline__ void render_map_bwd(
                 float alpha = v.alpha;
                 if (alpha > Thr<float>::sat_gt()) alpha = Thr<float>::alpha_cap();   // min(0.9999, .)
                 const float r1ma = fast_rcp(1.0f - alpha);
-                const float c = ch.c(ga, g2, i);
+                const float c = ch.c(ga, g2, i, alpha, T, r1ma);
                 T = T * r1ma;                        // T_k: the transmittance in front of the entry
                 aT = alpha * T;                      // w_k
                 const float dalpha = T * c - S * r1ma;
@@ -2301,7 +2308,9 @@ struct DepthBwd : DepthChannel {
         if (g_depth != nullptr) gd = g_depth[p];
     }
     __device__ __forceinline__ void begin(int, int) const {}
-    __device__ __forceinline__ float c(float ga, const Vec4<float>& g2, int) const { return __builtin_fmaf(gd, g2.y, ga); }
+    __device__ __forceinline__ float c(float ga, const Vec4<float>& g2, int, float, float, float) const {
+        return __builtin_fmaf(gd, g2.y, ga);
+    }
     __device__ __forceinline__ float column0(float aT) const { return gd * aT; }
     __device__ __forceinline__ void visited(float, int) const {}
     __device__ __forceinline__ void send(int g, int col, float x) const {
@@ -2377,16 +2386,55 @@ __global__ __launch_bounds__(RB) void k_render_distortion_fwd(
 }
 
 // The true derivative of distortion, depth and alpha together (decisions held constant, alpha above 0.9999 as 0.9999,
-// no walk quirk), back to front like render_map_bwd.  c_k of the distortion needs w_k, which render_map_bwd's c() hook
-// is called before, so the kernel has its OWN walk body (render_map_bwd keeps its ISA); what differs from that walk is
-// marked.  The suffix sums A_>k = sum_{j>k} w_j and D_>k = sum_{j>k} w_j z_j are carried, the prefixes come from the
-// forward's totals alpha[p] and depth[p]:
+// no walk quirk): a policy of render_map_bwd like DepthBwd.  c_k of the distortion needs w_k, which the walk forms after
+// it has called c(); the hook's arguments alpha, T and 1 / (1 - alpha) let the policy form it with the walk's own
+// expression (one value in the ISA).  The suffix sums A_>k = sum_{j>k} w_j and D_>k = sum_{j>k} w_j z_j are carried, the
+// prefixes come from the forward's totals alpha[p] and depth[p]:
 //   A_<k = alpha[p] - A_>k - w_k      D_<k = depth[p] - D_>k - w_k z_k
 //   e_k = 2 [z_k (A_<k - A_>k) - D_<k + D_>k]                        (d distortion / d w_k)
 //   c_k = fma(g_dist, e_k, fma(g_depth, z_k, g_alpha))               (g_dist = 0: the depth kernel's c_k, bit for bit)
 //   dL/dz_k = g_depth w_k + g_dist 2 w_k (A_<k - A_>k)               (sum 0 of the slot, to grad_z)
 // then dL/dalpha_k = T_k c_k - S / (1 - alpha_k), S = fma(w_k, c_k, S) and the chain to opacity, u, v, conic, the nine
-// sums, the slots and the flush exactly as render_map_bwd has them.
+// sums, the slots and the flush are the walk's.
+struct DistortionBwd : DepthChannel {
+    const float* __restrict__ depth_in;
+    const float* __restrict__ alpha_in;
+    const float* __restrict__ g_dist;
+    const float* __restrict__ g_depth;
+    float* __restrict__ grad_z;
+    float gx = 0.0f, gd = 0.0f;
+    float A_tot = 0.0f, D_tot = 0.0f;   // the forward's totals of the pixel
+    float A_gt = 0.0f, D_gt = 0.0f;     // sums of w_j and of w_j z_j over the contributors behind the current entry
+    float dA = 0.0f;                    // A_<k - A_>k of the entry, from c() to column0()
+    __device__ __forceinline__ void load(size_t p) {
+        // (the gradients first, the totals last: with the totals first the kernel measured 1.5 % slower at workload D,
+        // the instructions of the visit loop being the same; profiles/r17/README.md)
+        if (g_dist != nullptr) gx = g_dist[p];
+        if (g_depth != nullptr) gd = g_depth[p];
+        A_tot = alpha_in[p];
+        D_tot = depth_in[p];
+    }
+    __device__ __forceinline__ void begin(int, int) const {}
+    __device__ __forceinline__ float c(float ga, const Vec4<float>& g2, int, float alpha, float T, float r1ma) {
+        const float z = g2.y;
+        const float aT = alpha * (T * r1ma);   // w_k, the walk's expression
+        const float wz = aT * z;
+        const float A_lt = A_tot - A_gt - aT;
+        const float D_lt = D_tot - D_gt - wz;
+        dA = A_lt - A_gt;
+        const float e = 2.0f * (z * dA - D_lt + D_gt);
+        A_gt += aT;
+        D_gt += wz;
+        return __builtin_fmaf(gx, e, __builtin_fmaf(gd, z, ga));
+    }
+    __device__ __forceinline__ float column0(float aT) const { return __builtin_fmaf(gx, 2.0f * aT * dA, gd * aT); }
+    __device__ __forceinline__ void visited(float, int) const {}
+    __device__ __forceinline__ void send(int g, int col, float x) const {
+        if (col == 0) global_add(grad_z + g, x);
+    }
+    __device__ __forceinline__ void finish() const {}
+};
+
 __global__ __launch_bounds__(RB) void k_render_distortion_bwd(
     const float* __restrict__ packed, const float* __restrict__ xyz_cam, const int* __restrict__ ranges,
     const int* __restrict__ sorted, const int* __restrict__ nsp_in, const float* __restrict__ t_in,
@@ -2399,118 +2447,9 @@ __global__ __launch_bounds__(RB) void k_render_distortion_bwd(
     __shared__ int s_max[4];
     __shared__ unsigned long long s_mask[4][1];
     __shared__ unsigned long long s_hit[4][1];       // slots written by each wave
-    constexpr int SV = 9;
-    constexpr int RCHUNK = MAP_BWD_CHUNK;
-    const int t_local = tile_of_block(blockIdx.x, nt);
-    if (t_local >= nt) return;
-    const int tile = tile0 + t_local;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const PixelMap px = pixel_of_thread(tile % ntx, tile / ntx, tid);
-    const bool valid = px.u < W && px.v < H;
-    const int s0 = ranges[tile];
-    const int n_tile = ranges[tile + 1] - s0;
-    if (n_tile <= 0) return;
-    int nsp = 0;
-    float T = 1.0f, ga = 0.0f, gd = 0.0f, gx = 0.0f;
-    float A_tot = 0.0f, D_tot = 0.0f;   // the forward's totals of the pixel
-    if (valid) {
-        const size_t p = (size_t)px.v * W + px.u;
-        nsp = nsp_in[p];
-        T = t_in[p];
-        A_tot = alpha_in[p];
-        D_tot = depth_in[p];
-        if (g_dist != nullptr) gx = g_dist[p];
-        if (g_depth != nullptr) gd = g_depth[p];
-        if (g_alpha != nullptr) ga = g_alpha[p];
-    }
-    int n_used, wave_used;
-    zalpha_reach(nsp, n_tile, tid, s_max, n_used, wave_used);
-    if (n_used <= 0) return;
-    const float pu = float(px.u), pv = float(px.v);
-    const int slot_off = slot_lane_offset(lane);
-    const bool slot_stores = slot_off >= 0;
-    const int slot_lane_base = wave * RCHUNK * SV + (slot_stores ? slot_off : 0);
-    const DepthChannel ch{xyz_cam};
-    float S = 0.0f;                   // sum of alpha_j T_j c_j over the contributors behind the current entry
-    float A_gt = 0.0f, D_gt = 0.0f;   // sums of w_j and of w_j z_j over them
-    for (int chunk = (n_used - 1) / RCHUNK; chunk >= 0; chunk--) {
-        const int base = chunk * RCHUNK;
-        const int cnt = min(RCHUNK, n_used - base);
-        __syncthreads();   // previous chunk fully flushed
-        stage_chunk<float, 1>(packed, nullptr, sorted, s0 + base, cnt, tid, s_geom, nullptr, s_idx);
-        ch.stage(sorted, s0 + base, cnt, tid, s_geom, s_idx);
-        // (no barrier in between: thread t tests the record thread t staged)
-        build_touch_masks<float, RCHUNK>(s_geom, cnt, tid, tile % ntx, tile / ntx, s_mask);
-        __syncthreads();
-        unsigned long long m = wave_uniform(s_mask[wave][0]);
-        unsigned long long hit = 0;   // the entries of this chunk whose slot the wave wrote
-        while (m) {
-            const int i = 63 - __builtin_clzll(m);
-            m &= ~(1ull << i);
-            const int k = base + i;
-            if (k >= wave_used) continue;   // wave-uniform: no pixel of the patch walked this far
-            const float* rec = s_geom + i * GS_PACKED_WIDTH;
-            const Vec4<float> g0 = *reinterpret_cast<const Vec4<float>*>(rec);       // u v r2 opacity
-            const Vec4<float> g1 = *reinterpret_cast<const Vec4<float>*>(rec + 4);   // a b c det
-            const Vec4<float> g2 = *reinterpret_cast<const Vec4<float>*>(rec + 8);   // 1/det, z (depth)
-            const ZalphaVisit v = zalpha_alpha(g0, g1, g2.x, pu, pv, k < nsp);
-            if (ballot(v.contrib) == 0) continue;   // every reaching lane skipped the entry
-            float v0 = 0.0f, w = 0.0f;
-            if (v.contrib) {
-                float alpha = v.alpha;
-                if (alpha > Thr<float>::sat_gt()) alpha = Thr<float>::alpha_cap();   // min(0.9999, .)
-                const float r1ma = fast_rcp(1.0f - alpha);
-                const float z = g2.y;
-                T = T * r1ma;                        // T_k: the transmittance in front of the entry
-                const float aT = alpha * T;          // w_k
-                // (the distortion's part: prefixes from the totals, e_k, and the z column)
-                const float wz = aT * z;
-                const float A_lt = A_tot - A_gt - aT;
-                const float D_lt = D_tot - D_gt - wz;
-                const float dA = A_lt - A_gt;
-                const float e = 2.0f * (z * dA - D_lt + D_gt);
-                const float c = __builtin_fmaf(gx, e, __builtin_fmaf(gd, z, ga));
-                const float dalpha = T * c - S * r1ma;
-                S = __builtin_fmaf(aT, c, S);
-                v0 = __builtin_fmaf(gx, 2.0f * aT * dA, gd * aT);
-                A_gt += aT;
-                D_gt += wz;
-                w = v.norm_prob * dalpha;
-            }
-            float val[9];
-            const float du2 = v.du * v.du, dv2 = v.dv * v.dv, duv = v.du * v.dv;
-            val[0] = v0; val[1] = 0.0f; val[2] = 0.0f;
-            val[3] = w; val[4] = w * v.du; val[5] = w * v.dv;
-            val[6] = (dv2 - g1.z * v.mh) * w;
-            val[7] = (g1.y * v.mh - duv) * w;
-            val[8] = (du2 - g1.x * v.mh) * w;
-            int slot_i = i * SV;
-            asm volatile("" : "+s"(slot_i));
-            reduce9_to_slot(val, slot_stores, s_acc, slot_lane_base + slot_i);
-            hit |= 1ull << i;
-        }
-        if (lane == 0) s_hit[wave][0] = hit;
-        __syncthreads();
-        // (the flush's thread index is formed inside the chunk loop, as in render_map_bwd)
-        int row_tid = tid;
-        asm volatile("" : "+v"(row_tid));
-        flush_sum_slots<RCHUNK, SV>(s_acc, s_geom, s_hit, row_tid, cnt);
-        __syncthreads();
-        // nine lanes = one row (seven rows per wave instruction, see k_render_bwd)
-        const int sub = lane / SV, col = lane - sub * SV;   // lane 63: idle
-        for (int r0 = wave * 7; r0 < cnt; r0 += 28) {
-            const int r = r0 + sub;
-            const bool in = lane < 63 && r < cnt;
-            const float x = in ? s_acc[r * SV + col] : 0.0f;
-            const unsigned long long nz = ballot(x != 0.0f);
-            const bool any = in && ((nz >> (sub * SV)) & 0x1ffull) != 0;
-            if (any) {
-                const int g = s_idx[r];
-                if (col >= 3) global_add(slab + (size_t)g * SV + col, x);
-                else if (col == 0) global_add(grad_z + g, x);
-            }
-        }
-    }
+    DistortionBwd ch{{xyz_cam}, depth_in, alpha_in, g_dist, g_depth, grad_z};
+    render_map_bwd(ch, packed, ranges, sorted, nsp_in, t_in, g_alpha, W, H, ntx, tile0, nt, slab, s_geom, s_idx, s_acc,
+                   s_max, s_mask, s_hit);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2670,7 +2609,7 @@ struct FeaturesBwd : FeatureRows<CP> {
             __builtin_amdgcn_wave_barrier();
         }
     }
-    __device__ __forceinline__ float c(float ga, const Vec4<float>&, int i) const {
+    __device__ __forceinline__ float c(float ga, const Vec4<float>&, int i, float, float, float) const {
         float c = ga;
         const Vec4<float>* f4 = reinterpret_cast<const Vec4<float>*>(this->s_feat + i * CP);
 #pragma unroll
@@ -3352,41 +3291,21 @@ static int launch_bwd_slab(const char* name, const void* packed, const void* rgb
     if (order_given && zero_slab_rows > 0)
         if (int e = launch_bwd_prologue(grad_slab, zero_slab_rows, nullptr, nullptr, ntx, tile_row0, nt, s)) return e;
     if (nt == 0) return check_launch(name);
-    if (segment_state != nullptr) {
-        // (tile, depth segment) work items from the state the forward left (gs_render_tiles_prefix / _packed
-        // with the same segment_state); segment-major launch order = most work first, no order kernel
-        if constexpr (ABS) {
-            k_render_bwd_abs<<<grid * SEG_MAX, RB, 0, s>>>(
-                (const float*)packed, (const float*)rgb, nullptr, tile_ranges, sorted_gaussians,
-                (const float*)background_rgb, num_splats_per_pixel, (const float*)final_weight_per_pixel,
-                (const float*)grad_image, W, H, ntx, tile_row0 * ntx, nt, (float*)grad_slab, nullptr,
-                nullptr, nullptr, 1, exact, nullptr, nullptr, nullptr, seg_state_of((void*)segment_state, W, H, tile_row0, tile_row1),
-                cut_flags, full_ranges, overflow_sorted, (const unsigned long long*)touch_masks, (float*)grad_uv_abs);
-            return check_launch(name);
-        }
-        k_render_bwd<float, 1><<<grid * SEG_MAX, RB, 0, s>>>(
-            (const float*)packed, (const float*)rgb, nullptr, tile_ranges, sorted_gaussians,
-            (const float*)background_rgb, num_splats_per_pixel, (const float*)final_weight_per_pixel,
-            (const float*)grad_image, W, H, ntx, tile_row0 * ntx, nt, (float*)grad_slab, nullptr,
-            nullptr, nullptr, 1, exact, nullptr, nullptr, nullptr, seg_state_of((void*)segment_state, W, H, tile_row0, tile_row1),
-            cut_flags, full_ranges, overflow_sorted, (const unsigned long long*)touch_masks);
-        return check_launch(name);
-    }
-    if constexpr (ABS) {
-        k_render_bwd_abs<<<grid, RB, GS_BWD_LDS_PAD, s>>>(
+    // One launch for the four cases.  With segment_state: (tile, depth segment) work items from the state the forward
+    // left (gs_render_tiles_prefix / _packed with the same segment_state); segment-major launch order = most work first,
+    // no order kernel (use_order is false), no LDS padding.  tail: what the kernel takes after touch_masks.
+    const bool segmented = segment_state != nullptr;
+    auto launch = [&](auto kernel, auto... tail) {
+        kernel<<<segmented ? grid * SEG_MAX : grid, RB, segmented ? 0 : GS_BWD_LDS_PAD, s>>>(
             (const float*)packed, (const float*)rgb, nullptr, tile_ranges, sorted_gaussians,
             (const float*)background_rgb, num_splats_per_pixel, (const float*)final_weight_per_pixel,
             (const float*)grad_image, W, H, ntx, tile_row0 * ntx, nt, (float*)grad_slab, nullptr,
             nullptr, nullptr, 1, exact, use_order ? tile_order : nullptr, nullptr, nullptr,
-            SEG_NONE, cut_flags, full_ranges, overflow_sorted, (const unsigned long long*)touch_masks, (float*)grad_uv_abs);
-        return check_launch(name);
-    }
-    k_render_bwd<float, 1><<<grid, RB, GS_BWD_LDS_PAD, s>>>(
-        (const float*)packed, (const float*)rgb, nullptr, tile_ranges, sorted_gaussians,
-        (const float*)background_rgb, num_splats_per_pixel, (const float*)final_weight_per_pixel,
-        (const float*)grad_image, W, H, ntx, tile_row0 * ntx, nt, (float*)grad_slab, nullptr,
-        nullptr, nullptr, 1, exact, use_order ? tile_order : nullptr, nullptr, nullptr,
-        SEG_NONE, cut_flags, full_ranges, overflow_sorted, (const unsigned long long*)touch_masks);
+            segmented ? seg_state_of((void*)segment_state, W, H, tile_row0, tile_row1) : SEG_NONE,
+            cut_flags, full_ranges, overflow_sorted, (const unsigned long long*)touch_masks, tail...);
+    };
+    if constexpr (ABS) launch(k_render_bwd_abs, (float*)grad_uv_abs);
+    else launch(k_render_bwd<float, 1>);
     return check_launch(name);
 }
 
