@@ -128,6 +128,102 @@ __device__ inline void cam_grad_of(const T* c, T fx, T fy, const T* gJ6, const T
 }
 
 
+// ---- equidistant fisheye camera (GS_RASTER_FISHEYE; include/gsplat_hip.h "fisheye camera") ----
+// With c = (x, y, z) the camera-frame position (to_camera, as for the pinhole model):
+//     r2 = x x + y y      q = 1 / (r2 + z z)      r = sqrt(r2)      theta = atan2(r, z)
+//     s = theta / r                       (r2 == 0, the optical axis: s = 1 / z)
+//     a = (z q - s) / r2                  (d s / d x = a x,  d s / d y = a y,  d s / d z = -q)
+//     d = -(2 z q q + 3 a) / r2           (d a / d x = d x,  d a / d y = d y,  d a / d z = 2 q q)
+//     u = fx s x + cx     v = fy s y + cy
+//     J = [[fx (s + x x a),  fx x y a,        -fx x q],
+//          [fy x y a,        fy (s + y y a),  -fy y q]]
+// fp32, no contraction, IEEE divide and square root; atan2f is the device library's (no reference restatement exists
+// for this model; the fp64 yardstick of tests/fisheye_ref.py bounds it).
+// a and d cancel near the axis: z q -> s leaves a with an absolute error ~ 2^-24 / (z r2), harmless in J (a is
+// multiplied by x x, x y, y y) but not in the backward, whose terms 3 a x and x^3 d then carry a relative error
+// ~ 2^-24 z^2 / r2.  So for w = r2 / z^2 < 1/16 (theta < 14 degrees, the exact axis included) a and d are their series
+//     a z^3 = sum_{k>=1} (-1)^k 2k / (2k + 1) w^(k-1) = -2/3 + 4/5 w - 6/7 w^2 + ...          (eight terms)
+//     d z^5 / 2 = sum_{k>=2} (-1)^k 2k (k - 1) / (2k + 1) w^(k-2) = 4/5 - 12/7 w + 24/9 w^2 - ...   (seven terms)
+// in Horner form (truncation < 2^-24 of the sum), the limits a = -2 / (3 z^3), d = 8 / (5 z^5) at w = 0; beyond, the
+// closed forms are within ~1e-6 relative (the optical-axis rows of tests/test_gpu_fisheye.py).
+// The forward (is_culled, k_preprocess) and both backwards (k_preprocess_bwd, k_pose_bwd) call these functions.
+struct FisheyeTerms {
+    float s, a, q, d;
+};
+__device__ inline FisheyeTerms fisheye_terms_of(const float* c) {
+    FisheyeTerms t;
+    const float x = c[0], y = c[1], z = c[2];
+    const float r2 = x * x + y * y, z2 = z * z;
+    t.q = 1.0f / (r2 + z2);
+    if (r2 > 0.0f) {
+        const float r = __builtin_sqrtf(r2);
+        t.s = ::atan2f(r, z) / r;
+    } else {
+        t.s = 1.0f / z;
+    }
+    if (r2 < 0.0625f * z2) {
+        const float w = r2 / z2, z3 = z2 * z;
+        float fa = 16.0f / 17.0f, fd = 112.0f / 17.0f;
+        fa = fa * w + -14.0f / 15.0f;   fd = fd * w + -84.0f / 15.0f;
+        fa = fa * w + 12.0f / 13.0f;    fd = fd * w + 60.0f / 13.0f;
+        fa = fa * w + -10.0f / 11.0f;   fd = fd * w + -40.0f / 11.0f;
+        fa = fa * w + 8.0f / 9.0f;      fd = fd * w + 24.0f / 9.0f;
+        fa = fa * w + -6.0f / 7.0f;     fd = fd * w + -12.0f / 7.0f;
+        fa = fa * w + 4.0f / 5.0f;      fd = fd * w + 4.0f / 5.0f;
+        fa = fa * w + -2.0f / 3.0f;
+        t.a = fa / z3;
+        t.d = 2.0f * fd / (z3 * z2);
+    } else {
+        t.a = (z * t.q - t.s) / r2;
+        t.d = -(2.0f * z * t.q * t.q + 3.0f * t.a) / r2;
+    }
+    return t;
+}
+
+__device__ inline void fisheye_project(const float* c, const FisheyeTerms& t, float fx, float fy, float cx, float cy,
+                                       float* uv) {
+    uv[0] = fx * t.s * c[0] + cx;
+    uv[1] = fy * t.s * c[1] + cy;
+}
+
+__device__ inline void fisheye_J6_of(const float* c, const FisheyeTerms& t, float fx, float fy, float* J6) {
+    const float x = c[0], y = c[1];
+    const float xya = x * y * t.a;
+    J6[0] = fx * (t.s + x * x * t.a);
+    J6[1] = fx * xya;
+    J6[2] = -fx * x * t.q;
+    J6[3] = fy * xya;
+    J6[4] = fy * (t.s + y * y * t.a);
+    J6[5] = -fy * y * t.q;
+}
+
+// The fisheye twin of cam_grad_of: J (all six entries) and uv -> camera-frame xyz.  The uv part is g_uv^T J, read only
+// when z > 0 as there.  d J / d c from the derivatives listed above:
+//     dJ0 = fx (3 a x + x^3 d,   a y + x x y d,   2 x x q q - q)      dJ1 = fx (a y + x x y d,  a x + x y y d,  2 x y q q)
+//     dJ4 = fy (a x + x y y d,   3 a y + y^3 d,   2 y y q q - q)      dJ3 = dJ1 fy / fx
+//     dJ2 = fx (2 x x q q - q,   2 x y q q,       2 x z q q)          dJ5 = fy (2 x y q q,  2 y y q q - q,  2 y z q q)
+__device__ inline void fisheye_cam_grad_of(const float* c, const FisheyeTerms& t, float fx, float fy, const float* gJ6,
+                                           const float* g_uv, float* gcam) {
+    const float x = c[0], y = c[1], z = c[2];
+    const float a = t.a, d = t.d, q = t.q, qq2 = 2.0f * t.q * t.q;
+    const float ax = a * x, ay = a * y;
+    const float xxyd = x * x * y * d, xyyd = x * y * y * d;
+    const float zxx = x * x * qq2 - q, zyy = y * y * qq2 - q, zxy = x * y * qq2;
+    const float g0 = gJ6[0] * fx, g1 = gJ6[1] * fx + gJ6[3] * fy, g2 = gJ6[2] * fx;
+    const float g4 = gJ6[4] * fy, g5 = gJ6[5] * fy;
+    gcam[0] = g0 * (3.0f * ax + x * x * x * d) + g1 * (ay + xxyd) + g4 * (ax + xyyd) + g2 * zxx + g5 * zxy;
+    gcam[1] = g0 * (ay + xxyd) + g1 * (ax + xyyd) + g4 * (3.0f * ay + y * y * y * d) + g2 * zxy + g5 * zyy;
+    gcam[2] = g0 * zxx + g1 * zxy + g4 * zyy + g2 * (x * z * qq2) + g5 * (y * z * qq2);
+    if (z > 0.0f) {
+        float J6[6];
+        fisheye_J6_of(c, t, fx, fy, J6);
+        const float gu = g_uv[0], gv = g_uv[1];
+        gcam[0] += gu * J6[0] + gv * J6[3];
+        gcam[1] += gu * J6[1] + gv * J6[4];
+        gcam[2] += gu * J6[2] + gv * J6[5];
+    }
+}
+
 // precompute_sh.cu:28-39 ; rsqrt -> 1/sqrt (IEEE)
 template <typename T>
 __device__ inline void view_dir_of(const T* __restrict__ xyz, const T* __restrict__ M, int g,

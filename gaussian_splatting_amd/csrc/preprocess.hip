@@ -24,6 +24,10 @@
 // Every forward quantity is computed with the same device functions and operation order as the
 // stand-alone kernels (pg_math.h), so given the same camera-frame coordinates the results are
 // bit-identical to them and to the CPU restatement.
+//
+// GS_RASTER_FISHEYE (ABI 19): k_cull_count, k_preprocess, k_preprocess_bwd and k_pose_bwd have a FISH instantiation in
+// which the projection, its Jacobian and their backward are the equidistant fisheye model's (pg_math.h: fisheye_terms_of,
+// fisheye_project, fisheye_J6_of, fisheye_cam_grad_of); the pinhole instantiations are the text they were.
 #include <type_traits>
 
 #include "adam_math.h"
@@ -59,12 +63,40 @@ __device__ inline void to_camera(const float* __restrict__ M, float x, float y, 
     c[2] = M[8] * x + M[9] * y + M[10] * z + M[11];
 }
 
+// What a camera model's projection leaves for its Jacobian and backward: the fisheye terms, or nothing (pinhole)
+struct NoTerms {};
+template <bool FISH> using CamTerms = std::conditional_t<FISH, FisheyeTerms, NoTerms>;
+
+// FISH (GS_RASTER_FISHEYE): uv is the equidistant fisheye projection (pg_math.h: fisheye_project); the test keeps its
+// form.  terms, if given, receives the fisheye terms of c, so that a caller that goes on to J evaluates them once.
+template <bool FISH = false>
 __device__ inline bool is_culled(const float* c, const float* __restrict__ K, const Frustum& fr,
-                                 float* uv) {
-    uv[0] = K[0] * c[0] / c[2] + K[2];   // projection.cu:16-18
-    uv[1] = K[4] * c[1] / c[2] + K[5];
+                                 float* uv, CamTerms<FISH>* terms = nullptr) {
+    if constexpr (FISH) {
+        const FisheyeTerms t = fisheye_terms_of(c);
+        if (terms != nullptr) *terms = t;
+        fisheye_project(c, t, K[0], K[4], K[2], K[5], uv);
+    } else {
+        uv[0] = K[0] * c[0] / c[2] + K[2];   // projection.cu:16-18
+        uv[1] = K[4] * c[1] / c[2] + K[5];
+    }
     return (c[2] < fr.near) | (c[2] > fr.far) | (uv[0] < fr.u_lo) | (uv[0] > fr.u_hi) |
            (uv[1] < fr.v_lo) | (uv[1] > fr.v_hi);
+}
+
+// The projection Jacobian of the kernels' camera model at c; -> the terms its backward needs (none: pinhole)
+template <bool FISH>
+__device__ inline CamTerms<FISH> camera_J6_of(const float* c, float fx, float fy, float* J6) {
+    if constexpr (FISH) {
+        const FisheyeTerms t = fisheye_terms_of(c);
+        fisheye_J6_of(c, t, fx, fy, J6);
+        return t;
+    } else {
+        const float z = c[2], z2 = c[2] * c[2];
+        J6[0] = fx / z; J6[1] = 0; J6[2] = -fx * c[0] / z2;
+        J6[3] = 0; J6[4] = fy / z; J6[5] = -fy * c[1] / z2;
+        return NoTerms{};
+    }
 }
 
 // a depth's bin in the quantile histogram: GS_CUT_HIST_BINS bins over the sortable-bit range (tile_math.h:
@@ -76,6 +108,7 @@ __device__ inline int depth_bin(float z, const Frustum& fr) {
     return (int)(((uint64_t)(x - lo) * GS_CUT_HIST_BINS) / range);
 }
 
+template <bool FISH = false>
 __global__ __launch_bounds__(PP_BLOCK) void k_cull_count(const float* __restrict__ xyz,
                                                          const float* __restrict__ M,
                                                          const float* __restrict__ K, int N,
@@ -89,7 +122,7 @@ __global__ __launch_bounds__(PP_BLOCK) void k_cull_count(const float* __restrict
     if (g < N) {
         float c[3], uv[2];
         to_camera(M, xyz[g * 3 + 0], xyz[g * 3 + 1], xyz[g * 3 + 2], c);
-        vis = !is_culled(c, K, fr, uv);
+        vis = !is_culled<FISH>(c, K, fr, uv);
         // depth-bucketed binning (binning.hip "depth cut"): a histogram of the depths of every sample_stride-th
         // Gaussian that is visible, over [near, far] in sortable-bit (log-like) space; the bucket boundaries are
         // its quantiles (k_scan_counts).  ~65 k device-scope atomics per frame, behind the kernel's xyz stream.
@@ -241,7 +274,9 @@ struct Band {
 // directly (no LDS staging: most rows are skipped).
 // AA (GS_RASTER_ANTIALIASED, whole frames): the record's opacity is sigmoid * comp (pg_math.h: aa_terms_of) and its cutoff
 // radius is taken for that opacity; everything else the kernel writes -- o.opacity, the sigmoid, included -- is unchanged.
-template <int N_SH, bool BAND, bool AA = false>
+// FISH (GS_RASTER_FISHEYE, whole frames): uv, the cull and J are the fisheye model's (pg_math.h: fisheye_terms_of); the
+// camera-frame position, the depth the binning sorts and cuts by, the sigmoid and the colour keep the pinhole call's bits.
+template <int N_SH, bool BAND, bool AA = false, bool FISH = false>
 __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))) void k_preprocess(
     const float* __restrict__ xyz, const float* __restrict__ quat, const float* __restrict__ scale,
     const float* __restrict__ opacity, const float* __restrict__ rgb, const float* __restrict__ sh,
@@ -265,6 +300,7 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))
     }
     bool vis = false;
     float c[3] = {0, 0, 1}, uv[2] = {0, 0}, p[3] = {0, 0, 0};
+    CamTerms<FISH> cam_terms{};   // (FISH: the cull's terms, used again for J)
     // Every load of the Gaussian's own parameters and the workgroup's whole SH block are requested before
     // anything is computed (loads return in order: what is asked for first can be used first, the SH block lands while
     // the covariance is projected).  A workgroup that asks for its 23 KiB of SH only after its geometry is done has
@@ -297,7 +333,7 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))
     }
     if (g < N) {
         to_camera(M, p[0], p[1], p[2], c);
-        vis = !is_culled(c, K, fr, uv);
+        vis = !is_culled<FISH>(c, K, fr, uv, &cam_terms);
     }
     const unsigned long long bal = __ballot(vis);
     if (lane == 0) s_cnt[wave] = __popcll(bal);
@@ -332,12 +368,17 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))
         float S9[9], W[9], J6[6];
         sigma_world_of(q4, s3, S9);
         load_rotation(M, W);
-        J6[0] = K[0] / c[2];                       // projection.cu:169-174
-        J6[1] = 0;
-        J6[2] = -K[0] * c[0] / (c[2] * c[2]);
-        J6[3] = 0;
-        J6[4] = K[4] / c[2];
-        J6[5] = -K[4] * c[1] / (c[2] * c[2]);
+        if constexpr (FISH) {
+            static_assert(!BAND, "the fisheye mode serves whole frames");
+            fisheye_J6_of(c, cam_terms, K[0], K[4], J6);
+        } else {
+            J6[0] = K[0] / c[2];                       // projection.cu:169-174
+            J6[1] = 0;
+            J6[2] = -K[0] * c[0] / (c[2] * c[2]);
+            J6[3] = 0;
+            J6[4] = K[4] / c[2];
+            J6[5] = -K[4] * c[1] / (c[2] * c[2]);
+        }
         conic_of(J6, W, S9, c3);
         if (o.conic != nullptr) {
             o.conic[v * 3 + 0] = c3[0];
@@ -948,7 +989,9 @@ constexpr bool adam_rows_early(int n_sh) { return n_sh < 16; }
 // culled ones too, with gradient 0 -- is stepped, as the dense gradient + k_adam would.
 // AA (GS_RASTER_ANTIALIASED): slab column 3 is dL/d(sigmoid * comp); the row is folded in registers (pg_math.h:
 // aa_fold_row) with comp recomputed from the S9, J6, W at hand -- the forward's functions on the forward's bits.
-template <int N_SH, bool GATHER = false, bool ADAM = false, bool AA = false>
+// FISH (GS_RASTER_FISHEYE): J is the fisheye model's and gJ6 (all six entries) and the uv columns reach the camera-frame
+// position through fisheye_cam_grad_of (pg_math.h); everything before J and after gcam is the same text.
+template <int N_SH, bool GATHER = false, bool ADAM = false, bool AA = false, bool FISH = false>
 __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_preprocess_bwd(
     const float* __restrict__ xyz, const float* __restrict__ quat, const float* __restrict__ scale,
     const float* __restrict__ M, const float* __restrict__ K, const float* __restrict__ center,
@@ -957,6 +1000,7 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))
     std::conditional_t<ADAM, PreAdam, NoAdam> ad = {}) {
     static_assert(!(ADAM && GATHER), "the fused optimizer step serves the single-GPU frame");
     static_assert(!(AA && (ADAM || GATHER)), "the antialiased mode serves the plain single-GPU backward");
+    static_assert(!(FISH && (ADAM || GATHER)), "the fisheye mode serves the plain single-GPU backward");
     constexpr int SHW = 3 * (N_SH - 1);
     __shared__ int s_gather[GATHER ? GS_MAX_RANKS : 1][PP_BLOCK / GS_WAVE];
     float gathered[9];
@@ -1042,10 +1086,17 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))
         float S9[9], W[9], J6[6], gS9[9], gJ6[6];
         sigma_world_of(q4, s3, S9);
         load_rotation(M, W);
-        const float z = c[2], z2 = c[2] * c[2], z3 = c[2] * c[2] * c[2];
+        // (the pinhole expressions stay spelled out here, z, z2, z3 ahead of J: with them behind a helper this kernel's
+        // pinhole instantiations get another register allocation -- they must not move)
+        [[maybe_unused]] const float z = c[2], z2 = c[2] * c[2], z3 = c[2] * c[2] * c[2];
         const float fx = K[0], fy = K[4];
-        J6[0] = fx / z; J6[1] = 0; J6[2] = -fx * c[0] / z2;
-        J6[3] = 0; J6[4] = fy / z; J6[5] = -fy * c[1] / z2;
+        [[maybe_unused]] CamTerms<FISH> ft;   // (pinhole: an empty struct)
+        if constexpr (FISH) {
+            ft = camera_J6_of<true>(c, fx, fy, J6);
+        } else {
+            J6[0] = fx / z; J6[1] = 0; J6[2] = -fx * c[0] / z2;
+            J6[3] = 0; J6[4] = fy / z; J6[5] = -fy * c[1] / z2;
+        }
         float gc3[3] = {gsl[6], gsl[7], gsl[8]};
         if constexpr (AA) {
             float c3[3], g_opa = gsl[3];
@@ -1056,18 +1107,22 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))
         conic_bwd_of(J6, W, S9, gc3, gS9, gJ6);
         // Sigma_world -> quaternion, scale (projection_backward.cu:174-315)
         sigma_world_bwd_of(q4, s3, gS9, gq, gs);
-        // J -> camera-frame xyz (projection_backward.cu:93-120)
         float gcam[3];
-        gcam[0] = gJ6[2] * -fx / z2;
-        gcam[1] = gJ6[5] * -fy / z2;
-        gcam[2] = gJ6[0] * -fx / z2 + gJ6[4] * -fy / z2 + gJ6[2] * 2 * c[0] * fx / z3 +
-                  gJ6[5] * 2 * c[1] * fy / z3;
-        // uv -> camera-frame xyz (projection_backward.cu:9-36; nothing when z <= 0, Q10)
-        if (z > 0.0f) {
-            const float gu = gsl[4], gv = gsl[5];
-            gcam[0] += gu * (fx / z);
-            gcam[1] += gv * (fy / z);
-            gcam[2] += gu * (-fx * c[0] / z2) + gv * (-fy * c[1] / z2);
+        if constexpr (FISH) {
+            fisheye_cam_grad_of(c, ft, fx, fy, gJ6, gsl + 4, gcam);
+        } else {
+            // J -> camera-frame xyz (projection_backward.cu:93-120)
+            gcam[0] = gJ6[2] * -fx / z2;
+            gcam[1] = gJ6[5] * -fy / z2;
+            gcam[2] = gJ6[0] * -fx / z2 + gJ6[4] * -fy / z2 + gJ6[2] * 2 * c[0] * fx / z3 +
+                      gJ6[5] * 2 * c[1] * fy / z3;
+            // uv -> camera-frame xyz (projection_backward.cu:9-36; nothing when z <= 0, Q10)
+            if (z > 0.0f) {
+                const float gu = gsl[4], gv = gsl[5];
+                gcam[0] += gu * (fx / z);
+                gcam[1] += gv * (fy / z);
+                gcam[2] += gu * (-fx * c[0] / z2) + gv * (-fy * c[1] / z2);
+            }
         }
         // camera frame -> world: transpose of the rotation block (backward of utils.py:64)
         gx[0] = M[0] * gcam[0] + M[4] * gcam[1] + M[8] * gcam[2];
@@ -1182,8 +1237,9 @@ inline int pose_blocks(int N) {
 
 // AA (GS_RASTER_ANTIALIASED): the conic columns first gain the opacity column's share (aa_fold_row, as k_preprocess_bwd
 // folds the same row), which needs the sigmoid opacity_act[v]; the non-AA instantiation takes no such pointer.
+// FISH (GS_RASTER_FISHEYE): J and its backward are the fisheye model's (fisheye_J6_of, fisheye_cam_grad_of).
 struct NoOpacity {};
-template <bool AA = false>
+template <bool AA = false, bool FISH = false>
 __global__ __launch_bounds__(PP_BLOCK) void k_pose_bwd(
     const float* __restrict__ xyz, const float* __restrict__ quat, const float* __restrict__ scale,
     const float* __restrict__ M, const float* __restrict__ K, const int* __restrict__ rank,
@@ -1206,9 +1262,7 @@ __global__ __launch_bounds__(PP_BLOCK) void k_pose_bwd(
         float c[3], S9[9], J6[6], gJ6[6], gW9[9], gcam[3];
         to_camera(M, p[0], p[1], p[2], c);
         sigma_world_of(q4, s3, S9);
-        const float z = c[2], z2 = c[2] * c[2];
-        J6[0] = fx / z; J6[1] = 0; J6[2] = -fx * c[0] / z2;
-        J6[3] = 0; J6[4] = fy / z; J6[5] = -fy * c[1] / z2;
+        [[maybe_unused]] const CamTerms<FISH> ft = camera_J6_of<FISH>(c, fx, fy, J6);
         float gc3[3] = {gsl[6], gsl[7], gsl[8]};
         if constexpr (AA) {
             float c3[3], g_opa = gsl[3];
@@ -1216,7 +1270,8 @@ __global__ __launch_bounds__(PP_BLOCK) void k_pose_bwd(
             aa_fold_row(aa_terms_of(c3), opacity_act[v], g_opa, gc3);
         }
         conic_bwd_pose_of(J6, W, S9, gc3, gJ6, gW9);
-        cam_grad_of(c, fx, fy, gJ6, gsl + 4, gcam);
+        if constexpr (FISH) fisheye_cam_grad_of(c, ft, fx, fy, gJ6, gsl + 4, gcam);
+        else cam_grad_of(c, fx, fy, gJ6, gsl + 4, gcam);
 #pragma unroll
         for (int i = 0; i < 3; i++) {
 #pragma unroll
@@ -1286,13 +1341,25 @@ static Frustum make_frustum(int W, int H, float near, float far, float padding) 
             return GS_EINVAL;                                                                      \
     }
 
-// GS_RASTER_CLASSIC / GS_RASTER_ANTIALIASED -> whether the antialiased instantiations run; anything else is refused
-#define GS_RASTER_MODE(raster_mode, aa)                                                                      \
-    GS_REQUIRE((raster_mode) == GS_RASTER_CLASSIC || (raster_mode) == GS_RASTER_ANTIALIASED,               \
-               "raster_mode must be GS_RASTER_CLASSIC or GS_RASTER_ANTIALIASED, got %d", (int)(raster_mode)); \
-    const bool aa = (raster_mode) == GS_RASTER_ANTIALIASED
+// the raster_mode bit mask -> whether the antialiased / the fisheye instantiations run; any other bit is refused
+#define GS_RASTER_MODE(raster_mode, aa, fish)                                                                          \
+    GS_REQUIRE(((raster_mode) & ~(GS_RASTER_ANTIALIASED | GS_RASTER_FISHEYE)) == 0,                                    \
+               "raster_mode must be a combination of GS_RASTER_ANTIALIASED and GS_RASTER_FISHEYE, got %d",             \
+               (int)(raster_mode));                                                                                    \
+    const bool aa = ((raster_mode) & GS_RASTER_ANTIALIASED) != 0, fish = ((raster_mode) & GS_RASTER_FISHEYE) != 0
 
-// gs_preprocess_forward_cut and gs_preprocess_forward_mode: aa selects the AA instantiation of k_preprocess, nothing else
+// the (AA, FISH) instantiation a mode selects: CALL sees constexpr bool AA, FISH
+#define DISPATCH_MODE(aa, fish, CALL)                                                              \
+    if (fish) {                                                                                    \
+        constexpr bool FISH = true;                                                                \
+        if (aa) { constexpr bool AA = true; CALL; } else { constexpr bool AA = false; CALL; }      \
+    } else {                                                                                       \
+        constexpr bool FISH = false;                                                               \
+        if (aa) { constexpr bool AA = true; CALL; } else { constexpr bool AA = false; CALL; }      \
+    }
+
+// gs_preprocess_forward_cut and gs_preprocess_forward_mode: aa selects the AA instantiation of k_preprocess, fish the
+// FISH instantiations of k_cull_count and k_preprocess, nothing else
 static int preprocess_forward_launch(const void* xyz, const void* quaternion, const void* scale,
                                      const void* opacity, const void* rgb, const void* sh, int n_sh,
                                      const void* camera_T_world, const void* K, int N, int W, int H,
@@ -1302,7 +1369,7 @@ static int preprocess_forward_launch(const void* xyz, const void* quaternion, co
                                      uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
                                      void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
                                      void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
-                                     int sample_stride, bool aa, void* stream) {
+                                     int sample_stride, bool aa, bool fish, void* stream) {
     GS_REQUIRE((bin_records == nullptr) == (cut_workspace == nullptr) && (bin_records == nullptr) == (depth_hist == nullptr),
                "bin_records, cut_workspace and depth_hist go together");
     GS_REQUIRE(depth_hist == nullptr || sample_stride >= 1, "sample_stride must be gs_cut_sample_stride(N)");
@@ -1314,9 +1381,14 @@ static int preprocess_forward_launch(const void* xyz, const void* quaternion, co
     const int nb = div_up(N > 0 ? N : 1, PP_BLOCK);
     int* block_counts = workspace;
     int* block_offsets = workspace + nb;
-    k_cull_count<<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)camera_T_world,
-                                         (const float*)K, N, fr, block_counts, (float*)camera_center, depth_hist,
-                                         sample_stride > 0 ? sample_stride : 1);
+    if (fish)
+        k_cull_count<true><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)camera_T_world,
+                                                   (const float*)K, N, fr, block_counts, (float*)camera_center, depth_hist,
+                                                   sample_stride > 0 ? sample_stride : 1);
+    else
+        k_cull_count<false><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)camera_T_world,
+                                                    (const float*)K, N, fr, block_counts, (float*)camera_center, depth_hist,
+                                                    sample_stride > 0 ? sample_stride : 1);
     const int n_tiles = ((W + GS_TILE - 1) / GS_TILE) * ((H + GS_TILE - 1) / GS_TILE);
     CutState cs{};
     if (cut_workspace != nullptr) {
@@ -1348,12 +1420,13 @@ static int preprocess_forward_launch(const void* xyz, const void* quaternion, co
     const bool banded = !(band_row0 == 0 && band_row1 == band.nty);
     GS_REQUIRE(!(banded && bin_records != nullptr), "the depth-bucketed binning serves whole frames");
     GS_REQUIRE(!(banded && aa), "GS_RASTER_ANTIALIASED serves whole frames (no tile-row band)");
-    if (aa) {
-        DISPATCH_SH(n_sh, (k_preprocess<N_SH, false, true><<<nb, PP_BLOCK, 0, s>>>(
+    GS_REQUIRE(!(banded && fish), "GS_RASTER_FISHEYE serves whole frames (no tile-row band)");
+    if (aa || fish) {
+        DISPATCH_MODE(aa, fish, DISPATCH_SH(n_sh, (k_preprocess<N_SH, false, AA, FISH><<<nb, PP_BLOCK, 0, s>>>(
                               (const float*)xyz, (const float*)quaternion, (const float*)scale,
                               (const float*)opacity, (const float*)rgb, (const float*)sh,
                               (const float*)camera_T_world, (const float*)K,
-                              (const float*)camera_center, N, fr, block_offsets, o, band)));
+                              (const float*)camera_center, N, fr, block_offsets, o, band))));
     } else if (banded) {
         DISPATCH_SH(n_sh, (k_preprocess<N_SH, true><<<nb, PP_BLOCK, 0, s>>>(
                               (const float*)xyz, (const float*)quaternion, (const float*)scale,
@@ -1387,7 +1460,7 @@ int gs_preprocess_forward_cut(const void* xyz, const void* quaternion, const voi
     return preprocess_forward_launch(xyz, quaternion, scale, opacity, rgb, sh, n_sh, camera_T_world, K, N, W, H, near_thresh,
                                      far_thresh, cull_mask_padding, mh_dist, band_row0, band_row1, workspace, camera_center,
                                      visible_count, culling_mask, rank, vis_idx, uv, xyz_camera_frame, conic, opacity_act,
-                                     rgb_render, packed, bin_records, cut_workspace, depth_hist, sample_stride, false, stream);
+                                     rgb_render, packed, bin_records, cut_workspace, depth_hist, sample_stride, false, false, stream);
 }
 
 int gs_preprocess_forward_mode(const void* xyz, const void* quaternion, const void* scale,
@@ -1400,11 +1473,11 @@ int gs_preprocess_forward_mode(const void* xyz, const void* quaternion, const vo
                                void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
                                void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
                                int sample_stride, int raster_mode, void* stream) {
-    GS_RASTER_MODE(raster_mode, aa);
+    GS_RASTER_MODE(raster_mode, aa, fish);
     return preprocess_forward_launch(xyz, quaternion, scale, opacity, rgb, sh, n_sh, camera_T_world, K, N, W, H, near_thresh,
                                      far_thresh, cull_mask_padding, mh_dist, band_row0, band_row1, workspace, camera_center,
                                      visible_count, culling_mask, rank, vis_idx, uv, xyz_camera_frame, conic, opacity_act,
-                                     rgb_render, packed, bin_records, cut_workspace, depth_hist, sample_stride, aa, stream);
+                                     rgb_render, packed, bin_records, cut_workspace, depth_hist, sample_stride, aa, fish, stream);
 }
 
 
@@ -1419,8 +1492,8 @@ int gs_band_project(const void* xyz, const void* scale, const void* opacity, con
     const int nb = div_up(N > 0 ? N : 1, PP_BLOCK);
     int* block_counts = workspace;
     int* block_offsets = workspace + nb;
-    k_cull_count<<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)camera_T_world, (const float*)K, N, fr,
-                                         block_counts, (float*)camera_center, nullptr, 1);
+    k_cull_count<false><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)camera_T_world, (const float*)K, N, fr,
+                                                block_counts, (float*)camera_center, nullptr, 1);
     k_scan_counts<false><<<1, 1024, 0, s>>>(block_counts, nb, block_offsets, visible_count, nullptr, nullptr, fr);
     BandRows rows;
     for (int i = 0; i <= GS_MAX_RANKS; i++) rows.v[i] = i <= G ? band_rows[i] : 0;
@@ -1634,7 +1707,7 @@ int gs_preprocess_backward_mode(const void* xyz, const void* quaternion, const v
                                 int v_base, int N, void* grad_xyz, void* grad_quaternion, void* grad_scale,
                                 void* grad_opacity_logit, void* grad_rgb_param, void* grad_sh,
                                 int raster_mode, void* stream) {
-    GS_RASTER_MODE(raster_mode, aa);
+    GS_RASTER_MODE(raster_mode, aa, fish);
     GS_REQUIRE(n_sh == 1 || grad_sh != nullptr, "grad_sh must be given when n_sh > 1");
     hipStream_t s = (hipStream_t)stream;
     if (N <= 0) return GS_OK;
@@ -1645,12 +1718,12 @@ int gs_preprocess_backward_mode(const void* xyz, const void* quaternion, const v
     o.opacity = (float*)grad_opacity_logit;
     o.rgb = (float*)grad_rgb_param;
     o.sh = (float*)grad_sh;
-    if (aa) {
-        DISPATCH_SH(n_sh, (k_preprocess_bwd<N_SH, false, false, true><<<div_up(N, PP_BLOCK), PP_BLOCK, 0, s>>>(
+    if (aa || fish) {
+        DISPATCH_MODE(aa, fish, DISPATCH_SH(n_sh, (k_preprocess_bwd<N_SH, false, false, AA, FISH><<<div_up(N, PP_BLOCK), PP_BLOCK, 0, s>>>(
                               (const float*)xyz, (const float*)quaternion, (const float*)scale,
                               (const float*)camera_T_world, (const float*)K,
                               (const float*)camera_center, rank, (const float*)opacity_act,
-                              (const float*)grad_slab, v_base, N, o)));
+                              (const float*)grad_slab, v_base, N, o))));
     } else {
         DISPATCH_SH(n_sh, (k_preprocess_bwd<N_SH><<<div_up(N, PP_BLOCK), PP_BLOCK, 0, s>>>(
                               (const float*)xyz, (const float*)quaternion, (const float*)scale,
@@ -1677,7 +1750,7 @@ size_t gs_pose_workspace_floats(int N) { return (size_t)pose_blocks(N) * 12 + 4;
 int gs_pose_backward_mode(const void* xyz, const void* quaternion, const void* scale, const void* camera_T_world,
                           const void* K, const int32_t* rank, const void* opacity_act, const void* grad_slab, int v_base,
                           int N, void* workspace, void* grad_camera_T_world, int raster_mode, void* stream) {
-    GS_RASTER_MODE(raster_mode, aa);
+    GS_RASTER_MODE(raster_mode, aa, fish);
     GS_REQUIRE(!aa || N <= 0 || opacity_act != nullptr, "pose_backward: GS_RASTER_ANTIALIASED needs opacity_act");
     GS_REQUIRE(grad_camera_T_world != nullptr, "pose_backward: grad_camera_T_world is NULL");
     GS_REQUIRE(N <= 0 || (workspace != nullptr && xyz != nullptr && quaternion != nullptr && scale != nullptr &&
@@ -1685,11 +1758,20 @@ int gs_pose_backward_mode(const void* xyz, const void* quaternion, const void* s
                "pose_backward: an input or the workspace is NULL");
     hipStream_t s = (hipStream_t)stream;
     const int nb = pose_blocks(N);
-    if (nb > 0 && aa)
+    if (nb > 0 && aa && fish)
+        k_pose_bwd<true, true><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)quaternion, (const float*)scale,
+                                                       (const float*)camera_T_world, (const float*)K, rank,
+                                                       (const float*)grad_slab, v_base, N, (float*)workspace,
+                                                       (const float*)opacity_act);
+    else if (nb > 0 && aa)
         k_pose_bwd<true><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)quaternion, (const float*)scale,
                                                  (const float*)camera_T_world, (const float*)K, rank,
                                                  (const float*)grad_slab, v_base, N, (float*)workspace,
                                                  (const float*)opacity_act);
+    else if (nb > 0 && fish)
+        k_pose_bwd<false, true><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)quaternion, (const float*)scale,
+                                                        (const float*)camera_T_world, (const float*)K, rank,
+                                                        (const float*)grad_slab, v_base, N, (float*)workspace);
     else if (nb > 0)
         k_pose_bwd<false><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)quaternion, (const float*)scale,
                                                   (const float*)camera_T_world, (const float*)K, rank,

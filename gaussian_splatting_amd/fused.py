@@ -255,11 +255,25 @@ def want_depth_cut(hint_key, N, ntx, row0, row1, whole):
     return not want_segments(known, n_tiles)
 
 
+CAMERA_MODELS = ("pinhole", "fisheye")
+
+
+def _raster_mode(antialiased, camera_model):
+    """-> the raster_mode bit mask of the C ABI's _mode entries; a camera_model that is neither name raises RuntimeError"""
+    if camera_model not in CAMERA_MODELS:
+        raise RuntimeError(f"camera_model must be one of {' / '.join(repr(m) for m in CAMERA_MODELS)}, "
+                           f"got {camera_model!r}")
+    return ((_hip.GS_RASTER_ANTIALIASED if antialiased else _hip.GS_RASTER_CLASSIC)
+            | (_hip.GS_RASTER_FISHEYE if camera_model == "fisheye" else 0))
+
+
 def preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, width, height, near_thresh,
                        far_thresh, cull_mask_padding, mh_dist, tile_rows, sort_prefix, plan=None, plan_ints=0,
-                       defer=False, depth_cut=False, antialiased=False):
+                       defer=False, depth_cut=False, antialiased=False, camera_model="pinhole"):
     """Per-Gaussian stage, binning and per-tile sort of one frame.  antialiased: the packed record's opacity carries the
-    factor sqrt(det Sigma_2D / det(Sigma_2D + 0.25 I)) (gs_preprocess_forward_mode, GS_RASTER_ANTIALIASED; whole frames).  `plan`, if given, is called as
+    factor sqrt(det Sigma_2D / det(Sigma_2D + 0.25 I)) (gs_preprocess_forward_mode, GS_RASTER_ANTIALIASED; whole frames).
+    camera_model: "pinhole", or "fisheye" -- uv, the cull and the projection Jacobian of the equidistant fisheye model
+    (GS_RASTER_FISHEYE; whole frames, combines with antialiased).  `plan`, if given, is called as
     plan(f) after the per-Gaussian stage is enqueued and fills the device record f.record
     (plan_ints int32) that rides on the frame's one host read (its host copy is left in f.host:
     multi-GPU, the split sizes of the gradient exchange); it may set f.subset = (index list, device
@@ -272,8 +286,11 @@ def preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world,
     T = ntx * nty
     row0, row1 = tile_rows if tile_rows is not None else (0, nty)
     f = SimpleNamespace(N=N, n_sh=n_sh, ntx=ntx, nty=nty, T=T, row0=row0, row1=row1, width=width, height=height,
-                        mh_dist=mh_dist, sort_prefix=sort_prefix, antialiased=bool(antialiased))
+                        mh_dist=mh_dist, sort_prefix=sort_prefix, antialiased=bool(antialiased),
+                        camera_model=camera_model, raster_mode=_raster_mode(antialiased, camera_model))
     _require(not (antialiased and tile_rows is not None), "antialiased=True serves whole frames: tile_rows is not supported")
+    _require(not (camera_model == "fisheye" and tile_rows is not None),
+             'camera_model="fisheye" serves whole frames: tile_rows is not supported')
 
     stream = f.stream = _stream()
     f.hint_key = (dev.index, N, T, row0, row1)
@@ -293,12 +310,12 @@ def preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world,
     f.uv, f.xyz_cam, f.conic = uv.view(N, 2), xyz_cam.view(N, 3), conic.view(N, 3)
     f.opacity_act, f.rgb_render, f.packed = opa.view(N, 1), rgbr.view(N, 3), packed.view(N, 12)
     f.cut = None
-    if antialiased:
+    if f.raster_mode != _hip.GS_RASTER_CLASSIC:
         _hip.call("gs_preprocess_forward_mode", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), n_sh,
                   _p(camera_T_world), _p(K), N, width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, row0,
                   row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx), _p(f.uv),
                   _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), None, None, None, 0,
-                  _hip.GS_RASTER_ANTIALIASED, stream)
+                  f.raster_mode, stream)
     else:
         _hip.call("gs_preprocess_forward", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), n_sh,
                   _p(camera_T_world), _p(K), N, width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, row0,
@@ -386,12 +403,12 @@ def _preprocess_forward_cut(f, xyz, quaternion, scale, opacity, rgb, sh, camera_
     f.center, uv, xyz_cam, conic, opa, rgbr, packed, bin_rec = far.blocks()
     f.uv, f.xyz_cam, f.conic = uv.view(N, 2), xyz_cam.view(N, 3), conic.view(N, 3)
     f.opacity_act, f.rgb_render, f.packed = opa.view(N, 1), rgbr.view(N, 3), packed.view(N, 12)
-    if f.antialiased:
+    if f.raster_mode != _hip.GS_RASTER_CLASSIC:
         _hip.call("gs_preprocess_forward_mode", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), f.n_sh,
                   _p(camera_T_world), _p(K), N, f.width, f.height, near_thresh, far_thresh, cull_mask_padding, f.mh_dist,
                   row0, row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx),
                   _p(f.uv), _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), _p(bin_rec),
-                  _p(cut_ws), _p(_depth_hist(dev)), stride, _hip.GS_RASTER_ANTIALIASED, stream)
+                  _p(cut_ws), _p(_depth_hist(dev)), stride, f.raster_mode, stream)
     else:
         _hip.call("gs_preprocess_forward_cut", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), f.n_sh,
                   _p(camera_T_world), _p(K), N, f.width, f.height, near_thresh, far_thresh, cull_mask_padding, f.mh_dist,
@@ -456,10 +473,13 @@ def preprocess_finish(f):
     return redone
 
 
-def preprocess_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_base=0, i0=0, i1=None, antialiased=False):
+def preprocess_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_base=0, i0=0, i1=None, antialiased=False,
+                        camera_model="pinhole"):
     """Dense parameter gradients of the Gaussians [i0, i1) from the render-gradient slab
     (row of visible Gaussian v at slab[v - v_base]).  xyz, quaternion, scale: the full tensors.
-    antialiased: the slab's opacity column is the gradient of the antialiased opacity (gs_preprocess_backward_mode)."""
+    antialiased: the slab's opacity column is the gradient of the antialiased opacity (gs_preprocess_backward_mode).
+    camera_model: the model the forward projected with (the uv and conic columns go back through it)."""
+    mode = _raster_mode(antialiased, camera_model)
     i1 = f.N if i1 is None else i1
     n = i1 - i0
     dev = xyz.device
@@ -468,11 +488,11 @@ def preprocess_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_ba
     grad_xyz, grad_q, grad_scale = gx.view(n, 3), gq.view(n, 4), gs.view(n, 3)
     grad_opacity, grad_rgb = go.view(n, 1), gc.view(n, 3)
     grad_sh = gsh.view(n, 3, f.n_sh - 1) if f.n_sh > 1 else None
-    if n > 0 and antialiased:
+    if n > 0 and mode != _hip.GS_RASTER_CLASSIC:
         _hip.call("gs_preprocess_backward_mode", _p(xyz[i0:i1]), _p(quaternion[i0:i1]), _p(scale[i0:i1]), f.n_sh,
                   _p(camera_T_world), _p(K), _p(f.center), _p(f.rank[i0:i1]), _p(f.opacity_act), _p(slab), v_base, n,
                   _p(grad_xyz), _p(grad_q), _p(grad_scale), _p(grad_opacity), _p(grad_rgb), _p(grad_sh),
-                  _hip.GS_RASTER_ANTIALIASED, _stream())
+                  mode, _stream())
     elif n > 0:
         _hip.call("gs_preprocess_backward", _p(xyz[i0:i1]), _p(quaternion[i0:i1]), _p(scale[i0:i1]), f.n_sh,
                   _p(camera_T_world), _p(K), _p(f.center), _p(f.rank[i0:i1]), _p(f.opacity_act), _p(slab), v_base, n,
@@ -480,17 +500,19 @@ def preprocess_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_ba
     return grad_xyz, grad_q, grad_scale, grad_opacity, grad_rgb, grad_sh
 
 
-def pose_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_base=0, antialiased=False):
+def pose_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_base=0, antialiased=False,
+                  camera_model="pinhole"):
     """The gradient of camera_T_world [4, 4] from the render-gradient slab of frame record f (gs_pose_backward): the
     rotation block and the translation as twelve free numbers, the last row 0.  Reads the quaternion and scale the
     forward saw: with the fused optimizer step it goes BEFORE preprocess_backward_adam on the same stream."""
     n = f.N
+    mode = _raster_mode(antialiased, camera_model)
     # (two allocations: the gradient outlives the backward, the workspace must not live as long)
     grad = torch.empty(4, 4, dtype=torch.float32, device=xyz.device)
     ws = torch.empty(_hip.lib().gs_pose_workspace_floats(n), dtype=torch.float32, device=xyz.device)
-    if antialiased:   # (the opacity column reaches the pose through the factor's conic terms)
+    if mode != _hip.GS_RASTER_CLASSIC:   # (antialiased: the opacity column reaches the pose through the factor's conic terms)
         _hip.call("gs_pose_backward_mode", _p(xyz), _p(quaternion), _p(scale), _p(camera_T_world), _p(K), _p(f.rank),
-                  _p(f.opacity_act), _p(slab), v_base, n, _p(ws), _p(grad), _hip.GS_RASTER_ANTIALIASED, _stream())
+                  _p(f.opacity_act), _p(slab), v_base, n, _p(ws), _p(grad), mode, _stream())
     else:
         _hip.call("gs_pose_backward", _p(xyz), _p(quaternion), _p(scale), _p(camera_T_world), _p(K), _p(f.rank),
                   _p(slab), v_base, n, _p(ws), _p(grad), _stream())
@@ -762,7 +784,7 @@ def _as_slab(g_uv, g_conic, g_opa, g_rgb, V, dev):
 # ---------------------------------------------------------------------------------------------------
 def _frame_record(width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, tile_rows=None, sort_prefix=0,
                   background=None, pose_grad=False, adam_plan=None, antialiased=False, z_out=False, may_cut=False,
-                  slab_sync=None, absgrad=False):
+                  slab_sync=None, absgrad=False, camera_model="pinhole"):
     """What one frame's two nodes share and autograd does not differentiate: the frame's options, set here by the entry
     point, and -- filled by _Preprocess.forward -- the stage record's tensors the render and the caller read.  Handed
     to both nodes as a non-tensor argument.  The differentiable outputs are not kept on it (that would tie the record to
@@ -775,6 +797,8 @@ def _frame_record(width, height, near_thresh, far_thresh, cull_mask_padding, mh_
     tensor -- the handle through which the depth map's dL/dz comes back to that node
     antialiased: the packed record's opacity is sigmoid * comp; the opacity OUTPUT stays the sigmoid (the render reads
     the record), so the gradient that comes back for it is dL/d(sigmoid * comp) and the backward folds it
+    camera_model: "pinhole" or "fisheye" -- the projection of the per-Gaussian stage, forward and both backwards; the
+    render, the binning and the maps read only what that stage wrote
     may_cut: the frame may take the depth cut (want_depth_cut decides); its record, what _Render's two passes need,
     is then left in `cut`
     slab_sync: see rasterize()
@@ -783,8 +807,8 @@ def _frame_record(width, height, near_thresh, far_thresh, cull_mask_padding, mh_
     return SimpleNamespace(
         width=width, height=height, near_thresh=near_thresh, far_thresh=far_thresh, cull_mask_padding=cull_mask_padding,
         mh_dist=mh_dist, tile_rows=tile_rows, sort_prefix=sort_prefix, background=background, pose_grad=pose_grad,
-        adam_plan=adam_plan, antialiased=bool(antialiased), z_out=z_out, may_cut=may_cut, slab_sync=slab_sync,
-        absgrad=bool(absgrad), uv_absgrad=None,
+        adam_plan=adam_plan, antialiased=bool(antialiased), camera_model=camera_model, z_out=z_out, may_cut=may_cut,
+        slab_sync=slab_sync, absgrad=bool(absgrad), uv_absgrad=None,
         # after _Preprocess.forward (xyz_cam and vis_idx: the V visible rows)
         packed=None, xyz_cam=None, culling_mask=None, ranges=None, sorted_g=None, vis_idx=None, keys=None, cut=None,
         rendered=None)   # (image, nsp, fw, cost, seg) when _Preprocess.forward already enqueued _Render's kernels
@@ -805,7 +829,7 @@ class _Preprocess(torch.autograd.Function):
         f = preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, fr.width, fr.height,
                                fr.near_thresh, fr.far_thresh, fr.cull_mask_padding, fr.mh_dist, fr.tile_rows,
                                fr.sort_prefix, defer=(not cut) and EARLY_RENDER and fr.sort_prefix != 0, depth_cut=cut,
-                               antialiased=fr.antialiased)
+                               antialiased=fr.antialiased, camera_model=fr.camera_model)
         if cut:
             fr.rendered = render_forward(f.packed, f.rgb_render, f.ranges, f.sorted_g, f.keys, fr.background, fr.height,
                                          fr.width, fr.tile_rows, fr.sort_prefix, segments=False, cut=f.cut)
@@ -848,7 +872,8 @@ class _Preprocess(torch.autograd.Function):
         # (before the fused optimizer step, which overwrites the quaternion and scale the pose terms read)
         g_pose = None
         if fr.pose_grad and ctx.needs_input_grad[6]:
-            g_pose = pose_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab, antialiased=fr.antialiased)
+            g_pose = pose_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab, antialiased=fr.antialiased,
+                                   camera_model=fr.camera_model)
             if g_z is not None:
                 # the direct term of z = T[2, 0:3] . xyz + T[2, 3] (the slab's terms above already hold the depth map's
                 # uv / conic columns): plumbing on the visible rows, not a hot path
@@ -859,7 +884,7 @@ class _Preprocess(torch.autograd.Function):
             grads = (preprocess_backward_adam(xyz, camera_T_world, K, ctx.f, slab, fr.adam_plan),) + (None,) * 5
         else:
             grads = preprocess_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab,
-                                        antialiased=fr.antialiased)
+                                        antialiased=fr.antialiased, camera_model=fr.camera_model)
         if g_z is not None:
             _hip.call("gs_z_backward", _p(ctx.f.rank), _p(g_z), _p(camera_T_world), 0, ctx.f.N, _p(grads[0]), _stream())
         return grads + (g_pose, None, None)   # (K, the record)
@@ -1123,6 +1148,7 @@ def _begin_frame(gaussians, sh, camera_T_world, camera, near_thresh, far_thresh,
     coefficients the per-Gaussian stage folds into the colour.
     -> (the frame record, (uv, conic, opacity, rgb[, z]))"""
     g = gaussians
+    _raster_mode(False, options.get("camera_model", "pinhole"))   # (an unknown name raises before anything else)
     if who is not None:
         _refuse(who, g, camera_T_world, camera, use_sh_precompute, background_rgb, frame_options, adam_plan)
         if features is not None:
@@ -1143,7 +1169,7 @@ def _begin_frame(gaussians, sh, camera_T_world, camera, near_thresh, far_thresh,
 
 def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
               use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None, slab_sync=None,
-              frame_hook=None, adam_plan=None, antialiased=False, absgrad=False):
+              frame_hook=None, adam_plan=None, antialiased=False, absgrad=False, camera_model="pinhole"):
     """tile_rows=(row0, row1) restricts binning and rendering to those tile rows; slab_sync(flat) is
     called on the flat [9 V] render-gradient slab in the backward (grad_sync is the generic
     per-tensor form used by the reference-shaped path): the hooks gaussian_splatting_amd.sharded
@@ -1165,8 +1191,20 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
     densify.DensityController.accumulate in place of uv.grad: per-pixel gradients of opposite sign cancel in uv.grad
     for exactly the large Gaussians that need splitting, and add here.  Served like antialiased=True (which combines
     freely), on the Python orchestration -- the native frame has no such node -- with the depth cut, depth segments and
-    longest-first order under their usual policies; anything else raises RuntimeError before a kernel is enqueued."""
+    longest-first order under their usual policies; anything else raises RuntimeError before a kernel is enqueued.
+    camera_model="fisheye" projects with the equidistant fisheye model (gsplat's camera_model="fisheye"):
+    uv = (fx, fy) * theta / r * (x, y) + (cx, cy) with theta = atan2(r, z), r = |(x, y)| of the camera-frame position;
+    camera.K stays the 3x3 pinhole matrix (no skew, no distortion coefficients) and the cull keeps its form, so the field
+    of view stays under 180 degrees.  Only the per-Gaussian stage changes, forward and backward (pose included).  Served
+    like antialiased=True, with which and with absgrad=True it combines, natively or on the Python orchestration, with
+    the depth cut, depth segments and longest-first order under their usual policies; tile_rows, the hooks, adam_plan,
+    per-pixel SH (its rays are pinhole rays), non-fp32 or CPU tensors raise RuntimeError before a kernel is enqueued,
+    and so does any other camera_model string.  "pinhole" (the default) is exactly the frame without the keyword."""
     hooks = return_aux or grad_sync or slab_sync or frame_hook
+    raster_mode = _raster_mode(antialiased, camera_model)
+    if camera_model == "fisheye":
+        _refuse('rasterize(camera_model="fisheye")', gaussians, camera_T_world, camera, use_sh_precompute,
+                background_rgb, (tile_rows is not None, hooks), adam_plan)
     if absgrad:
         _refuse("rasterize(absgrad=True)", gaussians, camera_T_world, camera, use_sh_precompute, background_rgb,
                 (tile_rows is not None, hooks), adam_plan)
@@ -1202,13 +1240,13 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
                                       mh_dist, background_rgb, adam_plan)
         return nat.rasterize(g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
                              int(camera.width), int(camera.height), near_thresh, far_thresh, cull_mask_padding, mh_dist,
-                             background_rgb, row0, row1, bool(antialiased))
+                             background_rgb, row0, row1, raster_mode)
     # (refused and validated above; the depth cut only without hooks; the pose a constant on multi-GPU frames)
     fr, (uv, conic, opacity, rgb) = _begin_frame(
         g, g.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist, background_rgb,
         adam_plan=adam_plan, tile_rows=tile_rows, sort_prefix=_hip.GS_SORT_PREFIX if (SORT_PREFIX and not return_aux) else 0,
         pose_grad=not (grad_sync or slab_sync), antialiased=antialiased, may_cut=not hooks, slab_sync=slab_sync,
-        absgrad=absgrad)
+        absgrad=absgrad, camera_model=camera_model)
     if absgrad:   # (a row even when nothing is visible: an empty tensor has no address to hand to the entry)
         fr.uv_absgrad = torch.zeros(max(uv.shape[0], 1), 2, dtype=torch.float32, device=uv.device)
     if frame_hook is not None:   # multi-GPU cost-balanced bands: the band's tile ranges
@@ -1225,7 +1263,7 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
 
 def rasterize_rgbd(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
                    use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None, slab_sync=None,
-                   frame_hook=None, adam_plan=None, antialiased=False):
+                   frame_hook=None, adam_plan=None, antialiased=False, camera_model="pinhole"):
     """rasterize() with a differentiable depth map and accumulated opacity:
 
         image, depth, alpha, culling_mask, uv = rasterize_rgbd(...)
@@ -1237,19 +1275,21 @@ def rasterize_rgbd(gaussians, camera_T_world, camera, near_thresh, far_thresh, c
     camera_T_world; the backward of depth and alpha is their true derivative (DESIGN.md "Depth and alpha maps").
     Whole single-GPU fp32 frames in the SH-precompute colour mode, Python orchestration, depth cut off: anything
     else raises RuntimeError (the trailing keyword arguments exist only to say so).  antialiased: as rasterize()'s --
-    the maps' weights then carry the antialiased opacity too."""
+    the maps' weights then carry the antialiased opacity too.  camera_model: as rasterize()'s; depth stays the camera-frame
+    z, not the distance along the ray."""
     fr, (uv, conic, opacity, rgb, z) = _begin_frame(
         gaussians, gaussians.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
         background_rgb, "rasterize_rgbd", use_sh_precompute,
         (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), adam_plan=adam_plan,
-        antialiased=antialiased, z_out=True)
+        antialiased=antialiased, z_out=True, camera_model=camera_model)
     image, depth, alpha = _Render.apply(uv, conic, opacity, rgb, z, fr, _DepthMap)
     return image, depth, alpha, fr.culling_mask, uv
 
 
 def rasterize_distortion(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
                          use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None,
-                         slab_sync=None, frame_hook=None, adam_plan=None, antialiased=False):
+                         slab_sync=None, frame_hook=None, adam_plan=None, antialiased=False,
+                         camera_model="pinhole"):
     """rasterize_rgbd() with the depth-distortion map of the same walk:
 
         image, depth, alpha, distortion, culling_mask, uv = rasterize_distortion(...)
@@ -1262,20 +1302,21 @@ def rasterize_distortion(gaussians, camera_T_world, camera, near_thresh, far_thr
     parameters and, when it requires one, to camera_T_world; the maps' backward is their true derivative, one kernel
     for the three of them in place of rasterize_rgbd's (DESIGN.md "Depth distortion").  An output without a gradient
     costs nothing.  Whole single-GPU fp32 frames in the SH-precompute colour mode, Python orchestration, depth cut off:
-    anything else raises RuntimeError (the trailing keyword arguments exist only to say so).  antialiased: as
+    anything else raises RuntimeError (the trailing keyword arguments exist only to say so).  antialiased, camera_model: as
     rasterize()'s."""
     fr, (uv, conic, opacity, rgb, z) = _begin_frame(
         gaussians, gaussians.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
         background_rgb, "rasterize_distortion", use_sh_precompute,
         (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), adam_plan=adam_plan,
-        antialiased=antialiased, z_out=True)
+        antialiased=antialiased, z_out=True, camera_model=camera_model)
     image, depth, alpha, distortion = _Render.apply(uv, conic, opacity, rgb, z, fr, _DistortionMap)
     return image, depth, alpha, distortion, fr.culling_mask, uv
 
 
 def rasterize_features(gaussians, features, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
                        use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None,
-                       slab_sync=None, frame_hook=None, adam_plan=None, antialiased=False):
+                       slab_sync=None, frame_hook=None, adam_plan=None, antialiased=False,
+                       camera_model="pinhole"):
     """rasterize() with a map of caller-supplied per-Gaussian feature vectors and the accumulated opacity:
 
         image, feature_map, alpha, culling_mask, uv = rasterize_features(gaussians, features, ...)
@@ -1288,12 +1329,12 @@ def rasterize_features(gaussians, features, camera_T_world, camera, near_thresh,
     Gaussians' parameters and, when it requires one, to camera_T_world (through the slab; features have no direct
     pose term); their backward is the true derivative (DESIGN.md "Feature maps").  Whole single-GPU fp32 frames in the
     SH-precompute colour mode, Python orchestration, depth cut off: anything else raises RuntimeError (the trailing
-    keyword arguments exist only to say so).  antialiased: as rasterize()'s."""
+    keyword arguments exist only to say so).  antialiased, camera_model: as rasterize()'s."""
     fr, (uv, conic, opacity, rgb) = _begin_frame(
         gaussians, gaussians.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
         background_rgb, "rasterize_features", use_sh_precompute,
         (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), features, adam_plan,
-        antialiased=antialiased)
+        antialiased=antialiased, camera_model=camera_model)
     feat = _GatherRows.apply(features, fr.vis_idx.long()).contiguous()
     image, feature_map, alpha = _Render.apply(uv, conic, opacity, rgb, feat, fr, _FeatureMap)
     return image, feature_map, alpha, fr.culling_mask, uv
@@ -1341,7 +1382,8 @@ class ContributionStats:
 
 def rasterize_contributions(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
                             use_sh_precompute, background_rgb, stats=None, antialiased=False, tile_rows=None,
-                            return_aux=False, grad_sync=None, slab_sync=None, frame_hook=None, adam_plan=None):
+                            return_aux=False, grad_sync=None, slab_sync=None, frame_hook=None, adam_plan=None,
+                            camera_model="pinhole"):
     """rasterize() without gradients, with the per-Gaussian contribution statistics of the frame:
 
         image, stats, culling_mask = rasterize_contributions(gaussians, ...)                # a new record
@@ -1354,7 +1396,8 @@ def rasterize_contributions(gaussians, camera_T_world, camera, near_thresh, far_
     (gs_render_contributions with row_index = the frame's visible indices): no [V] temporary, no scatter.  Runs under
     torch.no_grad(); nothing returned carries a gradient.  Whole single-GPU fp32 frames in the SH-precompute colour
     mode, Python orchestration, depth cut off: anything else raises RuntimeError before a kernel is enqueued (the
-    trailing keyword arguments exist only to say so).  A stats of another N raises too.  antialiased: as rasterize()'s."""
+    trailing keyword arguments exist only to say so).  A stats of another N raises too.  antialiased, camera_model: as
+    rasterize()'s."""
     with torch.no_grad():
         n = int(gaussians.xyz.shape[0])
         if stats is not None:
@@ -1364,7 +1407,7 @@ def rasterize_contributions(gaussians, camera_T_world, camera, near_thresh, far_
             gaussians, gaussians.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
             background_rgb, "rasterize_contributions", use_sh_precompute,
             (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), adam_plan=adam_plan,
-            antialiased=antialiased)
+            antialiased=antialiased, camera_model=camera_model)
         if stats is None:
             stats = ContributionStats.zeros(n, gaussians.xyz.device)
         else:

@@ -329,10 +329,33 @@ int gs_pose_backward(const void* xyz, const void* quaternion, const void* scale,
  * gs_preprocess_backward_mode  gs_preprocess_backward + raster_mode; slices [i0, i1) and v_base as there.
  * gs_pose_backward_mode        gs_pose_backward + opacity_act (the full [V,1] array, indexed by v: the fold needs y; may
  *                              be NULL with GS_RASTER_CLASSIC) + raster_mode.
- * With GS_RASTER_CLASSIC each launches exactly the kernels of the entry it extends; any other raster_mode value returns
- * GS_EINVAL.  The band, list, gathered and Adam forms of the per-Gaussian stage have no antialiased mode. */
+ * raster_mode is a bit mask (ABI 19): GS_RASTER_ANTIALIASED | GS_RASTER_FISHEYE in any combination; a value with any
+ * other bit set returns GS_EINVAL (message names raster_mode) and writes nothing.  With GS_RASTER_CLASSIC each entry
+ * launches exactly the kernels of the entry it extends, with GS_RASTER_ANTIALIASED exactly those of ABI 14.  The band,
+ * list, gathered and Adam forms of the per-Gaussian stage have neither mode.
+ *
+ * ---- fisheye camera (fp32, ABI 19; the equidistant model, gsplat's camera_model="fisheye"; no reference counterpart) ----
+ * GS_RASTER_FISHEYE replaces the pinhole projection and its Jacobian in the per-Gaussian stage; K stays the 3x3
+ * matrix (fx, fy, cx, cy; no skew, no distortion coefficients).  With (x, y, z) = xyz_camera_frame (unchanged):
+ *     r2 = x x + y y      q = 1 / (r2 + z z)      r = sqrt(r2)      theta = atan2(r, z)
+ *     s = theta / r                                                   (r2 == 0:  s = 1 / z)
+ *     u = fx s x + cx     v = fy s y + cy
+ *     a = (z q - s) / r2                                              (r2 == 0:  a = -2 / (3 z^3))
+ *     J = [[fx (s + x x a),  fx x y a,        -fx x q],
+ *          [fy x y a,        fy (s + y y a),  -fy y q]]
+ *   forward   the cull keeps its form (z < near | z > far | u, v outside the padded image: the usable field of view stays
+ *             under 180 degrees); uv, conic = J W Sigma (J W)^T, bin_records and the packed record follow the model;
+ *             xyz_camera_frame, opacity_act and rgb_render keep the pinhole call's bits on a row visible in both; sort
+ *             keys, depth buckets and the depth maps keep using z.
+ *   backward  gJ reaches the camera-frame position through all six entries (J1 and J3 are not zero) and g_uv through
+ *             g_uv^T J (when z > 0, as for the pinhole model), with  d = -(2 z q q + 3 a) / r2  (r2 == 0: 8 / (5 z^5)):
+ *                 ds = (a x, a y, -q)     da = (d x, d y, 2 q q)     dq = -2 q q (x, y, z)
+ *             For r2 < z z / 16 a and d are evaluated as their series in r2 / (z z) (their closed forms cancel near the
+ *             axis); one definition, csrc/pg_math.h fisheye_terms_of / fisheye_J6_of / fisheye_cam_grad_of.
+ * Arithmetic: fp32, no contraction, IEEE divide and square root; atan2f is the device library's. */
 #define GS_RASTER_CLASSIC 0
 #define GS_RASTER_ANTIALIASED 1
+#define GS_RASTER_FISHEYE 2
 int gs_preprocess_forward_mode(const void* xyz, const void* quaternion, const void* scale,
                                const void* opacity, const void* rgb, const void* sh, int n_sh,
                                const void* camera_T_world, const void* K, int N, int W, int H,
