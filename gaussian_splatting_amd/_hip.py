@@ -196,13 +196,16 @@ def timed_region(name, fn):
     return out
 
 
-def call(name, *args):
+def call(name, *args, label=None):
+    """label: the name the call's GPU time is booked under (default: the entry point's) -- a step that one general
+    entry serves in every mode keeps one name in the timings"""
     fn = getattr(lib(), name)
-    if _timers is None or (_only is not None and _only != name):
+    label = label or name
+    if _timers is None or (_only is not None and _only != label):
         check(fn(*args))
         return
     a, b = _event(), _event()
     a.record()
     check(fn(*args))
     b.record()
-    _timers.setdefault(name, []).append((a, b))
+    _timers.setdefault(label, []).append((a, b))

@@ -469,22 +469,14 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
         const float* rgbr = packed;
         int32_t* depth_hist = cut ? depth_hist_of(dev, stream) : nullptr;
         timed("gs_preprocess_forward", stream, [&] {
-            if (raster_mode != GS_RASTER_CLASSIC)
-                return gs_preprocess_forward_mode(
-                    xyz.data_ptr(), quaternion.data_ptr(), scale.data_ptr(), opacity.data_ptr(), rgb.data_ptr(),
-                    has_sh ? sh.data_ptr() : nullptr, n_sh, camera_T_world.data_ptr(), K.data_ptr(), N, (int)W, (int)H,
-                    (float)near_thresh, (float)far_thresh, (float)padding, (float)mh_dist, (int)row0, (int)row1, ws, center,
-                    count, mask, rank, nullptr, cut ? nullptr : uv, cut ? nullptr : xyz_cam, cut ? nullptr : conic, opa,
-                    nullptr, packed, cut ? bin_rec : nullptr, cut ? cut_ws : nullptr, depth_hist, stride,
-                    (int)raster_mode, stream);
-            return gs_preprocess_forward_cut(xyz.data_ptr(), quaternion.data_ptr(), scale.data_ptr(), opacity.data_ptr(),
-                                             rgb.data_ptr(), has_sh ? sh.data_ptr() : nullptr, n_sh, camera_T_world.data_ptr(),
-                                             K.data_ptr(), N, (int)W, (int)H, (float)near_thresh, (float)far_thresh,
-                                             (float)padding, (float)mh_dist, (int)row0, (int)row1, ws, center, count, mask, rank,
-                                             nullptr /* vis_idx: nobody reads it on this path */, cut ? nullptr : uv,
-                                             cut ? nullptr : xyz_cam, cut ? nullptr : conic, opa,
-                                             nullptr /* rgb_render: the colour is in the packed record */, packed,
-                                             cut ? bin_rec : nullptr, cut ? cut_ws : nullptr, depth_hist, stride, stream);
+            return gs_preprocess_forward_mode(
+                xyz.data_ptr(), quaternion.data_ptr(), scale.data_ptr(), opacity.data_ptr(), rgb.data_ptr(),
+                has_sh ? sh.data_ptr() : nullptr, n_sh, camera_T_world.data_ptr(), K.data_ptr(), N, (int)W, (int)H,
+                (float)near_thresh, (float)far_thresh, (float)padding, (float)mh_dist, (int)row0, (int)row1, ws, center,
+                count, mask, rank, nullptr /* vis_idx: nobody reads it on this path */, cut ? nullptr : uv,
+                cut ? nullptr : xyz_cam, cut ? nullptr : conic, opa,
+                nullptr /* rgb_render: the colour is in the packed record */, packed, cut ? bin_rec : nullptr,
+                cut ? cut_ws : nullptr, depth_hist, stride, (int)raster_mode, stream);
         });
         const FrameKind kind{cut, sort_prefix, !cut && sort_prefix != 0, true};
         const FramePlan plan = plan_frame(start.st, g_policy, kind);
@@ -628,14 +620,10 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
             Tensor grad_pose = torch::empty({4, 4}, xyz.options());
             Tensor ws = torch::empty({(int64_t)gs_pose_workspace_floats(N)}, xyz.options());
             timed("gs_pose_backward", stream, [&] {
-                if (raster_mode != GS_RASTER_CLASSIC)
-                    return gs_pose_backward_mode(xyz.data_ptr(), quaternion.data_ptr(), scale.data_ptr(),
-                                                 camera_T_world.data_ptr(), K.data_ptr(), rank.data_ptr<int32_t>(),
-                                                 opacity_act.data_ptr(), slab.data_ptr(), 0, N, ws.data_ptr(),
-                                                 grad_pose.data_ptr(), raster_mode, stream);
-                return gs_pose_backward(xyz.data_ptr(), quaternion.data_ptr(), scale.data_ptr(), camera_T_world.data_ptr(),
-                                        K.data_ptr(), rank.data_ptr<int32_t>(), slab.data_ptr(), 0, N,
-                                        ws.data_ptr(), grad_pose.data_ptr(), stream);
+                return gs_pose_backward_mode(xyz.data_ptr(), quaternion.data_ptr(), scale.data_ptr(),
+                                             camera_T_world.data_ptr(), K.data_ptr(), rank.data_ptr<int32_t>(),
+                                             opacity_act.data_ptr(), slab.data_ptr(), 0, N, ws.data_ptr(),
+                                             grad_pose.data_ptr(), raster_mode, stream);
             });
             out[6] = grad_pose;
         }
@@ -678,16 +666,11 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
         if (n > 0) {
             void* stream = cur_stream();
             timed("gs_preprocess_backward", stream, [&] {
-                if (raster_mode != GS_RASTER_CLASSIC)
-                    return gs_preprocess_backward_mode(xyz.data_ptr(), quaternion.data_ptr(), scale.data_ptr(), n_sh,
-                                                       camera_T_world.data_ptr(), K.data_ptr(), center.data_ptr(),
-                                                       rank.data_ptr<int32_t>(), opacity_act.data_ptr(), slab.data_ptr(), 0,
-                                                       (int)n, ga.ptr(0), ga.ptr(1), ga.ptr(2), ga.ptr(3), ga.ptr(4),
-                                                       ga.ptr(5), raster_mode, stream);
-                return gs_preprocess_backward(xyz.data_ptr(), quaternion.data_ptr(), scale.data_ptr(), n_sh,
-                                              camera_T_world.data_ptr(), K.data_ptr(), center.data_ptr(),
-                                              rank.data_ptr<int32_t>(), opacity_act.data_ptr(), slab.data_ptr(), 0, (int)n,
-                                              ga.ptr(0), ga.ptr(1), ga.ptr(2), ga.ptr(3), ga.ptr(4), ga.ptr(5), stream);
+                return gs_preprocess_backward_mode(xyz.data_ptr(), quaternion.data_ptr(), scale.data_ptr(), n_sh,
+                                                   camera_T_world.data_ptr(), K.data_ptr(), center.data_ptr(),
+                                                   rank.data_ptr<int32_t>(), opacity_act.data_ptr(), slab.data_ptr(), 0,
+                                                   (int)n, ga.ptr(0), ga.ptr(1), ga.ptr(2), ga.ptr(3), ga.ptr(4),
+                                                   ga.ptr(5), raster_mode, stream);
             });
         }
         ga.views(out);
@@ -980,11 +963,12 @@ struct OwnerPreprocess : public torch::autograd::Function<OwnerPreprocess> {
             });
         } else {
             timed("gs_preprocess_forward", stream, [&] {
-                return gs_preprocess_forward(fr.xyz.data_ptr(), fr.quaternion.data_ptr(), fr.scale.data_ptr(), fr.opacity.data_ptr(),
-                                             fr.rgb.data_ptr(), has_sh ? fr.sh.data_ptr() : nullptr, n_sh,
-                                             fr.camera_T_world.data_ptr(), fr.K.data_ptr(), N, W, H, (float)fr.near_thresh,
-                                             (float)fr.far_thresh, (float)fr.padding, (float)fr.mh_dist, row0, row1, ws, center,
-                                             count, mask, rank, vis_idx, uv, xyz_cam, conic, opa, rgbr, packed, stream);
+                return gs_preprocess_forward_mode(
+                    fr.xyz.data_ptr(), fr.quaternion.data_ptr(), fr.scale.data_ptr(), fr.opacity.data_ptr(), fr.rgb.data_ptr(),
+                    has_sh ? fr.sh.data_ptr() : nullptr, n_sh, fr.camera_T_world.data_ptr(), fr.K.data_ptr(), N, W, H,
+                    (float)fr.near_thresh, (float)fr.far_thresh, (float)fr.padding, (float)fr.mh_dist, row0, row1, ws, center,
+                    count, mask, rank, vis_idx, uv, xyz_cam, conic, opa, rgbr, packed, nullptr, nullptr, nullptr, 0,
+                    GS_RASTER_CLASSIC /* band frames have no other mode */, stream);
             });
             // the exchange plan; its record rides on the frame's one host read, its send list is the binning's subset
             timed("gs_halo_plan", stream, [&] {
@@ -1149,11 +1133,12 @@ struct OwnerPreprocess : public torch::autograd::Function<OwnerPreprocess> {
                         fr.halo_ws.data_ptr<int32_t>(), fr.N, sp.G, sp.rank, sp.owner_blocks.data(), recv.data_ptr(),
                         fr.recv_offsets.data(), (int)n, ga.ptr(0), ga.ptr(1), ga.ptr(2), ga.ptr(3), ga.ptr(4), ga.ptr(5),
                         stream);
-                return gs_preprocess_backward(fr.xyz.data_ptr<float>() + 3 * i0, fr.quaternion.data_ptr<float>() + 4 * i0,
-                                              fr.scale.data_ptr<float>() + 3 * i0, n_sh, fr.camera_T_world.data_ptr(),
-                                              fr.K.data_ptr(), fr.center.data_ptr(), fr.rank_t.data_ptr<int32_t>() + i0,
-                                              fr.opa_act.data_ptr(), owned.data_ptr(), (int)fr.v_lo, (int)n, ga.ptr(0),
-                                              ga.ptr(1), ga.ptr(2), ga.ptr(3), ga.ptr(4), ga.ptr(5), stream);
+                return gs_preprocess_backward_mode(
+                    fr.xyz.data_ptr<float>() + 3 * i0, fr.quaternion.data_ptr<float>() + 4 * i0,
+                    fr.scale.data_ptr<float>() + 3 * i0, n_sh, fr.camera_T_world.data_ptr(), fr.K.data_ptr(),
+                    fr.center.data_ptr(), fr.rank_t.data_ptr<int32_t>() + i0, fr.opa_act.data_ptr(), owned.data_ptr(),
+                    (int)fr.v_lo, (int)n, ga.ptr(0), ga.ptr(1), ga.ptr(2), ga.ptr(3), ga.ptr(4), ga.ptr(5), GS_RASTER_CLASSIC,
+                    stream);
             });
         }
         ga.views(out);

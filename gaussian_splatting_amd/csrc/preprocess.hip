@@ -25,6 +25,11 @@
 // stand-alone kernels (pg_math.h), so given the same camera-frame coordinates the results are
 // bit-identical to them and to the CPU restatement.
 //
+// The row evaluation is stated once: k_preprocess, k_preprocess_list and k_band_rows share sigma_world_of, conic_of and
+// pack_record (pg_math.h) and, below, pinhole_J6_of, view_basis_of, sh_colour_of and store_record.  Three kernels keep a
+// text of their own because their machine code moves otherwise (each says so where it does): k_preprocess_list its
+// colour sum, camera_J6_of<false> (k_pose_bwd) its pinhole Jacobian, k_preprocess_bwd its pinhole Jacobian and backward.
+//
 // GS_RASTER_FISHEYE (ABI 19): k_cull_count, k_preprocess, k_preprocess_bwd and k_pose_bwd have a FISH instantiation in
 // which the projection, its Jacobian and their backward are the equidistant fisheye model's (pg_math.h: fisheye_terms_of,
 // fisheye_project, fisheye_J6_of, fisheye_cam_grad_of); the pinhole instantiations are the text they were.
@@ -84,6 +89,20 @@ __device__ inline bool is_culled(const float* c, const float* __restrict__ K, co
            (uv[1] < fr.v_lo) | (uv[1] > fr.v_hi);
 }
 
+// ---- the row evaluation's shared statements: k_preprocess, k_preprocess_list and k_band_rows call these four (the
+// colour of k_preprocess_list excepted, see there), k_preprocess_bwd the view basis.  Their argument forms are the ones
+// that leave every kernel's machine code where it was (profiles/r19/per_gaussian_isa.txt): fx, fy and the position by
+// value, the six Jacobian expressions as written. ----
+// The pinhole projection's Jacobian at c (projection.cu:169-174), the forward kernels' statement
+__device__ __forceinline__ void pinhole_J6_of(const float* c, float fx, float fy, float* J6) {
+    J6[0] = fx / c[2];
+    J6[1] = 0;
+    J6[2] = -fx * c[0] / (c[2] * c[2]);
+    J6[3] = 0;
+    J6[4] = fy / c[2];
+    J6[5] = -fy * c[1] / (c[2] * c[2]);
+}
+
 // The projection Jacobian of the kernels' camera model at c; -> the terms its backward needs (none: pinhole)
 template <bool FISH>
 __device__ inline CamTerms<FISH> camera_J6_of(const float* c, float fx, float fy, float* J6) {
@@ -92,11 +111,46 @@ __device__ inline CamTerms<FISH> camera_J6_of(const float* c, float fx, float fy
         fisheye_J6_of(c, t, fx, fy, J6);
         return t;
     } else {
+        // (pinhole_J6_of restated with z, z2 ahead: k_pose_bwd<AA> is scheduled differently behind the other form, and the
+        // forward kernels behind this one -- profiles/r19/README.md)
         const float z = c[2], z2 = c[2] * c[2];
         J6[0] = fx / z; J6[1] = 0; J6[2] = -fx * c[0] / z2;
         J6[3] = 0; J6[4] = fy / z; J6[5] = -fy * c[1] / z2;
         return NoTerms{};
     }
+}
+
+// The SH basis of the view direction from the camera centre to the world position p (precompute_sh.cu:28-39;
+// rsqrt -> 1 / sqrt, IEEE)
+template <int N_SH>
+__device__ __forceinline__ void view_basis_of(float px, float py, float pz, const float* center, float* Y) {
+    float d[3] = {px - center[0], py - center[1], pz - center[2]};
+    const float r = 1.0f / __builtin_sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    d[0] *= r; d[1] *= r; d[2] *= r;
+    sh_basis<float, N_SH>(d, Y);
+}
+
+// The colour the renderer consumes (precompute_sh.cu:40-55): coefficient 0 = the rgb row c0, 1.. = the SH row shg
+// [3][N_SH - 1] (rasterize.py:89)
+template <int N_SH>
+__device__ __forceinline__ void sh_colour_of(const float* Y, const float* c0, const float* shg, float* col) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        float t = 0;
+        t += Y[0] * c0[ch];
+#pragma unroll
+        for (int s = 1; s < N_SH; s++) t += Y[s] * shg[(N_SH - 1) * ch + (s - 1)];
+        t *= GS_R_SH_0;
+        col[ch] = t;
+    }
+}
+
+// the packed record pk[GS_PACKED_WIDTH] -> row `row` of packed, three 16-byte stores
+__device__ __forceinline__ void store_record(float* packed, size_t row, const float* pk) {
+    float4* dst = reinterpret_cast<float4*>(packed + row * GS_PACKED_WIDTH);
+    dst[0] = make_float4(pk[0], pk[1], pk[2], pk[3]);
+    dst[1] = make_float4(pk[4], pk[5], pk[6], pk[7]);
+    dst[2] = make_float4(pk[8], pk[9], pk[10], pk[11]);
 }
 
 // a depth's bin in the quantile histogram: GS_CUT_HIST_BINS bins over the sortable-bit range (tile_math.h:
@@ -372,12 +426,7 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))
             static_assert(!BAND, "the fisheye mode serves whole frames");
             fisheye_J6_of(c, cam_terms, K[0], K[4], J6);
         } else {
-            J6[0] = K[0] / c[2];                       // projection.cu:169-174
-            J6[1] = 0;
-            J6[2] = -K[0] * c[0] / (c[2] * c[2]);
-            J6[3] = 0;
-            J6[4] = K[4] / c[2];
-            J6[5] = -K[4] * c[1] / (c[2] * c[2]);
+            pinhole_J6_of(c, K[0], K[4], J6);
         }
         conic_of(J6, W, S9, c3);
         if (o.conic != nullptr) {
@@ -414,22 +463,9 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))
         // precompute_sh.cu:28-55 with coefficient 0 = rgb and 1.. = sh (rasterize.py:89)
         float Y[N_SH];
         if (act && in_band) {
-            float d[3] = {p[0] - center[0], p[1] - center[1], p[2] - center[2]};
-            const float r = 1.0f / __builtin_sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-            d[0] *= r; d[1] *= r; d[2] *= r;
-            sh_basis<float, N_SH>(d, Y);
+            view_basis_of<N_SH>(p[0], p[1], p[2], center, Y);
         }
-        auto colour_from = [&](const float* shg) {
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) {
-                float t = 0;
-                t += Y[0] * rgb[g * 3 + ch];
-#pragma unroll
-                for (int s = 1; s < N_SH; s++) t += Y[s] * shg[(N_SH - 1) * ch + (s - 1)];
-                t *= GS_R_SH_0;
-                col[ch] = t;
-            }
-        };
+        auto colour_from = [&](const float* shg) { sh_colour_of<N_SH>(Y, rgb + g * 3, shg, col); };
         if constexpr (BAND) {
             if (act && in_band) colour_from(sh + (size_t)g * SHW);
         } else {
@@ -471,10 +507,7 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))
     } else {
         pack_record<float>(uv[0], uv[1], c3, opa, col, pk);
     }
-    float4* dst = reinterpret_cast<float4*>(o.packed + (size_t)v * GS_PACKED_WIDTH);
-    dst[0] = make_float4(pk[0], pk[1], pk[2], pk[3]);
-    dst[1] = make_float4(pk[4], pk[5], pk[6], pk[7]);
-    dst[2] = make_float4(pk[8], pk[9], pk[10], pk[11]);
+    store_record(o.packed, (size_t)v, pk);
 }
 
 
@@ -494,7 +527,8 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))
 //   (gs_halo_plan_masked: the exchange plan from these masks; its send list -- the visible Gaussians with this
 //   rank's bit, ascending -- is the list of rows of the compact arrays)
 //   k_preprocess_list  row l of the list: Sigma, J, conic, SH colour, packed record of Gaussian vis_idx[send[l]],
-//                      written at row l.  Same device functions and operation order as k_preprocess: the same bits.
+//                      written at row l.  k_preprocess's device functions (the colour sum restated) in its operation
+//                      order: the same bits.
 // Binning, sort and render then work on the compact arrays (row index l, monotone in v: depth ties keep their
 // order, the tile lists are the single-GPU lists with v relabelled), and the band's render-gradient slab [L, 9]
 // IS the send buffer of the gradient exchange.
@@ -626,12 +660,7 @@ __global__ __launch_bounds__(PP_BLOCK) void k_preprocess_list(
     float S9[9], W[9], J6[6], c3[3];
     sigma_world_of(q4, s3, S9);
     load_rotation(M, W);
-    J6[0] = K[0] / c[2];                       // projection.cu:169-174
-    J6[1] = 0;
-    J6[2] = -K[0] * c[0] / (c[2] * c[2]);
-    J6[3] = 0;
-    J6[4] = K[4] / c[2];
-    J6[5] = -K[4] * c[1] / (c[2] * c[2]);
+    pinhole_J6_of(c, K[0], K[4], J6);
     conic_of(J6, W, S9, c3);
     conic_l[l * 3 + 0] = c3[0];
     conic_l[l * 3 + 1] = c3[1];
@@ -641,10 +670,8 @@ __global__ __launch_bounds__(PP_BLOCK) void k_preprocess_list(
         col[0] = rgb[g * 3 + 0]; col[1] = rgb[g * 3 + 1]; col[2] = rgb[g * 3 + 2];
     } else {
         float Y[N_SH];
-        float d[3] = {p[0] - center[0], p[1] - center[1], p[2] - center[2]};
-        const float r = 1.0f / __builtin_sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        d[0] *= r; d[1] *= r; d[2] *= r;
-        sh_basis<float, N_SH>(d, Y);
+        view_basis_of<N_SH>(p[0], p[1], p[2], center, Y);
+        // (sh_colour_of restated: behind any call this kernel's degrees 1-3 get another instruction order)
         const float* shg = sh + (size_t)g * SHW;
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
@@ -658,10 +685,7 @@ __global__ __launch_bounds__(PP_BLOCK) void k_preprocess_list(
     }
     float pk[GS_PACKED_WIDTH];
     pack_record<float>(uv[0], uv[1], c3, opa_v[v], col, pk);
-    float4* dst = reinterpret_cast<float4*>(packed_l + (size_t)l * GS_PACKED_WIDTH);
-    dst[0] = make_float4(pk[0], pk[1], pk[2], pk[3]);
-    dst[1] = make_float4(pk[4], pk[5], pk[6], pk[7]);
-    dst[2] = make_float4(pk[8], pk[9], pk[10], pk[11]);
+    store_record(packed_l, (size_t)l, pk);
 }
 
 // ---- multi-GPU: the fused band frontend (ABI 8) ---------------------------------------------------------------
@@ -678,7 +702,7 @@ __global__ __launch_bounds__(PP_BLOCK) void k_preprocess_list(
 //                  for the Gaussians of MY band -- rows l = row (1 + me)'s prefix, ascending in g, hence in v: the
 //                  send list -- send_index[l] = v, list_g[l] = g, uv_l[l], xyz_cam_l[l], the opacity slot of
 //                  packed_l[l] and the world position (staged in conic_l[l]); its extra workgroup writes the plan
-//   k_band_rows    row l: Sigma, J, conic, SH colour, packed record (k_preprocess_list's evaluation: the same device
+//   k_band_rows    row l: Sigma, J, conic, SH colour, packed record (k_preprocess's evaluation: the same device
 //                  functions in the same order, the same bits) from coalesced reads of what k_band_write left plus
 //                  gathers of quaternion / scale / rgb / sh
 struct BandOwners {
@@ -860,44 +884,24 @@ __global__ __launch_bounds__(PP_BLOCK) void k_band_rows(
     } else {
         float Y[N_SH];
         if (act) {
-            float d[3] = {p[0] - center[0], p[1] - center[1], p[2] - center[2]};
-            const float r = 1.0f / __builtin_sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-            d[0] *= r; d[1] *= r; d[2] *= r;
-            sh_basis<float, N_SH>(d, Y);
+            view_basis_of<N_SH>(p[0], p[1], p[2], center, Y);
         }
-        auto colour_from = [&](const float* shg) {   // precompute_sh.cu:28-55, coefficient 0 = rgb (rasterize.py:89)
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) {
-                float t = 0;
-                t += Y[0] * c0[ch];
-#pragma unroll
-                for (int s2 = 1; s2 < N_SH; s2++) t += Y[s2] * shg[(N_SH - 1) * ch + (s2 - 1)];
-                t *= GS_R_SH_0;
-                col[ch] = t;
-            }
-        };
+        // (through a lambda, as in k_preprocess: called directly, degree 1 gets another register allocation)
+        auto colour_from = [&](const float* shg) { sh_colour_of<N_SH>(Y, c0, shg, col); };
         if (act) colour_from(sh + (size_t)g * SHW);
     }
     if (!act) return;
     float S9[9], W[9], J6[6], c3[3];
     sigma_world_of(q4, s3, S9);
     load_rotation(M, W);
-    J6[0] = K[0] / c[2];                       // projection.cu:169-174
-    J6[1] = 0;
-    J6[2] = -K[0] * c[0] / (c[2] * c[2]);
-    J6[3] = 0;
-    J6[4] = K[4] / c[2];
-    J6[5] = -K[4] * c[1] / (c[2] * c[2]);
+    pinhole_J6_of(c, K[0], K[4], J6);
     conic_of(J6, W, S9, c3);
     conic_l[l * 3 + 0] = c3[0];
     conic_l[l * 3 + 1] = c3[1];
     conic_l[l * 3 + 2] = c3[2];
     float pk[GS_PACKED_WIDTH];
     pack_record<float>(uv[0], uv[1], c3, opa, col, pk);
-    float4* dst = reinterpret_cast<float4*>(packed_l + (size_t)l * GS_PACKED_WIDTH);
-    dst[0] = make_float4(pk[0], pk[1], pk[2], pk[3]);
-    dst[1] = make_float4(pk[4], pk[5], pk[6], pk[7]);
-    dst[2] = make_float4(pk[8], pk[9], pk[10], pk[11]);
+    store_record(packed_l, (size_t)l, pk);
 }
 
 // the receive side of the gradient exchange by Gaussian-index blocks: sender s's rows for my slice are its band's
@@ -1061,10 +1065,7 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))
         if constexpr (N_SH == 1) {
             gc[0] = gr[0]; gc[1] = gr[1]; gc[2] = gr[2];
         } else {
-            float d[3] = {p[0] - center[0], p[1] - center[1], p[2] - center[2]};
-            const float r = 1.0f / __builtin_sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-            d[0] *= r; d[1] *= r; d[2] *= r;
-            sh_basis<float, N_SH>(d, Y);
+            view_basis_of<N_SH>(p[0], p[1], p[2], center, Y);
 #pragma unroll
             for (int ch = 0; ch < 3; ch++) {
                 gl3[ch] = gr[ch] * GS_R_SH_0;
@@ -1358,18 +1359,40 @@ static Frustum make_frustum(int W, int H, float near, float far, float padding) 
         if (aa) { constexpr bool AA = true; CALL; } else { constexpr bool AA = false; CALL; }      \
     }
 
-// gs_preprocess_forward_cut and gs_preprocess_forward_mode: aa selects the AA instantiation of k_preprocess, fish the
-// FISH instantiations of k_cull_count and k_preprocess, nothing else
-static int preprocess_forward_launch(const void* xyz, const void* quaternion, const void* scale,
-                                     const void* opacity, const void* rgb, const void* sh, int n_sh,
-                                     const void* camera_T_world, const void* K, int N, int W, int H,
-                                     float near_thresh, float far_thresh, float cull_mask_padding,
-                                     float mh_dist, int band_row0, int band_row1,
-                                     int32_t* workspace, void* camera_center, int32_t* visible_count,
-                                     uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
-                                     void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
-                                     void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
-                                     int sample_stride, bool aa, bool fish, void* stream) {
+// the AA-only argument of k_pose_bwd: the sigmoid opacities, or nothing
+template <bool AA>
+static auto pose_opacity_arg(const void* opacity_act) {
+    if constexpr (AA) return (const float*)opacity_act;
+    else return NoOpacity{};
+}
+
+static PreGrad pre_grad_of(void* xyz, void* quaternion, void* scale, void* opacity, void* rgb, void* sh) {
+    return PreGrad{(float*)xyz, (float*)quaternion, (float*)scale, (float*)opacity, (float*)rgb, (float*)sh};
+}
+
+static BandRows band_rows_of(const int32_t* band_rows, int G) {
+    BandRows rows;
+    for (int i = 0; i <= GS_MAX_RANKS; i++) rows.v[i] = i <= G ? band_rows[i] : 0;
+    return rows;
+}
+
+extern "C" {
+
+size_t gs_preprocess_workspace_ints(int N) { return (size_t)div_up(N > 0 ? N : 1, PP_BLOCK) * 2 + 8; }
+
+// raster_mode: GS_RASTER_ANTIALIASED selects the AA instantiation of k_preprocess, GS_RASTER_FISHEYE the FISH
+// instantiations of k_cull_count and k_preprocess, nothing else
+int gs_preprocess_forward_mode(const void* xyz, const void* quaternion, const void* scale,
+                               const void* opacity, const void* rgb, const void* sh, int n_sh,
+                               const void* camera_T_world, const void* K, int N, int W, int H,
+                               float near_thresh, float far_thresh, float cull_mask_padding,
+                               float mh_dist, int band_row0, int band_row1,
+                               int32_t* workspace, void* camera_center, int32_t* visible_count,
+                               uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
+                               void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
+                               void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
+                               int sample_stride, int raster_mode, void* stream) {
+    GS_RASTER_MODE(raster_mode, aa, fish);
     GS_REQUIRE((bin_records == nullptr) == (cut_workspace == nullptr) && (bin_records == nullptr) == (depth_hist == nullptr),
                "bin_records, cut_workspace and depth_hist go together");
     GS_REQUIRE(depth_hist == nullptr || sample_stride >= 1, "sample_stride must be gs_cut_sample_stride(N)");
@@ -1381,14 +1404,10 @@ static int preprocess_forward_launch(const void* xyz, const void* quaternion, co
     const int nb = div_up(N > 0 ? N : 1, PP_BLOCK);
     int* block_counts = workspace;
     int* block_offsets = workspace + nb;
-    if (fish)
-        k_cull_count<true><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)camera_T_world,
-                                                   (const float*)K, N, fr, block_counts, (float*)camera_center, depth_hist,
-                                                   sample_stride > 0 ? sample_stride : 1);
-    else
-        k_cull_count<false><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)camera_T_world,
-                                                    (const float*)K, N, fr, block_counts, (float*)camera_center, depth_hist,
-                                                    sample_stride > 0 ? sample_stride : 1);
+    const auto cull_count = fish ? k_cull_count<true> : k_cull_count<false>;
+    cull_count<<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)camera_T_world, (const float*)K, N, fr,
+                                       block_counts, (float*)camera_center, depth_hist,
+                                       sample_stride > 0 ? sample_stride : 1);
     const int n_tiles = ((W + GS_TILE - 1) / GS_TILE) * ((H + GS_TILE - 1) / GS_TILE);
     CutState cs{};
     if (cut_workspace != nullptr) {
@@ -1421,65 +1440,20 @@ static int preprocess_forward_launch(const void* xyz, const void* quaternion, co
     GS_REQUIRE(!(banded && bin_records != nullptr), "the depth-bucketed binning serves whole frames");
     GS_REQUIRE(!(banded && aa), "GS_RASTER_ANTIALIASED serves whole frames (no tile-row band)");
     GS_REQUIRE(!(banded && fish), "GS_RASTER_FISHEYE serves whole frames (no tile-row band)");
-    if (aa || fish) {
-        DISPATCH_MODE(aa, fish, DISPATCH_SH(n_sh, (k_preprocess<N_SH, false, AA, FISH><<<nb, PP_BLOCK, 0, s>>>(
-                              (const float*)xyz, (const float*)quaternion, (const float*)scale,
-                              (const float*)opacity, (const float*)rgb, (const float*)sh,
-                              (const float*)camera_T_world, (const float*)K,
-                              (const float*)camera_center, N, fr, block_offsets, o, band))));
-    } else if (banded) {
-        DISPATCH_SH(n_sh, (k_preprocess<N_SH, true><<<nb, PP_BLOCK, 0, s>>>(
-                              (const float*)xyz, (const float*)quaternion, (const float*)scale,
-                              (const float*)opacity, (const float*)rgb, (const float*)sh,
-                              (const float*)camera_T_world, (const float*)K,
-                              (const float*)camera_center, N, fr, block_offsets, o, band)));
+    // BAND, or (AA, FISH), chooses the kernel (a band frame is a classic one: required above); one argument list
+    auto launch = [&](auto kernel) {
+        kernel<<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)quaternion, (const float*)scale,
+                                       (const float*)opacity, (const float*)rgb, (const float*)sh,
+                                       (const float*)camera_T_world, (const float*)K, (const float*)camera_center, N, fr,
+                                       block_offsets, o, band);
+    };
+    if (banded) {
+        DISPATCH_SH(n_sh, (launch(k_preprocess<N_SH, true>)));
     } else {
-        DISPATCH_SH(n_sh, (k_preprocess<N_SH, false><<<nb, PP_BLOCK, 0, s>>>(
-                              (const float*)xyz, (const float*)quaternion, (const float*)scale,
-                              (const float*)opacity, (const float*)rgb, (const float*)sh,
-                              (const float*)camera_T_world, (const float*)K,
-                              (const float*)camera_center, N, fr, block_offsets, o, band)));
+        DISPATCH_MODE(aa, fish, DISPATCH_SH(n_sh, (launch(k_preprocess<N_SH, false, AA, FISH>))));
     }
     return check_launch("preprocess_forward");
 }
-
-extern "C" {
-
-size_t gs_preprocess_workspace_ints(int N) { return (size_t)div_up(N > 0 ? N : 1, PP_BLOCK) * 2 + 8; }
-
-int gs_preprocess_forward_cut(const void* xyz, const void* quaternion, const void* scale,
-                              const void* opacity, const void* rgb, const void* sh, int n_sh,
-                              const void* camera_T_world, const void* K, int N, int W, int H,
-                              float near_thresh, float far_thresh, float cull_mask_padding,
-                              float mh_dist, int band_row0, int band_row1,
-                              int32_t* workspace, void* camera_center, int32_t* visible_count,
-                              uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
-                              void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
-                              void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
-                              int sample_stride, void* stream) {
-    return preprocess_forward_launch(xyz, quaternion, scale, opacity, rgb, sh, n_sh, camera_T_world, K, N, W, H, near_thresh,
-                                     far_thresh, cull_mask_padding, mh_dist, band_row0, band_row1, workspace, camera_center,
-                                     visible_count, culling_mask, rank, vis_idx, uv, xyz_camera_frame, conic, opacity_act,
-                                     rgb_render, packed, bin_records, cut_workspace, depth_hist, sample_stride, false, false, stream);
-}
-
-int gs_preprocess_forward_mode(const void* xyz, const void* quaternion, const void* scale,
-                               const void* opacity, const void* rgb, const void* sh, int n_sh,
-                               const void* camera_T_world, const void* K, int N, int W, int H,
-                               float near_thresh, float far_thresh, float cull_mask_padding,
-                               float mh_dist, int band_row0, int band_row1,
-                               int32_t* workspace, void* camera_center, int32_t* visible_count,
-                               uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
-                               void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
-                               void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
-                               int sample_stride, int raster_mode, void* stream) {
-    GS_RASTER_MODE(raster_mode, aa, fish);
-    return preprocess_forward_launch(xyz, quaternion, scale, opacity, rgb, sh, n_sh, camera_T_world, K, N, W, H, near_thresh,
-                                     far_thresh, cull_mask_padding, mh_dist, band_row0, band_row1, workspace, camera_center,
-                                     visible_count, culling_mask, rank, vis_idx, uv, xyz_camera_frame, conic, opacity_act,
-                                     rgb_render, packed, bin_records, cut_workspace, depth_hist, sample_stride, aa, fish, stream);
-}
-
 
 int gs_band_project(const void* xyz, const void* scale, const void* opacity, const void* camera_T_world, const void* K,
                     int N, int W, int H, float near_thresh, float far_thresh, float cull_mask_padding, float mh_dist,
@@ -1495,8 +1469,7 @@ int gs_band_project(const void* xyz, const void* scale, const void* opacity, con
     k_cull_count<false><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)camera_T_world, (const float*)K, N, fr,
                                                 block_counts, (float*)camera_center, nullptr, 1);
     k_scan_counts<false><<<1, 1024, 0, s>>>(block_counts, nb, block_offsets, visible_count, nullptr, nullptr, fr);
-    BandRows rows;
-    for (int i = 0; i <= GS_MAX_RANKS; i++) rows.v[i] = i <= G ? band_rows[i] : 0;
+    const BandRows rows = band_rows_of(band_rows, G);
     const int nty = (H + GS_TILE - 1) / GS_TILE;
     k_band_project<1><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)scale, (const float*)opacity,
                                               (const float*)camera_T_world, (const float*)K, N, fr, mh_dist, nty, rows, G,
@@ -1505,21 +1478,6 @@ int gs_band_project(const void* xyz, const void* scale, const void* opacity, con
     // per-block bit counts by visible index: the first block of gs_halo_workspace_ints' layout
     k_band_bit_counts<<<nb, PP_BLOCK, 0, s>>>(mask, visible_count, G, halo_workspace, nb);
     return check_launch("band_project");
-}
-
-int gs_preprocess_forward(const void* xyz, const void* quaternion, const void* scale,
-                          const void* opacity, const void* rgb, const void* sh, int n_sh,
-                          const void* camera_T_world, const void* K, int N, int W, int H,
-                          float near_thresh, float far_thresh, float cull_mask_padding,
-                          float mh_dist, int band_row0, int band_row1,
-                          int32_t* workspace, void* camera_center, int32_t* visible_count,
-                          uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
-                          void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
-                          void* packed, void* stream) {
-    return gs_preprocess_forward_cut(xyz, quaternion, scale, opacity, rgb, sh, n_sh, camera_T_world, K, N, W, H, near_thresh,
-                                     far_thresh, cull_mask_padding, mh_dist, band_row0, band_row1, workspace, camera_center,
-                                     visible_count, culling_mask, rank, vis_idx, uv, xyz_camera_frame, conic, opacity_act,
-                                     rgb_render, packed, nullptr, nullptr, nullptr, 0, stream);
 }
 
 int gs_preprocess_forward_list(const void* xyz, const void* quaternion, const void* scale, const void* rgb, const void* sh,
@@ -1587,10 +1545,9 @@ int gs_band_frontend(const void* xyz, const void* quaternion, const void* scale,
     hipStream_t s = (hipStream_t)stream;
     const Frustum fr = make_frustum(W, H, near_thresh, far_thresh, cull_mask_padding);
     const FrontendWs w = frontend_ws(workspace, N, G);
-    BandRows rows;
+    const BandRows rows = band_rows_of(band_rows, G);
     BandOwners owners;
     for (int i = 0; i <= GS_MAX_RANKS; i++) {
-        rows.v[i] = i <= G ? band_rows[i] : 0;
         owners.v[i] = i <= G ? owner_blocks[i] : 0;
         GS_REQUIRE(i == 0 || i > G || owner_blocks[i] >= owner_blocks[i - 1], "band_frontend: owner_blocks must ascend");
     }
@@ -1638,13 +1595,7 @@ int gs_preprocess_backward_gathered(const void* xyz, const void* quaternion, con
     const FrontendWs w = frontend_ws(const_cast<int32_t*>(workspace), N_total, G);
     const GatherPlan gp = gather_plan(w, G, rank, owner_blocks, recv, recv_offsets);
     GS_REQUIRE((size_t)gp.blk0 * PP_BLOCK + (size_t)n <= (size_t)N_total, "preprocess_backward_gathered: slice beyond N");
-    PreGrad o;
-    o.xyz = (float*)grad_xyz;
-    o.quaternion = (float*)grad_quaternion;
-    o.scale = (float*)grad_scale;
-    o.opacity = (float*)grad_opacity_logit;
-    o.rgb = (float*)grad_rgb_param;
-    o.sh = (float*)grad_sh;
+    const PreGrad o = pre_grad_of(grad_xyz, grad_quaternion, grad_scale, grad_opacity_logit, grad_rgb_param, grad_sh);
     DISPATCH_SH(n_sh, (k_preprocess_bwd<N_SH, true><<<div_up(n, PP_BLOCK), PP_BLOCK, 0, (hipStream_t)stream>>>(
                           (const float*)xyz, (const float*)quaternion, (const float*)scale, (const float*)camera_T_world,
                           (const float*)K, (const float*)camera_center, rank_of_gaussian, (const float*)opacity_act, nullptr,
@@ -1692,8 +1643,7 @@ int gs_preprocess_backward_adam(const void* xyz, int n_sh, const void* camera_T_
     ad.sh = n_sh > 1 ? row(sh, sh_exp_avg, sh_exp_avg_sq, sh_lr, sh_step) : AdamRow{nullptr, nullptr, nullptr, 0.0f, 1.0f};
     ad.s = adam_shared(beta1, beta2, eps);
     ad.sh_vec_ok = n_sh > 1 && (((uintptr_t)sh | (uintptr_t)sh_exp_avg | (uintptr_t)sh_exp_avg_sq) & 15) == 0;
-    PreGrad o{};
-    o.xyz = (float*)grad_xyz;
+    const PreGrad o = pre_grad_of(grad_xyz, nullptr, nullptr, nullptr, nullptr, nullptr);
     DISPATCH_SH(n_sh, (k_preprocess_bwd<N_SH, false, true><<<div_up(N, PP_BLOCK), PP_BLOCK, 0, (hipStream_t)stream>>>(
                           (const float*)xyz, nullptr, nullptr, (const float*)camera_T_world, (const float*)K,
                           (const float*)camera_center, rank, (const float*)opacity_act, (const float*)grad_slab, v_base,
@@ -1711,38 +1661,12 @@ int gs_preprocess_backward_mode(const void* xyz, const void* quaternion, const v
     GS_REQUIRE(n_sh == 1 || grad_sh != nullptr, "grad_sh must be given when n_sh > 1");
     hipStream_t s = (hipStream_t)stream;
     if (N <= 0) return GS_OK;
-    PreGrad o;
-    o.xyz = (float*)grad_xyz;
-    o.quaternion = (float*)grad_quaternion;
-    o.scale = (float*)grad_scale;
-    o.opacity = (float*)grad_opacity_logit;
-    o.rgb = (float*)grad_rgb_param;
-    o.sh = (float*)grad_sh;
-    if (aa || fish) {
-        DISPATCH_MODE(aa, fish, DISPATCH_SH(n_sh, (k_preprocess_bwd<N_SH, false, false, AA, FISH><<<div_up(N, PP_BLOCK), PP_BLOCK, 0, s>>>(
-                              (const float*)xyz, (const float*)quaternion, (const float*)scale,
-                              (const float*)camera_T_world, (const float*)K,
-                              (const float*)camera_center, rank, (const float*)opacity_act,
-                              (const float*)grad_slab, v_base, N, o))));
-    } else {
-        DISPATCH_SH(n_sh, (k_preprocess_bwd<N_SH><<<div_up(N, PP_BLOCK), PP_BLOCK, 0, s>>>(
-                              (const float*)xyz, (const float*)quaternion, (const float*)scale,
-                              (const float*)camera_T_world, (const float*)K,
-                              (const float*)camera_center, rank, (const float*)opacity_act,
-                              (const float*)grad_slab, v_base, N, o)));
-    }
+    const PreGrad o = pre_grad_of(grad_xyz, grad_quaternion, grad_scale, grad_opacity_logit, grad_rgb_param, grad_sh);
+    DISPATCH_MODE(aa, fish, DISPATCH_SH(n_sh, (k_preprocess_bwd<N_SH, false, false, AA, FISH><<<div_up(N, PP_BLOCK), PP_BLOCK, 0, s>>>(
+                      (const float*)xyz, (const float*)quaternion, (const float*)scale, (const float*)camera_T_world,
+                      (const float*)K, (const float*)camera_center, rank, (const float*)opacity_act,
+                      (const float*)grad_slab, v_base, N, o))));
     return check_launch("preprocess_backward");
-}
-
-int gs_preprocess_backward(const void* xyz, const void* quaternion, const void* scale, int n_sh,
-                           const void* camera_T_world, const void* K, const void* camera_center,
-                           const int32_t* rank, const void* opacity_act, const void* grad_slab,
-                           int v_base, int N, void* grad_xyz, void* grad_quaternion, void* grad_scale,
-                           void* grad_opacity_logit, void* grad_rgb_param, void* grad_sh,
-                           void* stream) {
-    return gs_preprocess_backward_mode(xyz, quaternion, scale, n_sh, camera_T_world, K, camera_center, rank, opacity_act,
-                                       grad_slab, v_base, N, grad_xyz, grad_quaternion, grad_scale, grad_opacity_logit,
-                                       grad_rgb_param, grad_sh, GS_RASTER_CLASSIC, stream);
 }
 
 size_t gs_pose_workspace_floats(int N) { return (size_t)pose_blocks(N) * 12 + 4; }
@@ -1758,27 +1682,59 @@ int gs_pose_backward_mode(const void* xyz, const void* quaternion, const void* s
                "pose_backward: an input or the workspace is NULL");
     hipStream_t s = (hipStream_t)stream;
     const int nb = pose_blocks(N);
-    if (nb > 0 && aa && fish)
-        k_pose_bwd<true, true><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)quaternion, (const float*)scale,
-                                                       (const float*)camera_T_world, (const float*)K, rank,
-                                                       (const float*)grad_slab, v_base, N, (float*)workspace,
-                                                       (const float*)opacity_act);
-    else if (nb > 0 && aa)
-        k_pose_bwd<true><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)quaternion, (const float*)scale,
-                                                 (const float*)camera_T_world, (const float*)K, rank,
-                                                 (const float*)grad_slab, v_base, N, (float*)workspace,
-                                                 (const float*)opacity_act);
-    else if (nb > 0 && fish)
-        k_pose_bwd<false, true><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)quaternion, (const float*)scale,
-                                                        (const float*)camera_T_world, (const float*)K, rank,
-                                                        (const float*)grad_slab, v_base, N, (float*)workspace);
-    else if (nb > 0)
-        k_pose_bwd<false><<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)quaternion, (const float*)scale,
-                                                  (const float*)camera_T_world, (const float*)K, rank,
-                                                  (const float*)grad_slab, v_base, N, (float*)workspace);
+    if (nb > 0) {
+        DISPATCH_MODE(aa, fish, (k_pose_bwd<AA, FISH><<<nb, PP_BLOCK, 0, s>>>(
+                          (const float*)xyz, (const float*)quaternion, (const float*)scale, (const float*)camera_T_world,
+                          (const float*)K, rank, (const float*)grad_slab, v_base, N, (float*)workspace,
+                          pose_opacity_arg<AA>(opacity_act))));
+    }
     // (N == 0: no rows, the sum writes the zeros)
     k_pose_sum<<<1, POSE_SUM_BLOCK, 0, s>>>((const float*)workspace, nb, (float*)grad_camera_T_world);
     return check_launch("pose_backward");
+}
+
+// ---- the entries the general ones above superseded: each forwards, in one line, to the entry named in its body ----
+int gs_preprocess_forward_cut(const void* xyz, const void* quaternion, const void* scale,
+                              const void* opacity, const void* rgb, const void* sh, int n_sh,
+                              const void* camera_T_world, const void* K, int N, int W, int H,
+                              float near_thresh, float far_thresh, float cull_mask_padding,
+                              float mh_dist, int band_row0, int band_row1,
+                              int32_t* workspace, void* camera_center, int32_t* visible_count,
+                              uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
+                              void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
+                              void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
+                              int sample_stride, void* stream) {
+    return gs_preprocess_forward_mode(xyz, quaternion, scale, opacity, rgb, sh, n_sh, camera_T_world, K, N, W, H, near_thresh,
+                                      far_thresh, cull_mask_padding, mh_dist, band_row0, band_row1, workspace, camera_center,
+                                      visible_count, culling_mask, rank, vis_idx, uv, xyz_camera_frame, conic, opacity_act,
+                                      rgb_render, packed, bin_records, cut_workspace, depth_hist, sample_stride,
+                                      GS_RASTER_CLASSIC, stream);
+}
+
+int gs_preprocess_forward(const void* xyz, const void* quaternion, const void* scale,
+                          const void* opacity, const void* rgb, const void* sh, int n_sh,
+                          const void* camera_T_world, const void* K, int N, int W, int H,
+                          float near_thresh, float far_thresh, float cull_mask_padding,
+                          float mh_dist, int band_row0, int band_row1,
+                          int32_t* workspace, void* camera_center, int32_t* visible_count,
+                          uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
+                          void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
+                          void* packed, void* stream) {
+    return gs_preprocess_forward_cut(xyz, quaternion, scale, opacity, rgb, sh, n_sh, camera_T_world, K, N, W, H, near_thresh,
+                                     far_thresh, cull_mask_padding, mh_dist, band_row0, band_row1, workspace, camera_center,
+                                     visible_count, culling_mask, rank, vis_idx, uv, xyz_camera_frame, conic, opacity_act,
+                                     rgb_render, packed, nullptr, nullptr, nullptr, 0, stream);
+}
+
+int gs_preprocess_backward(const void* xyz, const void* quaternion, const void* scale, int n_sh,
+                           const void* camera_T_world, const void* K, const void* camera_center,
+                           const int32_t* rank, const void* opacity_act, const void* grad_slab,
+                           int v_base, int N, void* grad_xyz, void* grad_quaternion, void* grad_scale,
+                           void* grad_opacity_logit, void* grad_rgb_param, void* grad_sh,
+                           void* stream) {
+    return gs_preprocess_backward_mode(xyz, quaternion, scale, n_sh, camera_T_world, K, camera_center, rank, opacity_act,
+                                       grad_slab, v_base, N, grad_xyz, grad_quaternion, grad_scale, grad_opacity_logit,
+                                       grad_rgb_param, grad_sh, GS_RASTER_CLASSIC, stream);
 }
 
 int gs_pose_backward(const void* xyz, const void* quaternion, const void* scale, const void* camera_T_world,

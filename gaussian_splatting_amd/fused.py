@@ -310,17 +310,11 @@ def preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world,
     f.uv, f.xyz_cam, f.conic = uv.view(N, 2), xyz_cam.view(N, 3), conic.view(N, 3)
     f.opacity_act, f.rgb_render, f.packed = opa.view(N, 1), rgbr.view(N, 3), packed.view(N, 12)
     f.cut = None
-    if f.raster_mode != _hip.GS_RASTER_CLASSIC:
-        _hip.call("gs_preprocess_forward_mode", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), n_sh,
-                  _p(camera_T_world), _p(K), N, width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, row0,
-                  row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx), _p(f.uv),
-                  _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), None, None, None, 0,
-                  f.raster_mode, stream)
-    else:
-        _hip.call("gs_preprocess_forward", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), n_sh,
-                  _p(camera_T_world), _p(K), N, width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, row0,
-                  row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx), _p(f.uv),
-                  _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), stream)
+    _hip.call("gs_preprocess_forward_mode", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), n_sh,
+              _p(camera_T_world), _p(K), N, width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, row0,
+              row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx), _p(f.uv),
+              _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), None, None, None, 0,
+              f.raster_mode, stream, label="gs_preprocess_forward")
 
     # the plan's record lives right behind (S, V) at the tail of ranges_buf: one host read gets both
     f.subset = (None, None)
@@ -403,18 +397,11 @@ def _preprocess_forward_cut(f, xyz, quaternion, scale, opacity, rgb, sh, camera_
     f.center, uv, xyz_cam, conic, opa, rgbr, packed, bin_rec = far.blocks()
     f.uv, f.xyz_cam, f.conic = uv.view(N, 2), xyz_cam.view(N, 3), conic.view(N, 3)
     f.opacity_act, f.rgb_render, f.packed = opa.view(N, 1), rgbr.view(N, 3), packed.view(N, 12)
-    if f.raster_mode != _hip.GS_RASTER_CLASSIC:
-        _hip.call("gs_preprocess_forward_mode", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), f.n_sh,
-                  _p(camera_T_world), _p(K), N, f.width, f.height, near_thresh, far_thresh, cull_mask_padding, f.mh_dist,
-                  row0, row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx),
-                  _p(f.uv), _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), _p(bin_rec),
-                  _p(cut_ws), _p(_depth_hist(dev)), stride, f.raster_mode, stream)
-    else:
-        _hip.call("gs_preprocess_forward_cut", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), f.n_sh,
-                  _p(camera_T_world), _p(K), N, f.width, f.height, near_thresh, far_thresh, cull_mask_padding, f.mh_dist,
-                  row0, row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx),
-                  _p(f.uv), _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), _p(bin_rec),
-                  _p(cut_ws), _p(_depth_hist(dev)), stride, stream)
+    _hip.call("gs_preprocess_forward_mode", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), f.n_sh,
+              _p(camera_T_world), _p(K), N, f.width, f.height, near_thresh, far_thresh, cull_mask_padding, f.mh_dist,
+              row0, row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx),
+              _p(f.uv), _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), _p(bin_rec),
+              _p(cut_ws), _p(_depth_hist(dev)), stride, f.raster_mode, stream, label="gs_preprocess_forward")
     _hip.call("gs_tile_count_cut", _p(bin_rec), N, _p(f.count), ntx, nty, f.mh_dist, row0, row1,
               _p(f.tile_counts), _p(cut_ws), _p(f.ranges_buf), _p(full_ranges), None, stream)
     f.subset = (None, None)
@@ -488,15 +475,11 @@ def preprocess_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_ba
     grad_xyz, grad_q, grad_scale = gx.view(n, 3), gq.view(n, 4), gs.view(n, 3)
     grad_opacity, grad_rgb = go.view(n, 1), gc.view(n, 3)
     grad_sh = gsh.view(n, 3, f.n_sh - 1) if f.n_sh > 1 else None
-    if n > 0 and mode != _hip.GS_RASTER_CLASSIC:
+    if n > 0:
         _hip.call("gs_preprocess_backward_mode", _p(xyz[i0:i1]), _p(quaternion[i0:i1]), _p(scale[i0:i1]), f.n_sh,
                   _p(camera_T_world), _p(K), _p(f.center), _p(f.rank[i0:i1]), _p(f.opacity_act), _p(slab), v_base, n,
                   _p(grad_xyz), _p(grad_q), _p(grad_scale), _p(grad_opacity), _p(grad_rgb), _p(grad_sh),
-                  mode, _stream())
-    elif n > 0:
-        _hip.call("gs_preprocess_backward", _p(xyz[i0:i1]), _p(quaternion[i0:i1]), _p(scale[i0:i1]), f.n_sh,
-                  _p(camera_T_world), _p(K), _p(f.center), _p(f.rank[i0:i1]), _p(f.opacity_act), _p(slab), v_base, n,
-                  _p(grad_xyz), _p(grad_q), _p(grad_scale), _p(grad_opacity), _p(grad_rgb), _p(grad_sh), _stream())
+                  mode, _stream(), label="gs_preprocess_backward")
     return grad_xyz, grad_q, grad_scale, grad_opacity, grad_rgb, grad_sh
 
 
@@ -510,12 +493,10 @@ def pose_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_base=0, 
     # (two allocations: the gradient outlives the backward, the workspace must not live as long)
     grad = torch.empty(4, 4, dtype=torch.float32, device=xyz.device)
     ws = torch.empty(_hip.lib().gs_pose_workspace_floats(n), dtype=torch.float32, device=xyz.device)
-    if mode != _hip.GS_RASTER_CLASSIC:   # (antialiased: the opacity column reaches the pose through the factor's conic terms)
-        _hip.call("gs_pose_backward_mode", _p(xyz), _p(quaternion), _p(scale), _p(camera_T_world), _p(K), _p(f.rank),
-                  _p(f.opacity_act), _p(slab), v_base, n, _p(ws), _p(grad), mode, _stream())
-    else:
-        _hip.call("gs_pose_backward", _p(xyz), _p(quaternion), _p(scale), _p(camera_T_world), _p(K), _p(f.rank),
-                  _p(slab), v_base, n, _p(ws), _p(grad), _stream())
+    # (antialiased: the opacity column reaches the pose through the factor's conic terms, which need the sigmoid)
+    opacity_act = f.opacity_act if mode & _hip.GS_RASTER_ANTIALIASED else None
+    _hip.call("gs_pose_backward_mode", _p(xyz), _p(quaternion), _p(scale), _p(camera_T_world), _p(K), _p(f.rank),
+              _p(opacity_act), _p(slab), v_base, n, _p(ws), _p(grad), mode, _stream(), label="gs_pose_backward")
     return grad
 
 

@@ -211,27 +211,10 @@ int gs_cut_debug_views(int32_t* cut_workspace, int N, int n_tiles, int32_t** bst
  *            (1 = culled); rank int32[N] (visible index or -1); and, with capacity N rows of which
  *            the first V are written: vis_idx int32, uv[.,2], xyz_camera_frame[.,3], conic[.,3],
  *            opacity_act[.,1] = sigmoid, rgb_render[.,3], packed[.,12] (see gs_pack_splats).  vis_idx and
- *            rgb_render may be NULL (not written: the renderer reads the colour from the packed record). */
+ *            rgb_render may be NULL (not written: the renderer reads the colour from the packed record).
+ * The entry of this form is gs_preprocess_forward, its depth-cut form gs_preprocess_forward_cut (above): both are declared
+ * with the classic entries below and forward to gs_preprocess_forward_mode, which takes a raster mode as well. */
 size_t gs_preprocess_workspace_ints(int N);
-int gs_preprocess_forward(const void* xyz, const void* quaternion, const void* scale,
-                          const void* opacity, const void* rgb, const void* sh, int n_sh,
-                          const void* camera_T_world, const void* K, int N, int W, int H,
-                          float near_thresh, float far_thresh, float cull_mask_padding,
-                          float mh_dist, int band_row0, int band_row1,
-                          int32_t* workspace, void* camera_center, int32_t* visible_count,
-                          uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
-                          void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
-                          void* packed, void* stream);
-int gs_preprocess_forward_cut(const void* xyz, const void* quaternion, const void* scale,
-                              const void* opacity, const void* rgb, const void* sh, int n_sh,
-                              const void* camera_T_world, const void* K, int N, int W, int H,
-                              float near_thresh, float far_thresh, float cull_mask_padding,
-                              float mh_dist, int band_row0, int band_row1,
-                              int32_t* workspace, void* camera_center, int32_t* visible_count,
-                              uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
-                              void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
-                              void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
-                              int sample_stride, void* stream);
 
 /* Backward of the above (projection_backward.cu:9-471, precompute_sh.cu:61-111 and the autograd of
  * the glue: sigmoid', the cat split, the dense scatter of rasterize.py:52-75, matmul').
@@ -244,13 +227,8 @@ int gs_preprocess_forward_cut(const void* xyz, const void* quaternion, const voi
  * A slice [i0, i1) of the Gaussians (multi-GPU: the slice this rank owns) is processed by passing
  * the parameter / rank / output pointers advanced to row i0, N = i1 - i0, and a slab that holds
  * the rows of the slice's visible Gaussians with v_base = their first visible index;
- * opacity_act stays the full array (it is indexed by v). */
-int gs_preprocess_backward(const void* xyz, const void* quaternion, const void* scale, int n_sh,
-                           const void* camera_T_world, const void* K, const void* camera_center,
-                           const int32_t* rank, const void* opacity_act, const void* grad_slab,
-                           int v_base, int N, void* grad_xyz, void* grad_quaternion,
-                           void* grad_scale, void* grad_opacity_logit, void* grad_rgb_param,
-                           void* grad_sh, void* stream);
+ * opacity_act stays the full array (it is indexed by v).
+ * gs_preprocess_backward (classic entries, below) has these arguments, gs_preprocess_backward_mode a raster mode as well. */
 
 /* gs_preprocess_backward with the optimizer step folded in (ABI 9; single-GPU form, no reference counterpart):
  * the gradients are computed exactly as above, grad_xyz[N,3] is written as above, and for quaternion[N,4],
@@ -293,11 +271,9 @@ int gs_preprocess_backward_adam(const void* xyz, int n_sh, const void* camera_T_
  *   output    grad_camera_T_world[4,4] row-major, written (not accumulated), last row 0; all zeros for N == 0 or
  *             when no Gaussian is visible
  * Two launches, no atomics: the sums are added in an order that depends on N only, so equal inputs give equal
- * bits.  Must be enqueued BEFORE gs_preprocess_backward_adam, which overwrites the quaternion and scale it reads. */
+ * bits.  Must be enqueued BEFORE gs_preprocess_backward_adam, which overwrites the quaternion and scale it reads.
+ * gs_pose_backward (classic entries, below) has these arguments, gs_pose_backward_mode opacity_act and a raster mode too. */
 size_t gs_pose_workspace_floats(int N);
-int gs_pose_backward(const void* xyz, const void* quaternion, const void* scale, const void* camera_T_world,
-                     const void* K, const int32_t* rank, const void* grad_slab, int v_base, int N, void* workspace,
-                     void* grad_camera_T_world, void* stream);
 
 /* ---- antialiased opacity (fp32, ABI 14; the 2D factor of Mip-Splatting, no reference counterpart) -----------
  * The fp32 packed record dilates every projected covariance by 0.25 px^2 and leaves the opacity alone, so a splat
@@ -375,6 +351,41 @@ int gs_preprocess_backward_mode(const void* xyz, const void* quaternion, const v
 int gs_pose_backward_mode(const void* xyz, const void* quaternion, const void* scale, const void* camera_T_world,
                           const void* K, const int32_t* rank, const void* opacity_act, const void* grad_slab, int v_base,
                           int N, void* workspace, void* grad_camera_T_world, int raster_mode, void* stream);
+
+/* ---- the classic per-Gaussian entries: one-line forwards, kept for callers outside the package ----
+ *   gs_preprocess_forward      -> gs_preprocess_forward_cut with bin_records, cut_workspace, depth_hist NULL, sample_stride 0
+ *   gs_preprocess_forward_cut  -> gs_preprocess_forward_mode with GS_RASTER_CLASSIC
+ *   gs_preprocess_backward     -> gs_preprocess_backward_mode with GS_RASTER_CLASSIC
+ *   gs_pose_backward           -> gs_pose_backward_mode with opacity_act NULL and GS_RASTER_CLASSIC
+ * The package's own callers (fused.py, csrc/frame_hip.cpp) call the _mode entries in every mode. */
+int gs_preprocess_forward(const void* xyz, const void* quaternion, const void* scale,
+                          const void* opacity, const void* rgb, const void* sh, int n_sh,
+                          const void* camera_T_world, const void* K, int N, int W, int H,
+                          float near_thresh, float far_thresh, float cull_mask_padding,
+                          float mh_dist, int band_row0, int band_row1,
+                          int32_t* workspace, void* camera_center, int32_t* visible_count,
+                          uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
+                          void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
+                          void* packed, void* stream);
+int gs_preprocess_forward_cut(const void* xyz, const void* quaternion, const void* scale,
+                              const void* opacity, const void* rgb, const void* sh, int n_sh,
+                              const void* camera_T_world, const void* K, int N, int W, int H,
+                              float near_thresh, float far_thresh, float cull_mask_padding,
+                              float mh_dist, int band_row0, int band_row1,
+                              int32_t* workspace, void* camera_center, int32_t* visible_count,
+                              uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
+                              void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
+                              void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
+                              int sample_stride, void* stream);
+int gs_preprocess_backward(const void* xyz, const void* quaternion, const void* scale, int n_sh,
+                           const void* camera_T_world, const void* K, const void* camera_center,
+                           const int32_t* rank, const void* opacity_act, const void* grad_slab,
+                           int v_base, int N, void* grad_xyz, void* grad_quaternion,
+                           void* grad_scale, void* grad_opacity_logit, void* grad_rgb_param,
+                           void* grad_sh, void* stream);
+int gs_pose_backward(const void* xyz, const void* quaternion, const void* scale, const void* camera_T_world,
+                     const void* K, const int32_t* rank, const void* grad_slab, int v_base, int N, void* workspace,
+                     void* grad_camera_T_world, void* stream);
 
 /* ---- tile renderer ---------------------------------------------------------------------------- */
 /* Packs what the render kernels read per splat into one 48-byte (fp32) record per visible Gaussian:

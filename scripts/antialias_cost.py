@@ -4,10 +4,10 @@
 
 One process: per workload the scene once, a spin-up, then `--rounds` alternating blocks (classic, antialiased) of
 `--reps` iterations each of
-  forward    the per-Gaussian forward's entry point (gs_preprocess_forward / gs_preprocess_forward_mode: k_cull_count,
+  forward    the per-Gaussian forward's entry point (gs_preprocess_forward_mode, booked as gs_preprocess_forward: k_cull_count,
              k_scan_counts and k_preprocess -- only the last differs between the modes), events around the C-ABI call
              (gaussian_splatting_amd._hip.enable_timing)
-  backward   gs_preprocess_backward / gs_preprocess_backward_mode (k_preprocess_bwd alone) on one fixed random slab
+  backward   gs_preprocess_backward_mode, booked as gs_preprocess_backward (k_preprocess_bwd alone) on one fixed random slab
   frame      fused.rasterize + image.backward() through the default (native) orchestration, events around the pair
 The record holds the median and minimum per mode over all blocks, the per-round medians, the spread of the classic
 blocks (max - min of their per-round medians) and antialiased - classic next to it: the mode adds no memory traffic, so
@@ -23,8 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 MODES = ("classic", "antialiased")
-ENTRY = {"gs_preprocess_forward": ("classic", "forward"), "gs_preprocess_forward_mode": ("antialiased", "forward"),
-         "gs_preprocess_backward": ("classic", "backward"), "gs_preprocess_backward_mode": ("antialiased", "backward")}
+ENTRY = {"gs_preprocess_forward": "forward", "gs_preprocess_backward": "backward"}   # the labels both modes book under
 
 
 def measure(workload, rounds, reps):
@@ -76,8 +75,8 @@ def measure(workload, rounds, reps):
             for _ in range(reps):
                 stage_pass(m)
             for entry, ms in _hip.collect_timing().items():
-                if entry in ENTRY and ENTRY[entry][0] == m:
-                    what = ENTRY[entry][1]
+                if entry in ENTRY:   # (this block ran mode m only)
+                    what = ENTRY[entry]
                     row[m][what] = round(statistics.median(ms), 4)
                     pooled[m][what].extend(ms)
             _hip.enable_timing(False)

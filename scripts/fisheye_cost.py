@@ -4,10 +4,10 @@
 
 One process: per workload the scene once, a spin-up, then `--rounds` alternating blocks (pinhole, fisheye) of `--reps`
 iterations each of
-  forward    the per-Gaussian forward's entry point (gs_preprocess_forward / gs_preprocess_forward_mode: k_cull_count,
+  forward    the per-Gaussian forward's entry point (gs_preprocess_forward_mode, booked as gs_preprocess_forward: k_cull_count,
              k_scan_counts and k_preprocess -- the first and the last differ between the models), events around the
              C-ABI call (gaussian_splatting_amd._hip.enable_timing)
-  backward   gs_preprocess_backward / gs_preprocess_backward_mode (k_preprocess_bwd alone) on one fixed random slab
+  backward   gs_preprocess_backward_mode, booked as gs_preprocess_backward (k_preprocess_bwd alone) on one fixed random slab
   frame      fused.rasterize + image.backward() through the default (native) orchestration, events around the pair
 The fisheye model draws the same directions closer to the principal point (theta < tan theta), so with the scene's K
 it sees more Gaussians than the pinhole model; the fisheye blocks run with fx, fy scaled by the factor (searched over
@@ -26,8 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 MODES = ("pinhole", "fisheye")
-ENTRY = {"gs_preprocess_forward": ("pinhole", "forward"), "gs_preprocess_forward_mode": ("fisheye", "forward"),
-         "gs_preprocess_backward": ("pinhole", "backward"), "gs_preprocess_backward_mode": ("fisheye", "backward")}
+ENTRY = {"gs_preprocess_forward": "forward", "gs_preprocess_backward": "backward"}   # the labels both modes book under
 
 
 def measure(workload, rounds, reps):
@@ -90,8 +89,8 @@ def measure(workload, rounds, reps):
             for _ in range(reps):
                 stage_pass(m)
             for entry, ms in _hip.collect_timing().items():
-                if entry in ENTRY and ENTRY[entry][0] == m:
-                    what = ENTRY[entry][1]
+                if entry in ENTRY:   # (this block ran mode m only)
+                    what = ENTRY[entry]
                     row[m][what] = round(statistics.median(ms), 4)
                     pooled[m][what].extend(ms)
             _hip.enable_timing(False)

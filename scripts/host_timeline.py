@@ -36,9 +36,9 @@ marks = []
 orig_call = _hip.call
 
 
-def timed_call(name, *args):
+def timed_call(name, *args, **kw):
     t0 = time.perf_counter()
-    orig_call(name, *args)
+    orig_call(name, *args, **kw)
     marks.append((name, t0, time.perf_counter()))
 
 

@@ -185,6 +185,67 @@ def test_frame_without_a_pose_gradient_launches_nothing_new(mode):
     assert T.grad is not None
 
 
+RASTER_MODES = {"classic": {}, "antialiased": dict(antialiased=True), "fisheye": dict(camera_model="fisheye")}
+STEP_LABELS = ("gs_preprocess_forward", "gs_preprocess_backward", "gs_pose_backward")
+
+
+@functools.lru_cache(maxsize=None)
+def booked_frame(orch, raster):
+    """One forward and one backward, under _hip.enable_timing, of a frame whose pose requires a gradient: 700 Gaussians
+    (two whole 256-thread workgroups and a ragged third, some rows culled) on 517 x 301.  Computed once per case.
+    The orchestration is chosen with fused.NATIVE: orchestration()'s frame_hook is refused by the antialiased and
+    fisheye frames; it still skips the native case where the module is not built."""
+    orchestration(orch)
+    sc, g, cam, T, args = frame_scene(N=700)
+    T.requires_grad_(True)
+    w = make_grad_image(sc.W, sc.H, seed=4, device=DEV)
+    prev = fused.NATIVE
+    fused.NATIVE = orch == "native"
+    fused.keep_last_slab(True)
+    _hip.enable_timing(True)
+    try:
+        image, culling_mask, uv = fused.rasterize(g, T, cam, *args, **RASTER_MODES[raster])
+        (image * w).sum().backward()
+        booked = _hip.collect_timing()
+        slab = fused.last_slab()
+    finally:
+        _hip.enable_timing(False)
+        fused.keep_last_slab(False)
+        fused.NATIVE = prev
+    assert bool(culling_mask.any()) and not bool(culling_mask.all())
+    grads = {k: getattr(g, k).grad for k in PARAMS}
+    return SimpleNamespace(image=image.detach(), mask=culling_mask, slab=slab.contiguous(), grads=grads, pose=T.grad,
+                           booked={k: len(v) for k, v in booked.items()})
+
+
+@pytest.mark.parametrize("raster", list(RASTER_MODES))
+@pytest.mark.parametrize("orch", ["python", "native"])
+def test_one_general_call_per_step_in_every_mode(orch, raster):
+    """Both orchestrations make one call per per-Gaussian step, to the general entry, and book it under the step's name
+    in every mode; nothing is booked under a name ending in _mode.  The two orchestrations give the same image bit for
+    bit.  Their gradients are compared through the slab each frame's own render backward left (its atomics' summation
+    order differs from run to run, so two frames' gradients are not comparable directly): the six leaf gradients and
+    the pose's are torch.equal to the per-Gaussian backward of that slab at the stage level -- one function of the
+    slab for both orchestrations."""
+    fr = booked_frame(orch, raster)
+    for label in STEP_LABELS:
+        assert fr.booked.get(label) == 1, (label, fr.booked)
+    assert not [k for k in fr.booked if k.endswith("_mode")], fr.booked
+    if fused.native() is not None:
+        other = booked_frame("native" if orch == "python" else "python", raster)
+        assert torch.equal(fr.image, other.image) and torch.equal(fr.mask, other.mask)
+    sc, g, cam, T, args = frame_scene(N=700)
+    f = fused.preprocess_forward(g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, T, cam.K, sc.W, sc.H, sc.near,
+                                 sc.far, sc.pad, sc.mh, None, 0, **RASTER_MODES[raster])
+    assert f.V == fr.slab.shape[0] and 0 < f.V < 700
+    with torch.no_grad():
+        want = fused.preprocess_backward(g.xyz, g.quaternion, g.scale, T, cam.K, f, fr.slab, **RASTER_MODES[raster])
+        pose = fused.pose_backward(g.xyz, g.quaternion, g.scale, T, cam.K, f, fr.slab, **RASTER_MODES[raster])
+    for k, wk in zip(PARAMS, want):
+        assert bool(wk.any()) and torch.equal(fr.grads[k], wk), k
+    assert bool(pose.any()) and torch.equal(fr.pose, pose)
+
+
 def test_leaf_gradients_do_not_depend_on_the_pose_gradient():
     """the per-Gaussian node with and without a pose that requires grad, fed the same render gradients: the six leaf
     gradients are torch.equal"""
