@@ -429,7 +429,10 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
     static variable_list forward(AutogradContext* ctx, Tensor xyz, Tensor quaternion, Tensor scale, Tensor opacity,
                                  Tensor rgb, c10::optional<Tensor> sh_opt, Tensor camera_T_world, Tensor K, Tensor bg,
                                  int64_t W, int64_t H, double near_thresh, double far_thresh, double padding,
-                                 double mh_dist, int64_t row0, int64_t row1, PlanHolder adam_plan, int64_t raster_mode) {
+                                 double mh_dist, int64_t row0, int64_t row1, PlanHolder adam_plan, int64_t raster_mode,
+                                 c10::optional<Tensor> filter3d_opt) {
+        // filter3d: the 3D smoothing filter's variances [N] (a constant: no edge), or nothing -- the _filtered entries with
+        // NULL launch what the _mode entries launch
         // raster_mode: the bit mask of include/gsplat_hip.h.  GS_RASTER_ANTIALIASED: the record's opacity carries
         // sqrt(det Sigma_2D / det(Sigma_2D + 0.25 I)); GS_RASTER_FISHEYE: uv, the cull and the projection Jacobian are the
         // equidistant fisheye model's.  Only the per-Gaussian kernels differ, forward and backward -- binning, sort and
@@ -439,6 +442,8 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
         const bool has_sh = sh_opt.has_value() && sh_opt->defined();
         Tensor sh = has_sh ? sh_opt->contiguous() : Tensor();
         const int n_sh = has_sh ? (int)sh.size(2) + 1 : 1;
+        const bool has_filter = filter3d_opt.has_value() && filter3d_opt->defined();
+        Tensor filter3d = has_filter ? filter3d_opt->contiguous() : Tensor();
         const int ntx = ((int)W + 15) / 16, nty = ((int)H + 15) / 16, T = ntx * nty;
         const bool whole = row0 == 0 && row1 == nty;
         const int sort_prefix = g_policy.sort_prefix ? GS_SORT_PREFIX : 0;
@@ -469,14 +474,15 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
         const float* rgbr = packed;
         int32_t* depth_hist = cut ? depth_hist_of(dev, stream) : nullptr;
         timed("gs_preprocess_forward", stream, [&] {
-            return gs_preprocess_forward_mode(
+            return gs_preprocess_forward_filtered(
                 xyz.data_ptr(), quaternion.data_ptr(), scale.data_ptr(), opacity.data_ptr(), rgb.data_ptr(),
                 has_sh ? sh.data_ptr() : nullptr, n_sh, camera_T_world.data_ptr(), K.data_ptr(), N, (int)W, (int)H,
                 (float)near_thresh, (float)far_thresh, (float)padding, (float)mh_dist, (int)row0, (int)row1, ws, center,
                 count, mask, rank, nullptr /* vis_idx: nobody reads it on this path */, cut ? nullptr : uv,
                 cut ? nullptr : xyz_cam, cut ? nullptr : conic, opa,
                 nullptr /* rgb_render: the colour is in the packed record */, packed, cut ? bin_rec : nullptr,
-                cut ? cut_ws : nullptr, depth_hist, stride, (int)raster_mode, stream);
+                cut ? cut_ws : nullptr, depth_hist, stride, has_filter ? filter3d.data_ptr() : nullptr, (int)raster_mode,
+                stream);
         });
         const FrameKind kind{cut, sort_prefix, !cut && sort_prefix != 0, true};
         const FramePlan plan = plan_frame(start.st, g_policy, kind);
@@ -568,6 +574,7 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
         // (recorded here: the node's edge indices skip an absent sh, its backward cannot ask by argument position)
         ctx->saved_data["pose_grad"] = camera_T_world.requires_grad();
         ctx->saved_data["raster_mode"] = raster_mode;
+        if (has_filter) ctx->saved_data["filter3d"] = filter3d;   // (a constant without a graph: no cycle through the node)
         ctx->set_materialize_grads(false);
         ctx->mark_non_differentiable(variable_list(o.begin() + PRE_PACKED, o.end()));
         return o;
@@ -610,7 +617,8 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
         }
         const int64_t n = N, extra = 3 * (int64_t)(n_sh - 1);
         const int raster_mode = (int)ctx->saved_data["raster_mode"].toInt();
-        variable_list out(19);
+        const void* filter3d = ctx->saved_data.count("filter3d") ? ctx->saved_data["filter3d"].toTensor().data_ptr() : nullptr;
+        variable_list out(20);
         if (g_keep_slab) note_slab(slab.narrow(0, 0, V));
         // camera_T_world's gradient (gs_pose_backward), before the fused optimizer step, which overwrites the quaternion
         // and scale the pose terms read
@@ -620,10 +628,10 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
             Tensor grad_pose = torch::empty({4, 4}, xyz.options());
             Tensor ws = torch::empty({(int64_t)gs_pose_workspace_floats(N)}, xyz.options());
             timed("gs_pose_backward", stream, [&] {
-                return gs_pose_backward_mode(xyz.data_ptr(), quaternion.data_ptr(), scale.data_ptr(),
-                                             camera_T_world.data_ptr(), K.data_ptr(), rank.data_ptr<int32_t>(),
-                                             opacity_act.data_ptr(), slab.data_ptr(), 0, N, ws.data_ptr(),
-                                             grad_pose.data_ptr(), raster_mode, stream);
+                return gs_pose_backward_filtered(xyz.data_ptr(), quaternion.data_ptr(), scale.data_ptr(),
+                                                 camera_T_world.data_ptr(), K.data_ptr(), rank.data_ptr<int32_t>(),
+                                                 opacity_act.data_ptr(), slab.data_ptr(), 0, N, ws.data_ptr(),
+                                                 grad_pose.data_ptr(), filter3d, raster_mode, stream);
             });
             out[6] = grad_pose;
         }
@@ -666,11 +674,11 @@ struct Preprocess : public torch::autograd::Function<Preprocess> {
         if (n > 0) {
             void* stream = cur_stream();
             timed("gs_preprocess_backward", stream, [&] {
-                return gs_preprocess_backward_mode(xyz.data_ptr(), quaternion.data_ptr(), scale.data_ptr(), n_sh,
-                                                   camera_T_world.data_ptr(), K.data_ptr(), center.data_ptr(),
-                                                   rank.data_ptr<int32_t>(), opacity_act.data_ptr(), slab.data_ptr(), 0,
-                                                   (int)n, ga.ptr(0), ga.ptr(1), ga.ptr(2), ga.ptr(3), ga.ptr(4),
-                                                   ga.ptr(5), raster_mode, stream);
+                return gs_preprocess_backward_filtered(xyz.data_ptr(), quaternion.data_ptr(), scale.data_ptr(), n_sh,
+                                                       camera_T_world.data_ptr(), K.data_ptr(), center.data_ptr(),
+                                                       rank.data_ptr<int32_t>(), opacity_act.data_ptr(), slab.data_ptr(), 0,
+                                                       (int)n, ga.ptr(0), ga.ptr(1), ga.ptr(2), ga.ptr(3), ga.ptr(4),
+                                                       ga.ptr(5), filter3d, raster_mode, stream);
             });
         }
         ga.views(out);
@@ -748,12 +756,21 @@ std::tuple<Tensor, Tensor, Tensor> rasterize_impl(Tensor xyz, Tensor quaternion,
                                                   int64_t height, double near_thresh, double far_thresh,
                                                   double cull_mask_padding, double mh_dist, Tensor background_rgb,
                                                   int64_t row0, int64_t row1, PlanHolder adam_plan,
-                                                  int64_t raster_mode = GS_RASTER_CLASSIC) {
+                                                  int64_t raster_mode = GS_RASTER_CLASSIC,
+                                                  c10::optional<Tensor> filter3d = c10::nullopt) {
+    const bool filtered = filter3d.has_value() && filter3d->defined();
     const bool antialiased = (raster_mode & GS_RASTER_ANTIALIASED) != 0, fisheye = (raster_mode & GS_RASTER_FISHEYE) != 0;
     TORCH_CHECK((raster_mode & ~(int64_t)(GS_RASTER_ANTIALIASED | GS_RASTER_FISHEYE)) == 0,
                 "raster_mode must be a combination of GS_RASTER_ANTIALIASED and GS_RASTER_FISHEYE, got ", raster_mode);
     TORCH_CHECK(!(antialiased && adam_plan), "antialiased frames do not take the fused optimizer step");
     TORCH_CHECK(!(fisheye && adam_plan), "fisheye frames do not take the fused optimizer step");
+    TORCH_CHECK(!(filtered && adam_plan), "filter3d frames do not take the fused optimizer step");
+    if (filtered) {
+        TORCH_CHECK(filter3d->is_cuda() && filter3d->device() == xyz.device() && filter3d->scalar_type() == torch::kFloat32 &&
+                        filter3d->dim() == 1 && filter3d->size(0) == xyz.size(0),
+                    "filter3d must be float32 [N] on the Gaussians' device, one variance per Gaussian");
+        TORCH_CHECK(!filter3d->requires_grad(), "filter3d is a constant of the frame and must not require a gradient");
+    }
     check_frame_inputs(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, background_rgb, width, height);
     const auto dev = xyz.device();
     const int64_t nty = (height + 15) / 16;
@@ -761,11 +778,12 @@ std::tuple<Tensor, Tensor, Tensor> rasterize_impl(Tensor xyz, Tensor quaternion,
     TORCH_CHECK(0 <= row0 && row0 <= row1 && row1 <= nty, "bad tile row range");
     TORCH_CHECK(!antialiased || (row0 == 0 && row1 == nty), "antialiased frames are whole frames (no tile-row band)");
     TORCH_CHECK(!fisheye || (row0 == 0 && row1 == nty), "fisheye frames are whole frames (no tile-row band)");
+    TORCH_CHECK(!filtered || (row0 == 0 && row1 == nty), "filter3d frames are whole frames (no tile-row band)");
     c10::DeviceGuard guard(dev);
     auto o = Preprocess::apply(xyz.contiguous(), quaternion.contiguous(), scale.contiguous(), opacity.contiguous(),
                                rgb.contiguous(), sh, camera_T_world.contiguous(), K.contiguous(), background_rgb.contiguous(),
                                width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, row0, row1, adam_plan,
-                               raster_mode);
+                               raster_mode, filter3d);
     Tensor image = Render::apply(o[PRE_UV], o[PRE_CONIC], o[PRE_OPACITY], o[PRE_RGB], o[PRE_PACKED], o[PRE_RANGES],
                                  o[PRE_SORTED], background_rgb.contiguous(), o[PRE_IMAGE], o[PRE_FW], o[PRE_NSP], o[PRE_SEG],
                                  o[PRE_CUT_FLAGS], o[PRE_FULL_RANGES], o[PRE_OVERFLOW], o[PRE_MASKS], row0, row1);
@@ -776,9 +794,9 @@ std::tuple<Tensor, Tensor, Tensor> rasterize(Tensor xyz, Tensor quaternion, Tens
                                              c10::optional<Tensor> sh, Tensor camera_T_world, Tensor K, int64_t width,
                                              int64_t height, double near_thresh, double far_thresh, double cull_mask_padding,
                                              double mh_dist, Tensor background_rgb, int64_t row0, int64_t row1,
-                                             int64_t raster_mode) {
+                                             int64_t raster_mode, c10::optional<Tensor> filter3d) {
     return rasterize_impl(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, width, height, near_thresh, far_thresh,
-                          cull_mask_padding, mh_dist, background_rgb, row0, row1, PlanHolder(), raster_mode);
+                          cull_mask_padding, mh_dist, background_rgb, row0, row1, PlanHolder(), raster_mode, filter3d);
 }
 
 // the same frame with the optimizer step of quaternion, scale, opacity, rgb and sh inside its backward
@@ -1525,7 +1543,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("scale"), py::arg("opacity"), py::arg("rgb"), py::arg("sh"), py::arg("camera_T_world"), py::arg("K"),
           py::arg("width"), py::arg("height"), py::arg("near_thresh"), py::arg("far_thresh"), py::arg("cull_mask_padding"),
           py::arg("mh_dist"), py::arg("background_rgb"), py::arg("row0") = 0, py::arg("row1") = -1,
-          py::arg("raster_mode") = (int64_t)GS_RASTER_CLASSIC);
+          py::arg("raster_mode") = (int64_t)GS_RASTER_CLASSIC, py::arg("filter3d") = py::none());
     m.def("rasterize_adam", &rasterize_adam,
           "fused frame whose backward steps quaternion, scale, opacity, rgb and sh (Adam) itself: -> (image, culling_mask, uv)",
           py::arg("xyz"), py::arg("quaternion"), py::arg("scale"), py::arg("opacity"), py::arg("rgb"), py::arg("sh"),

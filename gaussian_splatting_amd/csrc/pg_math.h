@@ -48,6 +48,13 @@ __device__ inline void load_rotation(const T* __restrict__ M, T* W) {   // proje
     W[6] = M[8]; W[7] = M[9]; W[8] = M[10];
 }
 
+// utils.py:60-72 as explicit fp32 arithmetic: ((m0*x + m1*y) + m2*z) + m3
+__device__ inline void to_camera(const float* __restrict__ M, float x, float y, float z, float* c) {
+    c[0] = M[0] * x + M[1] * y + M[2] * z + M[3];
+    c[1] = M[4] * x + M[5] * y + M[6] * z + M[7];
+    c[2] = M[8] * x + M[9] * y + M[10] * z + M[11];
+}
+
 // projection.cu:214-257
 template <typename T>
 __device__ inline void conic_of(const T* J6, const T* W, const T* S9, T* conic3) {
@@ -311,16 +318,81 @@ __device__ inline AaTerms aa_terms_of(const float* conic3) {
 // The backward of opa_eff = y * comp folded into one row of the render-gradient slab, in registers: g = dL/d opa_eff
 // (slab column 3) becomes dL/dy, and the conic columns gain dL/d opa_eff * y * d comp / d conic -- the true derivative,
 // no epsilon (d comp / d rho = 0.5 / comp grows without bound as det_0 cancels; comp == 0 rows get nothing).
+// WIDE (the F3D instantiations): a filter can make a splat millions of pixels wide, and from det_d ~ 1e19 on det_d^2 and
+// c0 det_d leave fp32's range (inf / inf).  Beyond det_d > 1e18 the same three terms are formed as (c0 - rho c) / det_d,
+// b (rho - 1) / det_d, (a0 - rho a) / det_d, whose products stay finite; below, the expressions -- and bits -- are the
+// ones every other instantiation has.  (A wider band, not every magnitude: from conic ~ 1e19 det_0 and det_d are infinite
+// themselves and comp = sqrt(inf / inf) is not a number, as in 7e without a filter.  tests/test_gpu_filter3d.py puts rows on both sides of the threshold.)
+template <bool WIDE = false>
 __device__ inline void aa_fold_row(const AaTerms& t, float y, float& g_opa, float* gc3) {
     const float g = g_opa;
     g_opa = g * t.comp;
     if (t.comp > 0.0f) {
         const float g_rho = g * y * 0.5f / t.comp;
+        if constexpr (WIDE) {
+            if (t.det_d > 1e18f) {
+                const float rho = t.det_0 / t.det_d;
+                gc3[0] += g_rho * (t.c0 - rho * t.c) / t.det_d;
+                gc3[1] += g_rho * t.b * (rho - 1.0f) / t.det_d;
+                gc3[2] += g_rho * (t.a0 - rho * t.a) / t.det_d;
+                return;
+            }
+        }
         const float dd = t.det_d * t.det_d;
         gc3[0] += g_rho * (t.c0 * t.det_d - t.det_0 * t.c) / dd;
         gc3[1] += g_rho * t.b * (t.det_0 - t.det_d) / dd;   // conic1 = 2 b
         gc3[2] += g_rho * (t.a0 * t.det_d - t.det_0 * t.a) / dd;
     }
+}
+
+// ---- 3D smoothing filter (the filter3d argument of the _filtered entries; include/gsplat_hip.h "3D smoothing filter",
+// DESIGN.md 7k) ----
+// phi >= 0 is a per-Gaussian world-space variance, a constant of the frame.  The filter is isotropic:
+// R diag(s^2 + phi) R^T = Sigma + phi I, so the forward adds phi to the diagonal of what sigma_world_of returned and the
+// covariance's gradient passes through sigma_world_bwd_of on the unfiltered scale unchanged.  With s_k = exp(scale_k)
+// (sigma_world_of's expression, squared as there):
+//     rho3  = ((s_0^2 / (s_0^2 + phi)) * (s_1^2 / (s_1^2 + phi))) * (s_2^2 / (s_2^2 + phi))
+//     comp3 = rho3 > 0 ? sqrt(rho3) : 0                     (a NaN compares false)
+//     opa3  = sigmoid(opacity) * comp3                      (what the record, and comp of 7e, multiply)
+//     d opa3 / d scale_k = opa3 phi / (s_k^2 + phi)         (no epsilon; a comp3 == 0 row gets no term)
+// fp32, no contraction, IEEE divide and square root.  With phi == 0 every step is exact (x + 0, s^2 / s^2 = 1, sqrt(1) = 1,
+// y * 1, + 0): such a row carries the values of the call without a filter.  The forward (k_preprocess) and both backwards
+// (k_preprocess_bwd, k_pose_bwd) call these functions.
+__device__ inline void filter3d_sigma(float* S9, float phi) {
+    S9[0] += phi;
+    S9[4] += phi;
+    S9[8] += phi;
+}
+
+// comp3 and the three denominators d[k] = s_k^2 + phi, the exponentials evaluated once
+struct F3dTerms {
+    float comp3, d[3];
+};
+__device__ inline F3dTerms filter3d_terms_of(const float* s3, float phi) {
+    F3dTerms t;
+    float rho3 = 1.0f;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float e = gexp<float>(s3[k]);
+        const float s2 = e * e;
+        t.d[k] = s2 + phi;
+        rho3 *= s2 / t.d[k];
+    }
+    t.comp3 = rho3 > 0.0f ? __builtin_sqrtf(rho3) : 0.0f;
+    return t;
+}
+__device__ inline float filter3d_comp_of(const float* s3, float phi) { return filter3d_terms_of(s3, phi).comp3; }
+
+// The backward of opa3 = y comp3 for g_opa3 = dL/d opa3: -> the opacity-logit gradient, and ts[k] = the term the scale
+// gradient gains, g_opa3 opa3 phi / (s_k^2 + phi); zeros for a comp3 == 0 row.  Formed where the caller has the terms, ahead
+// of the covariance's backward: three values cross it instead of phi, comp3, y and g_opa3.
+__device__ inline float filter3d_bwd_of(const F3dTerms& t, float phi, float y, float g_opa3, float* ts) {
+    ts[0] = ts[1] = ts[2] = 0.0f;
+    if (!(t.comp3 > 0.0f)) return 0.0f;
+    const float num = g_opa3 * (y * t.comp3) * phi;
+#pragma unroll
+    for (int k = 0; k < 3; k++) ts[k] = num / t.d[k];
+    return g_opa3 * t.comp3 * (1.0f - y) * y;
 }
 
 // projection_backward.cu:174-315

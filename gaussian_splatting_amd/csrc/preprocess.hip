@@ -61,15 +61,11 @@ __device__ inline void camera_center(const float* __restrict__ M, float* __restr
     center[2] = (float)(-(inv[6] * tx + inv[7] * ty + inv[8] * tz));
 }
 
-// utils.py:60-72 as explicit fp32 arithmetic: ((m0*x + m1*y) + m2*z) + m3
-__device__ inline void to_camera(const float* __restrict__ M, float x, float y, float z, float* c) {
-    c[0] = M[0] * x + M[1] * y + M[2] * z + M[3];
-    c[1] = M[4] * x + M[5] * y + M[6] * z + M[7];
-    c[2] = M[8] * x + M[9] * y + M[10] * z + M[11];
-}
-
 // What a camera model's projection leaves for its Jacobian and backward: the fisheye terms, or nothing (pinhole)
 struct NoTerms {};
+// The F3D instantiations' trailing argument: the filter variances phi [N] (csrc/pg_math.h "3D smoothing filter"), or nothing
+struct NoFilter {};
+template <bool F3D> using FilterArg = std::conditional_t<F3D, const float*, NoFilter>;
 template <bool FISH> using CamTerms = std::conditional_t<FISH, FisheyeTerms, NoTerms>;
 
 // FISH (GS_RASTER_FISHEYE): uv is the equidistant fisheye projection (pg_math.h: fisheye_project); the test keeps its
@@ -330,12 +326,15 @@ struct Band {
 // radius is taken for that opacity; everything else the kernel writes -- o.opacity, the sigmoid, included -- is unchanged.
 // FISH (GS_RASTER_FISHEYE, whole frames): uv, the cull and J are the fisheye model's (pg_math.h: fisheye_terms_of); the
 // camera-frame position, the depth the binning sorts and cuts by, the sigmoid and the colour keep the pinhole call's bits.
-template <int N_SH, bool BAND, bool AA = false, bool FISH = false>
+// F3D (the _filtered entry with a filter, whole frames): Sigma_world gains filter3d[g] on its diagonal before the conic and
+// the record's opacity the factor comp3 (pg_math.h: filter3d_sigma, filter3d_comp_of) -- under AA the value comp multiplies;
+// o.opacity stays the sigmoid, and uv, xyz_cam, the colour, the cull, rank and vis_idx do not depend on the filter.
+template <int N_SH, bool BAND, bool AA = false, bool FISH = false, bool F3D = false>
 __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))) void k_preprocess(
     const float* __restrict__ xyz, const float* __restrict__ quat, const float* __restrict__ scale,
     const float* __restrict__ opacity, const float* __restrict__ rgb, const float* __restrict__ sh,
     const float* __restrict__ M, const float* __restrict__ K, const float* __restrict__ center,
-    int N, Frustum fr, const int* __restrict__ block_offsets, PreOut o, Band band) {
+    int N, Frustum fr, const int* __restrict__ block_offsets, PreOut o, Band band, FilterArg<F3D> filter3d = {}) {
     __shared__ int s_cnt[PP_BLOCK / GS_WAVE];
     // The workgroup's SH coefficients are one contiguous block of 256 * 3 * (N_SH-1) floats: fetched
     // with coalesced 16-byte loads into LDS (a per-thread walk over its own 180-byte row makes every
@@ -364,6 +363,7 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))
     constexpr int SH_PRE = (N_SH > 1 && !BAND) ? (HALF * SHW / 4 + PP_BLOCK - 1) / PP_BLOCK : 1;
     vfloat4 pre[2][SH_PRE];   // both halves: 48 registers at degree 3 -- the LDS staging, not the registers, sets the occupancy
     float q4[4] = {0, 0, 0, 1}, s3[3] = {0, 0, 0}, opa_raw = 0;
+    [[maybe_unused]] float phi = 0, comp3 = 1;
     if (g < N) {
         p[0] = xyz[g * 3 + 0]; p[1] = xyz[g * 3 + 1]; p[2] = xyz[g * 3 + 2];
         if constexpr (!BAND) {
@@ -371,6 +371,7 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))
             s3[0] = scale[g * 3 + 0]; s3[1] = scale[g * 3 + 1]; s3[2] = scale[g * 3 + 2];
             opa_raw = opacity[g];
         }
+        if constexpr (F3D) phi = filter3d[g];
     }
     if constexpr (N_SH > 1 && !BAND) {   // the SH block -> pre[][] (coalesced 16-byte non-temporal loads)
 #pragma unroll
@@ -421,6 +422,11 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))
         }
         float S9[9], W[9], J6[6];
         sigma_world_of(q4, s3, S9);
+        if constexpr (F3D) {
+            static_assert(!BAND, "the 3D smoothing filter serves whole frames");
+            filter3d_sigma(S9, phi);
+            comp3 = filter3d_comp_of(s3, phi);
+        }
         load_rotation(M, W);
         if constexpr (FISH) {
             static_assert(!BAND, "the fisheye mode serves whole frames");
@@ -499,6 +505,7 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))
 
     // packed render record, identical to k_pack
     float pk[GS_PACKED_WIDTH];
+    if constexpr (F3D) opa = opa * comp3;   // opa3 (o.opacity, the sigmoid, is written)
     if constexpr (AA) {
         static_assert(!BAND, "the antialiased mode serves whole frames");
         const AaTerms t = aa_terms_of(c3);
@@ -506,6 +513,9 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))
         if (!(t.comp > 0.0f)) pk[2] = -1.0f;   // never contributes, whatever the dilated conic is
     } else {
         pack_record<float>(uv[0], uv[1], c3, opa, col, pk);
+    }
+    if constexpr (F3D) {
+        if (!(comp3 > 0.0f)) pk[2] = -1.0f;
     }
     store_record(o.packed, (size_t)v, pk);
 }
@@ -995,14 +1005,18 @@ constexpr bool adam_rows_early(int n_sh) { return n_sh < 16; }
 // aa_fold_row) with comp recomputed from the S9, J6, W at hand -- the forward's functions on the forward's bits.
 // FISH (GS_RASTER_FISHEYE): J is the fisheye model's and gJ6 (all six entries) and the uv columns reach the camera-frame
 // position through fisheye_cam_grad_of (pg_math.h); everything before J and after gcam is the same text.
-template <int N_SH, bool GATHER = false, bool ADAM = false, bool AA = false, bool FISH = false>
+// F3D (the _filtered entry with a filter): S9 is Sigma_eff, slab column 3 (after AA's fold, which then takes opa3 in the place
+// of y) is dL/d opa3: the opacity gradient gains comp3 and the scale gradient its filter term,
+// formed ahead of the covariance's backward (pg_math.h: filter3d_bwd_of); its three values are added behind sigma_world_bwd_of.
+template <int N_SH, bool GATHER = false, bool ADAM = false, bool AA = false, bool FISH = false, bool F3D = false>
 __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_preprocess_bwd(
     const float* __restrict__ xyz, const float* __restrict__ quat, const float* __restrict__ scale,
     const float* __restrict__ M, const float* __restrict__ K, const float* __restrict__ center,
     const int* __restrict__ rank, const float* __restrict__ opacity_act,
     const float* __restrict__ g_slab, int v_base, int N, PreGrad o, GatherPlan gp = GatherPlan{},
-    std::conditional_t<ADAM, PreAdam, NoAdam> ad = {}) {
+    std::conditional_t<ADAM, PreAdam, NoAdam> ad = {}, FilterArg<F3D> filter3d = {}) {
     static_assert(!(ADAM && GATHER), "the fused optimizer step serves the single-GPU frame");
+    static_assert(!(F3D && (ADAM || GATHER)), "the 3D smoothing filter serves the plain single-GPU backward");
     static_assert(!(AA && (ADAM || GATHER)), "the antialiased mode serves the plain single-GPU backward");
     static_assert(!(FISH && (ADAM || GATHER)), "the fisheye mode serves the plain single-GPU backward");
     constexpr int SHW = 3 * (N_SH - 1);
@@ -1074,7 +1088,7 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))
         }
         // opacity: d sigmoid = y (1 - y)
         const float y = opacity_act[v];
-        if constexpr (!AA) go = gsl[3] * (1.0f - y) * y;
+        if constexpr (!AA && !F3D) go = gsl[3] * (1.0f - y) * y;
         // conic -> Sigma_world, J (projection_backward.cu:385-471)
         float q4[4], s3[3];
         if constexpr (ADAM) {
@@ -1086,6 +1100,14 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))
         }
         float S9[9], W[9], J6[6], gS9[9], gJ6[6];
         sigma_world_of(q4, s3, S9);
+        [[maybe_unused]] float phi = 0, ts[3] = {0, 0, 0};   // (ts: the filter's term of the scale gradient)
+        [[maybe_unused]] F3dTerms f3{};
+        if constexpr (F3D) {
+            phi = filter3d[g];
+            filter3d_sigma(S9, phi);
+            f3 = filter3d_terms_of(s3, phi);
+            if constexpr (!AA) go = filter3d_bwd_of(f3, phi, y, gsl[3], ts);
+        }
         load_rotation(M, W);
         // (the pinhole expressions stay spelled out here, z, z2, z3 ahead of J: with them behind a helper this kernel's
         // pinhole instantiations get another register allocation -- they must not move)
@@ -1102,12 +1124,20 @@ __global__ __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))
         if constexpr (AA) {
             float c3[3], g_opa = gsl[3];
             conic_of(J6, W, S9, c3);
-            aa_fold_row(aa_terms_of(c3), y, g_opa, gc3);
-            go = g_opa * (1.0f - y) * y;
+            if constexpr (F3D) {
+                aa_fold_row<true>(aa_terms_of(c3), y * f3.comp3, g_opa, gc3);
+                go = filter3d_bwd_of(f3, phi, y, g_opa, ts);
+            } else {
+                aa_fold_row(aa_terms_of(c3), y, g_opa, gc3);
+                go = g_opa * (1.0f - y) * y;
+            }
         }
         conic_bwd_of(J6, W, S9, gc3, gS9, gJ6);
         // Sigma_world -> quaternion, scale (projection_backward.cu:174-315)
         sigma_world_bwd_of(q4, s3, gS9, gq, gs);
+        if constexpr (F3D) {
+            gs[0] += ts[0]; gs[1] += ts[1]; gs[2] += ts[2];
+        }
         float gcam[3];
         if constexpr (FISH) {
             fisheye_cam_grad_of(c, ft, fx, fy, gJ6, gsl + 4, gcam);
@@ -1239,13 +1269,14 @@ inline int pose_blocks(int N) {
 // AA (GS_RASTER_ANTIALIASED): the conic columns first gain the opacity column's share (aa_fold_row, as k_preprocess_bwd
 // folds the same row), which needs the sigmoid opacity_act[v]; the non-AA instantiation takes no such pointer.
 // FISH (GS_RASTER_FISHEYE): J and its backward are the fisheye model's (fisheye_J6_of, fisheye_cam_grad_of).
+// F3D: S9 is Sigma_eff, and AA's fold takes opa3 = opacity_act[v] * comp3 in the place of the sigmoid (k_preprocess_bwd's).
 struct NoOpacity {};
-template <bool AA = false, bool FISH = false>
+template <bool AA = false, bool FISH = false, bool F3D = false>
 __global__ __launch_bounds__(PP_BLOCK) void k_pose_bwd(
     const float* __restrict__ xyz, const float* __restrict__ quat, const float* __restrict__ scale,
     const float* __restrict__ M, const float* __restrict__ K, const int* __restrict__ rank,
     const float* __restrict__ g_slab, int v_base, int N, float* __restrict__ rows,
-    std::conditional_t<AA, const float*, NoOpacity> opacity_act = {}) {
+    std::conditional_t<AA, const float*, NoOpacity> opacity_act = {}, FilterArg<F3D> filter3d = {}) {
     __shared__ float s_part[PP_BLOCK / GS_WAVE][12];
     float acc[12];
 #pragma unroll
@@ -1263,12 +1294,19 @@ __global__ __launch_bounds__(PP_BLOCK) void k_pose_bwd(
         float c[3], S9[9], J6[6], gJ6[6], gW9[9], gcam[3];
         to_camera(M, p[0], p[1], p[2], c);
         sigma_world_of(q4, s3, S9);
+        [[maybe_unused]] float phi = 0;
+        if constexpr (F3D) {
+            phi = filter3d[g];
+            filter3d_sigma(S9, phi);
+        }
         [[maybe_unused]] const CamTerms<FISH> ft = camera_J6_of<FISH>(c, fx, fy, J6);
         float gc3[3] = {gsl[6], gsl[7], gsl[8]};
         if constexpr (AA) {
             float c3[3], g_opa = gsl[3];
             conic_of(J6, W, S9, c3);
-            aa_fold_row(aa_terms_of(c3), opacity_act[v], g_opa, gc3);
+            float y = opacity_act[v];
+            if constexpr (F3D) y = y * filter3d_comp_of(s3, phi);
+            aa_fold_row<F3D>(aa_terms_of(c3), y, g_opa, gc3);
         }
         conic_bwd_pose_of(J6, W, S9, gc3, gJ6, gW9);
         if constexpr (FISH) fisheye_cam_grad_of(c, ft, fx, fy, gJ6, gsl + 4, gcam);
@@ -1359,6 +1397,17 @@ static Frustum make_frustum(int W, int H, float near, float far, float padding) 
         if (aa) { constexpr bool AA = true; CALL; } else { constexpr bool AA = false; CALL; }      \
     }
 
+// the F3D instantiation a non-NULL filter selects: CALL sees constexpr bool F3D
+#define DISPATCH_F3D(f3d, CALL)                                                                    \
+    if (f3d) { constexpr bool F3D = true; CALL; } else { constexpr bool F3D = false; CALL; }
+
+// the F3D-only argument of the per-Gaussian kernels: the filter variances, or nothing
+template <bool F3D>
+static auto filter_arg(const void* filter3d) {
+    if constexpr (F3D) return (const float*)filter3d;
+    else return NoFilter{};
+}
+
 // the AA-only argument of k_pose_bwd: the sigmoid opacities, or nothing
 template <bool AA>
 static auto pose_opacity_arg(const void* opacity_act) {
@@ -1381,8 +1430,8 @@ extern "C" {
 size_t gs_preprocess_workspace_ints(int N) { return (size_t)div_up(N > 0 ? N : 1, PP_BLOCK) * 2 + 8; }
 
 // raster_mode: GS_RASTER_ANTIALIASED selects the AA instantiation of k_preprocess, GS_RASTER_FISHEYE the FISH
-// instantiations of k_cull_count and k_preprocess, nothing else
-int gs_preprocess_forward_mode(const void* xyz, const void* quaternion, const void* scale,
+// instantiations of k_cull_count and k_preprocess, a non-NULL filter3d the F3D instantiation of k_preprocess, nothing else
+int gs_preprocess_forward_filtered(const void* xyz, const void* quaternion, const void* scale,
                                const void* opacity, const void* rgb, const void* sh, int n_sh,
                                const void* camera_T_world, const void* K, int N, int W, int H,
                                float near_thresh, float far_thresh, float cull_mask_padding,
@@ -1391,8 +1440,12 @@ int gs_preprocess_forward_mode(const void* xyz, const void* quaternion, const vo
                                uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
                                void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
                                void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
-                               int sample_stride, int raster_mode, void* stream) {
+                               int sample_stride, const void* filter3d, int raster_mode, void* stream) {
     GS_RASTER_MODE(raster_mode, aa, fish);
+    const bool f3d = filter3d != nullptr;
+    // (ahead of the first launch: a refused filtered call writes nothing)
+    GS_REQUIRE(!f3d || (band_row0 == 0 && band_row1 == (H + GS_TILE - 1) / GS_TILE),
+               "filter3d serves whole frames (no tile-row band)");
     GS_REQUIRE((bin_records == nullptr) == (cut_workspace == nullptr) && (bin_records == nullptr) == (depth_hist == nullptr),
                "bin_records, cut_workspace and depth_hist go together");
     GS_REQUIRE(depth_hist == nullptr || sample_stride >= 1, "sample_stride must be gs_cut_sample_stride(N)");
@@ -1440,19 +1493,37 @@ int gs_preprocess_forward_mode(const void* xyz, const void* quaternion, const vo
     GS_REQUIRE(!(banded && bin_records != nullptr), "the depth-bucketed binning serves whole frames");
     GS_REQUIRE(!(banded && aa), "GS_RASTER_ANTIALIASED serves whole frames (no tile-row band)");
     GS_REQUIRE(!(banded && fish), "GS_RASTER_FISHEYE serves whole frames (no tile-row band)");
-    // BAND, or (AA, FISH), chooses the kernel (a band frame is a classic one: required above); one argument list
-    auto launch = [&](auto kernel) {
+    // BAND, or (AA, FISH, F3D), chooses the kernel (a band frame is a classic one: required above); one argument list
+    auto launch = [&](auto kernel, auto filter) {
         kernel<<<nb, PP_BLOCK, 0, s>>>((const float*)xyz, (const float*)quaternion, (const float*)scale,
                                        (const float*)opacity, (const float*)rgb, (const float*)sh,
                                        (const float*)camera_T_world, (const float*)K, (const float*)camera_center, N, fr,
-                                       block_offsets, o, band);
+                                       block_offsets, o, band, filter);
     };
     if (banded) {
-        DISPATCH_SH(n_sh, (launch(k_preprocess<N_SH, true>)));
+        DISPATCH_SH(n_sh, (launch(k_preprocess<N_SH, true>, NoFilter{})));
     } else {
-        DISPATCH_MODE(aa, fish, DISPATCH_SH(n_sh, (launch(k_preprocess<N_SH, false, AA, FISH>))));
+        DISPATCH_F3D(f3d, DISPATCH_MODE(aa, fish, DISPATCH_SH(n_sh, (launch(k_preprocess<N_SH, false, AA, FISH, F3D>,
+                                                                            filter_arg<F3D>(filter3d))))));
     }
     return check_launch("preprocess_forward");
+}
+
+int gs_preprocess_forward_mode(const void* xyz, const void* quaternion, const void* scale,
+                               const void* opacity, const void* rgb, const void* sh, int n_sh,
+                               const void* camera_T_world, const void* K, int N, int W, int H,
+                               float near_thresh, float far_thresh, float cull_mask_padding,
+                               float mh_dist, int band_row0, int band_row1,
+                               int32_t* workspace, void* camera_center, int32_t* visible_count,
+                               uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
+                               void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
+                               void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
+                               int sample_stride, int raster_mode, void* stream) {
+    return gs_preprocess_forward_filtered(xyz, quaternion, scale, opacity, rgb, sh, n_sh, camera_T_world, K, N, W, H,
+                                          near_thresh, far_thresh, cull_mask_padding, mh_dist, band_row0, band_row1, workspace,
+                                          camera_center, visible_count, culling_mask, rank, vis_idx, uv, xyz_camera_frame,
+                                          conic, opacity_act, rgb_render, packed, bin_records, cut_workspace, depth_hist,
+                                          sample_stride, nullptr, raster_mode, stream);
 }
 
 int gs_band_project(const void* xyz, const void* scale, const void* opacity, const void* camera_T_world, const void* K,
@@ -1651,30 +1722,44 @@ int gs_preprocess_backward_adam(const void* xyz, int n_sh, const void* camera_T_
     return check_launch("preprocess_backward_adam");
 }
 
+int gs_preprocess_backward_filtered(const void* xyz, const void* quaternion, const void* scale, int n_sh,
+                                    const void* camera_T_world, const void* K, const void* camera_center,
+                                    const int32_t* rank, const void* opacity_act, const void* grad_slab,
+                                    int v_base, int N, void* grad_xyz, void* grad_quaternion, void* grad_scale,
+                                    void* grad_opacity_logit, void* grad_rgb_param, void* grad_sh,
+                                    const void* filter3d, int raster_mode, void* stream) {
+    GS_RASTER_MODE(raster_mode, aa, fish);
+    const bool f3d = filter3d != nullptr;
+    GS_REQUIRE(n_sh == 1 || grad_sh != nullptr, "grad_sh must be given when n_sh > 1");
+    hipStream_t s = (hipStream_t)stream;
+    if (N <= 0) return GS_OK;
+    const PreGrad o = pre_grad_of(grad_xyz, grad_quaternion, grad_scale, grad_opacity_logit, grad_rgb_param, grad_sh);
+    DISPATCH_F3D(f3d, DISPATCH_MODE(aa, fish, DISPATCH_SH(n_sh, (k_preprocess_bwd<N_SH, false, false, AA, FISH, F3D><<<div_up(N, PP_BLOCK), PP_BLOCK, 0, s>>>(
+                      (const float*)xyz, (const float*)quaternion, (const float*)scale, (const float*)camera_T_world,
+                      (const float*)K, (const float*)camera_center, rank, (const float*)opacity_act,
+                      (const float*)grad_slab, v_base, N, o, GatherPlan{}, NoAdam{}, filter_arg<F3D>(filter3d))))));
+    return check_launch("preprocess_backward");
+}
+
 int gs_preprocess_backward_mode(const void* xyz, const void* quaternion, const void* scale, int n_sh,
                                 const void* camera_T_world, const void* K, const void* camera_center,
                                 const int32_t* rank, const void* opacity_act, const void* grad_slab,
                                 int v_base, int N, void* grad_xyz, void* grad_quaternion, void* grad_scale,
                                 void* grad_opacity_logit, void* grad_rgb_param, void* grad_sh,
                                 int raster_mode, void* stream) {
-    GS_RASTER_MODE(raster_mode, aa, fish);
-    GS_REQUIRE(n_sh == 1 || grad_sh != nullptr, "grad_sh must be given when n_sh > 1");
-    hipStream_t s = (hipStream_t)stream;
-    if (N <= 0) return GS_OK;
-    const PreGrad o = pre_grad_of(grad_xyz, grad_quaternion, grad_scale, grad_opacity_logit, grad_rgb_param, grad_sh);
-    DISPATCH_MODE(aa, fish, DISPATCH_SH(n_sh, (k_preprocess_bwd<N_SH, false, false, AA, FISH><<<div_up(N, PP_BLOCK), PP_BLOCK, 0, s>>>(
-                      (const float*)xyz, (const float*)quaternion, (const float*)scale, (const float*)camera_T_world,
-                      (const float*)K, (const float*)camera_center, rank, (const float*)opacity_act,
-                      (const float*)grad_slab, v_base, N, o))));
-    return check_launch("preprocess_backward");
+    return gs_preprocess_backward_filtered(xyz, quaternion, scale, n_sh, camera_T_world, K, camera_center, rank, opacity_act,
+                                           grad_slab, v_base, N, grad_xyz, grad_quaternion, grad_scale, grad_opacity_logit,
+                                           grad_rgb_param, grad_sh, nullptr, raster_mode, stream);
 }
 
 size_t gs_pose_workspace_floats(int N) { return (size_t)pose_blocks(N) * 12 + 4; }
 
-int gs_pose_backward_mode(const void* xyz, const void* quaternion, const void* scale, const void* camera_T_world,
-                          const void* K, const int32_t* rank, const void* opacity_act, const void* grad_slab, int v_base,
-                          int N, void* workspace, void* grad_camera_T_world, int raster_mode, void* stream) {
+int gs_pose_backward_filtered(const void* xyz, const void* quaternion, const void* scale, const void* camera_T_world,
+                              const void* K, const int32_t* rank, const void* opacity_act, const void* grad_slab, int v_base,
+                              int N, void* workspace, void* grad_camera_T_world, const void* filter3d, int raster_mode,
+                              void* stream) {
     GS_RASTER_MODE(raster_mode, aa, fish);
+    const bool f3d = filter3d != nullptr;
     GS_REQUIRE(!aa || N <= 0 || opacity_act != nullptr, "pose_backward: GS_RASTER_ANTIALIASED needs opacity_act");
     GS_REQUIRE(grad_camera_T_world != nullptr, "pose_backward: grad_camera_T_world is NULL");
     GS_REQUIRE(N <= 0 || (workspace != nullptr && xyz != nullptr && quaternion != nullptr && scale != nullptr &&
@@ -1683,14 +1768,21 @@ int gs_pose_backward_mode(const void* xyz, const void* quaternion, const void* s
     hipStream_t s = (hipStream_t)stream;
     const int nb = pose_blocks(N);
     if (nb > 0) {
-        DISPATCH_MODE(aa, fish, (k_pose_bwd<AA, FISH><<<nb, PP_BLOCK, 0, s>>>(
+        DISPATCH_F3D(f3d, DISPATCH_MODE(aa, fish, (k_pose_bwd<AA, FISH, F3D><<<nb, PP_BLOCK, 0, s>>>(
                           (const float*)xyz, (const float*)quaternion, (const float*)scale, (const float*)camera_T_world,
                           (const float*)K, rank, (const float*)grad_slab, v_base, N, (float*)workspace,
-                          pose_opacity_arg<AA>(opacity_act))));
+                          pose_opacity_arg<AA>(opacity_act), filter_arg<F3D>(filter3d)))));
     }
     // (N == 0: no rows, the sum writes the zeros)
     k_pose_sum<<<1, POSE_SUM_BLOCK, 0, s>>>((const float*)workspace, nb, (float*)grad_camera_T_world);
     return check_launch("pose_backward");
+}
+
+int gs_pose_backward_mode(const void* xyz, const void* quaternion, const void* scale, const void* camera_T_world,
+                          const void* K, const int32_t* rank, const void* opacity_act, const void* grad_slab, int v_base,
+                          int N, void* workspace, void* grad_camera_T_world, int raster_mode, void* stream) {
+    return gs_pose_backward_filtered(xyz, quaternion, scale, camera_T_world, K, rank, opacity_act, grad_slab, v_base, N,
+                                     workspace, grad_camera_T_world, nullptr, raster_mode, stream);
 }
 
 // ---- the entries the general ones above superseded: each forwards, in one line, to the entry named in its body ----

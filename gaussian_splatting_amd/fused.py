@@ -29,6 +29,11 @@ depth kernels).
 rasterize_features composites caller-supplied per-Gaussian feature vectors [N, C <= 32] with the frame's weights into a
 differentiable [H, W, C] map next to the image and the accumulated opacity (_Render with the map policy _FeatureMap:
 gs_render_features / gs_render_features_backward).
+
+filter3d= on the entry points is Mip-Splatting's 3D smoothing filter: per-Gaussian world-space variances
+that the per-Gaussian stage adds to the covariance and compensates in the opacity, forward and backward
+(gs_preprocess_forward_filtered and its two backward twins).  filter3d_rate / filter3d_from_rate make the filter from the
+training cameras (gs_filter3d_rate), bake_filter3d folds it into the parameters for export.
 """
 import os
 from types import SimpleNamespace
@@ -269,8 +274,10 @@ def _raster_mode(antialiased, camera_model):
 
 def preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, width, height, near_thresh,
                        far_thresh, cull_mask_padding, mh_dist, tile_rows, sort_prefix, plan=None, plan_ints=0,
-                       defer=False, depth_cut=False, antialiased=False, camera_model="pinhole"):
-    """Per-Gaussian stage, binning and per-tile sort of one frame.  antialiased: the packed record's opacity carries the
+                       defer=False, depth_cut=False, antialiased=False, camera_model="pinhole", filter3d=None):
+    """Per-Gaussian stage, binning and per-tile sort of one frame.  filter3d: float32 [N] world-space variances of the 3D
+    smoothing filter (gs_preprocess_forward_filtered; whole frames, combines with the two below); None: the call without
+    it (the entry then launches what gs_preprocess_forward_mode launches).  antialiased: the packed record's opacity carries the
     factor sqrt(det Sigma_2D / det(Sigma_2D + 0.25 I)) (gs_preprocess_forward_mode, GS_RASTER_ANTIALIASED; whole frames).
     camera_model: "pinhole", or "fisheye" -- uv, the cull and the projection Jacobian of the equidistant fisheye model
     (GS_RASTER_FISHEYE; whole frames, combines with antialiased).  `plan`, if given, is called as
@@ -287,7 +294,8 @@ def preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world,
     row0, row1 = tile_rows if tile_rows is not None else (0, nty)
     f = SimpleNamespace(N=N, n_sh=n_sh, ntx=ntx, nty=nty, T=T, row0=row0, row1=row1, width=width, height=height,
                         mh_dist=mh_dist, sort_prefix=sort_prefix, antialiased=bool(antialiased),
-                        camera_model=camera_model, raster_mode=_raster_mode(antialiased, camera_model))
+                        camera_model=camera_model, raster_mode=_raster_mode(antialiased, camera_model), filter3d=filter3d)
+    _require(not (filter3d is not None and tile_rows is not None), "filter3d serves whole frames: tile_rows is not supported")
     _require(not (antialiased and tile_rows is not None), "antialiased=True serves whole frames: tile_rows is not supported")
     _require(not (camera_model == "fisheye" and tile_rows is not None),
              'camera_model="fisheye" serves whole frames: tile_rows is not supported')
@@ -310,11 +318,11 @@ def preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world,
     f.uv, f.xyz_cam, f.conic = uv.view(N, 2), xyz_cam.view(N, 3), conic.view(N, 3)
     f.opacity_act, f.rgb_render, f.packed = opa.view(N, 1), rgbr.view(N, 3), packed.view(N, 12)
     f.cut = None
-    _hip.call("gs_preprocess_forward_mode", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), n_sh,
-              _p(camera_T_world), _p(K), N, width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, row0,
-              row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx), _p(f.uv),
-              _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), None, None, None, 0,
-              f.raster_mode, stream, label="gs_preprocess_forward")
+    _hip.call("gs_preprocess_forward_filtered", _p(xyz), _p(quaternion), _p(scale), _p(opacity),
+              _p(rgb), _p(sh), n_sh, _p(camera_T_world), _p(K), N, width, height, near_thresh, far_thresh,
+              cull_mask_padding, mh_dist, row0, row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank),
+              _p(f.vis_idx), _p(f.uv), _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed),
+              None, None, None, 0, _p(filter3d), f.raster_mode, stream, label="gs_preprocess_forward")
 
     # the plan's record lives right behind (S, V) at the tail of ranges_buf: one host read gets both
     f.subset = (None, None)
@@ -397,11 +405,12 @@ def _preprocess_forward_cut(f, xyz, quaternion, scale, opacity, rgb, sh, camera_
     f.center, uv, xyz_cam, conic, opa, rgbr, packed, bin_rec = far.blocks()
     f.uv, f.xyz_cam, f.conic = uv.view(N, 2), xyz_cam.view(N, 3), conic.view(N, 3)
     f.opacity_act, f.rgb_render, f.packed = opa.view(N, 1), rgbr.view(N, 3), packed.view(N, 12)
-    _hip.call("gs_preprocess_forward_mode", _p(xyz), _p(quaternion), _p(scale), _p(opacity), _p(rgb), _p(sh), f.n_sh,
-              _p(camera_T_world), _p(K), N, f.width, f.height, near_thresh, far_thresh, cull_mask_padding, f.mh_dist,
-              row0, row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask), _p(f.rank), _p(f.vis_idx),
-              _p(f.uv), _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render), _p(f.packed), _p(bin_rec),
-              _p(cut_ws), _p(_depth_hist(dev)), stride, f.raster_mode, stream, label="gs_preprocess_forward")
+    _hip.call("gs_preprocess_forward_filtered", _p(xyz), _p(quaternion), _p(scale), _p(opacity),
+              _p(rgb), _p(sh), f.n_sh, _p(camera_T_world), _p(K), N, f.width, f.height, near_thresh, far_thresh,
+              cull_mask_padding, f.mh_dist, row0, row1, _p(f.ws), _p(f.center), _p(f.count), _p(f.culling_mask),
+              _p(f.rank), _p(f.vis_idx), _p(f.uv), _p(f.xyz_cam), _p(f.conic), _p(f.opacity_act), _p(f.rgb_render),
+              _p(f.packed), _p(bin_rec), _p(cut_ws), _p(_depth_hist(dev)), stride, _p(f.filter3d),
+              f.raster_mode, stream, label="gs_preprocess_forward")
     _hip.call("gs_tile_count_cut", _p(bin_rec), N, _p(f.count), ntx, nty, f.mh_dist, row0, row1,
               _p(f.tile_counts), _p(cut_ws), _p(f.ranges_buf), _p(full_ranges), None, stream)
     f.subset = (None, None)
@@ -461,11 +470,12 @@ def preprocess_finish(f):
 
 
 def preprocess_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_base=0, i0=0, i1=None, antialiased=False,
-                        camera_model="pinhole"):
+                        camera_model="pinhole", filter3d=None):
     """Dense parameter gradients of the Gaussians [i0, i1) from the render-gradient slab
     (row of visible Gaussian v at slab[v - v_base]).  xyz, quaternion, scale: the full tensors.
     antialiased: the slab's opacity column is the gradient of the antialiased opacity (gs_preprocess_backward_mode).
-    camera_model: the model the forward projected with (the uv and conic columns go back through it)."""
+    camera_model: the model the forward projected with (the uv and conic columns go back through it).
+    filter3d: the full [N] filter the forward ran with (gs_preprocess_backward_filtered), or None."""
     mode = _raster_mode(antialiased, camera_model)
     i1 = f.N if i1 is None else i1
     n = i1 - i0
@@ -476,15 +486,15 @@ def preprocess_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_ba
     grad_opacity, grad_rgb = go.view(n, 1), gc.view(n, 3)
     grad_sh = gsh.view(n, 3, f.n_sh - 1) if f.n_sh > 1 else None
     if n > 0:
-        _hip.call("gs_preprocess_backward_mode", _p(xyz[i0:i1]), _p(quaternion[i0:i1]), _p(scale[i0:i1]), f.n_sh,
-                  _p(camera_T_world), _p(K), _p(f.center), _p(f.rank[i0:i1]), _p(f.opacity_act), _p(slab), v_base, n,
-                  _p(grad_xyz), _p(grad_q), _p(grad_scale), _p(grad_opacity), _p(grad_rgb), _p(grad_sh),
-                  mode, _stream(), label="gs_preprocess_backward")
+        _hip.call("gs_preprocess_backward_filtered", _p(xyz[i0:i1]), _p(quaternion[i0:i1]),
+                  _p(scale[i0:i1]), f.n_sh, _p(camera_T_world), _p(K), _p(f.center), _p(f.rank[i0:i1]), _p(f.opacity_act),
+                  _p(slab), v_base, n, _p(grad_xyz), _p(grad_q), _p(grad_scale), _p(grad_opacity), _p(grad_rgb),
+                  _p(grad_sh), _p(filter3d[i0:i1] if filter3d is not None else None), mode, _stream(), label="gs_preprocess_backward")
     return grad_xyz, grad_q, grad_scale, grad_opacity, grad_rgb, grad_sh
 
 
 def pose_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_base=0, antialiased=False,
-                  camera_model="pinhole"):
+                  camera_model="pinhole", filter3d=None):
     """The gradient of camera_T_world [4, 4] from the render-gradient slab of frame record f (gs_pose_backward): the
     rotation block and the translation as twelve free numbers, the last row 0.  Reads the quaternion and scale the
     forward saw: with the fused optimizer step it goes BEFORE preprocess_backward_adam on the same stream."""
@@ -495,8 +505,9 @@ def pose_backward(xyz, quaternion, scale, camera_T_world, K, f, slab, v_base=0, 
     ws = torch.empty(_hip.lib().gs_pose_workspace_floats(n), dtype=torch.float32, device=xyz.device)
     # (antialiased: the opacity column reaches the pose through the factor's conic terms, which need the sigmoid)
     opacity_act = f.opacity_act if mode & _hip.GS_RASTER_ANTIALIASED else None
-    _hip.call("gs_pose_backward_mode", _p(xyz), _p(quaternion), _p(scale), _p(camera_T_world), _p(K), _p(f.rank),
-              _p(opacity_act), _p(slab), v_base, n, _p(ws), _p(grad), mode, _stream(), label="gs_pose_backward")
+    _hip.call("gs_pose_backward_filtered", _p(xyz), _p(quaternion), _p(scale), _p(camera_T_world),
+              _p(K), _p(f.rank), _p(opacity_act), _p(slab), v_base, n, _p(ws), _p(grad), _p(filter3d), mode,
+              _stream(), label="gs_pose_backward")
     return grad
 
 
@@ -765,7 +776,7 @@ def _as_slab(g_uv, g_conic, g_opa, g_rgb, V, dev):
 # ---------------------------------------------------------------------------------------------------
 def _frame_record(width, height, near_thresh, far_thresh, cull_mask_padding, mh_dist, tile_rows=None, sort_prefix=0,
                   background=None, pose_grad=False, adam_plan=None, antialiased=False, z_out=False, may_cut=False,
-                  slab_sync=None, absgrad=False, camera_model="pinhole"):
+                  slab_sync=None, absgrad=False, camera_model="pinhole", filter3d=None):
     """What one frame's two nodes share and autograd does not differentiate: the frame's options, set here by the entry
     point, and -- filled by _Preprocess.forward -- the stage record's tensors the render and the caller read.  Handed
     to both nodes as a non-tensor argument.  The differentiable outputs are not kept on it (that would tie the record to
@@ -780,6 +791,8 @@ def _frame_record(width, height, near_thresh, far_thresh, cull_mask_padding, mh_
     the record), so the gradient that comes back for it is dL/d(sigmoid * comp) and the backward folds it
     camera_model: "pinhole" or "fisheye" -- the projection of the per-Gaussian stage, forward and both backwards; the
     render, the binning and the maps read only what that stage wrote
+    filter3d: None, or the float32 [N] variances of the 3D smoothing filter: a constant of the frame that
+    the per-Gaussian stage reads forward and backward, carried here next to antialiased
     may_cut: the frame may take the depth cut (want_depth_cut decides); its record, what _Render's two passes need,
     is then left in `cut`
     slab_sync: see rasterize()
@@ -788,7 +801,8 @@ def _frame_record(width, height, near_thresh, far_thresh, cull_mask_padding, mh_
     return SimpleNamespace(
         width=width, height=height, near_thresh=near_thresh, far_thresh=far_thresh, cull_mask_padding=cull_mask_padding,
         mh_dist=mh_dist, tile_rows=tile_rows, sort_prefix=sort_prefix, background=background, pose_grad=pose_grad,
-        adam_plan=adam_plan, antialiased=bool(antialiased), camera_model=camera_model, z_out=z_out, may_cut=may_cut,
+        adam_plan=adam_plan, antialiased=bool(antialiased), camera_model=camera_model, filter3d=filter3d, z_out=z_out,
+        may_cut=may_cut,
         slab_sync=slab_sync, absgrad=bool(absgrad), uv_absgrad=None,
         # after _Preprocess.forward (xyz_cam and vis_idx: the V visible rows)
         packed=None, xyz_cam=None, culling_mask=None, ranges=None, sorted_g=None, vis_idx=None, keys=None, cut=None,
@@ -810,7 +824,7 @@ class _Preprocess(torch.autograd.Function):
         f = preprocess_forward(xyz, quaternion, scale, opacity, rgb, sh, camera_T_world, K, fr.width, fr.height,
                                fr.near_thresh, fr.far_thresh, fr.cull_mask_padding, fr.mh_dist, fr.tile_rows,
                                fr.sort_prefix, defer=(not cut) and EARLY_RENDER and fr.sort_prefix != 0, depth_cut=cut,
-                               antialiased=fr.antialiased, camera_model=fr.camera_model)
+                               antialiased=fr.antialiased, camera_model=fr.camera_model, filter3d=fr.filter3d)
         if cut:
             fr.rendered = render_forward(f.packed, f.rgb_render, f.ranges, f.sorted_g, f.keys, fr.background, fr.height,
                                          fr.width, fr.tile_rows, fr.sort_prefix, segments=False, cut=f.cut)
@@ -854,7 +868,7 @@ class _Preprocess(torch.autograd.Function):
         g_pose = None
         if fr.pose_grad and ctx.needs_input_grad[6]:
             g_pose = pose_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab, antialiased=fr.antialiased,
-                                   camera_model=fr.camera_model)
+                                   camera_model=fr.camera_model, filter3d=fr.filter3d)
             if g_z is not None:
                 # the direct term of z = T[2, 0:3] . xyz + T[2, 3] (the slab's terms above already hold the depth map's
                 # uv / conic columns): plumbing on the visible rows, not a hot path
@@ -865,7 +879,7 @@ class _Preprocess(torch.autograd.Function):
             grads = (preprocess_backward_adam(xyz, camera_T_world, K, ctx.f, slab, fr.adam_plan),) + (None,) * 5
         else:
             grads = preprocess_backward(xyz, quaternion, scale, camera_T_world, K, ctx.f, slab,
-                                        antialiased=fr.antialiased, camera_model=fr.camera_model)
+                                        antialiased=fr.antialiased, camera_model=fr.camera_model, filter3d=fr.filter3d)
         if g_z is not None:
             _hip.call("gs_z_backward", _p(ctx.f.rank), _p(g_z), _p(camera_T_world), 0, ctx.f.N, _p(grads[0]), _stream())
         return grads + (g_pose, None, None)   # (K, the record)
@@ -1072,7 +1086,7 @@ def _require(cond, msg):
         raise RuntimeError(msg)
 
 
-def validate(gaussians, camera_T_world, camera, background_rgb):
+def validate(gaussians, camera_T_world, camera, background_rgb, filter3d=None):
     """The checks of the reference's extension (src/checks.cuh:5-14, render.cu:204-246) for the tensors the
     fused path hands to the C ABI as raw pointers: device, dtype, shape.  (Contiguity is established by
     the caller with .contiguous().)  Raises RuntimeError like the reference's TORCH_CHECKs."""
@@ -1092,6 +1106,12 @@ def validate(gaussians, camera_T_world, camera, background_rgb):
         _require(t.dtype == torch.float32, "sh is not a float tensor")
         _require(t.dim() == 3 and t.shape[0] == N and t.shape[1] == 3 and t.shape[2] in (3, 8, 15),
                  f"sh must have shape [{N}, 3, 3|8|15], got {list(t.shape)}")
+    if filter3d is not None:
+        t = filter3d
+        _require(torch.is_tensor(t) and t.is_cuda and t.device == dev, f"filter3d is not a CUDA tensor on {dev}")
+        _require(t.dtype == torch.float32, "filter3d is not a float tensor")
+        _require(tuple(t.shape) == (N,), f"filter3d must have shape [{N}], one variance per Gaussian, got {list(t.shape)} "
+                                         "(recompute the filter after a step that changes N)")
 
 
 def supported(gaussians, camera_T_world, camera, use_sh_precompute):
@@ -1102,9 +1122,11 @@ def supported(gaussians, camera_T_world, camera, use_sh_precompute):
     return True
 
 
-def _refuse(who, gaussians, camera_T_world, camera, use_sh_precompute, background_rgb, frame_options, adam_plan):
+def _refuse(who, gaussians, camera_T_world, camera, use_sh_precompute, background_rgb, frame_options, adam_plan,
+            filter3d=None):
     """what the antialiased frame and the map frames (`who`) are served on, checked before anything is enqueued: each
-    refusal names its reason"""
+    refusal names its reason.  filter3d: the frame's 3D smoothing filter, if it has one -- float32 [N] on the Gaussians'
+    device, a constant (no requires_grad)"""
     g = gaussians
     _require(not any(frame_options),
              f"{who} serves whole single-GPU frames: tile_rows, return_aux, grad_sync, slab_sync and "
@@ -1116,6 +1138,12 @@ def _refuse(who, gaussians, camera_T_world, camera, use_sh_precompute, backgroun
                            background_rgb) if t is not None]
     _require(all(t.is_cuda and t.dtype == torch.float32 for t in tensors),
              f"{who} needs float32 tensors on the GPU (no fp64, no CPU path)")
+    if filter3d is not None:
+        _require(torch.is_tensor(filter3d) and filter3d.dtype == torch.float32 and filter3d.device == g.xyz.device
+                 and tuple(filter3d.shape) == (g.xyz.shape[0],),
+                 f"{who}: filter3d must be float32 [N] on the Gaussians' device, one variance per Gaussian "
+                 "(recompute the filter after a step that changes N)")
+        _require(not filter3d.requires_grad, f"{who}: filter3d is a constant of the frame and must not require a gradient")
 
 
 def _begin_frame(gaussians, sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
@@ -1130,8 +1158,9 @@ def _begin_frame(gaussians, sh, camera_T_world, camera, near_thresh, far_thresh,
     -> (the frame record, (uv, conic, opacity, rgb[, z]))"""
     g = gaussians
     _raster_mode(False, options.get("camera_model", "pinhole"))   # (an unknown name raises before anything else)
+    filter3d = options.get("filter3d")
     if who is not None:
-        _refuse(who, g, camera_T_world, camera, use_sh_precompute, background_rgb, frame_options, adam_plan)
+        _refuse(who, g, camera_T_world, camera, use_sh_precompute, background_rgb, frame_options, adam_plan, filter3d)
         if features is not None:
             _require(torch.is_tensor(features) and features.dim() == 2 and features.shape[0] == g.xyz.shape[0],
                      f"{who}: features must be [N, C], one row per Gaussian")
@@ -1139,8 +1168,10 @@ def _begin_frame(gaussians, sh, camera_T_world, camera, near_thresh, far_thresh,
                      f"{who}: features must have 1 to 32 columns (callers with more split the channels)")
             _require(features.dtype == torch.float32 and features.device == g.xyz.device,
                      f"{who}: features must be float32 on the Gaussians' device (no fp64, no CPU path)")
-        validate(g, camera_T_world, camera, background_rgb)
+        validate(g, camera_T_world, camera, background_rgb, filter3d)
         options = dict(options, sort_prefix=_hip.GS_SORT_PREFIX if SORT_PREFIX else 0, pose_grad=True)
+    if filter3d is not None:
+        options = dict(options, filter3d=filter3d.contiguous())
     fr = _frame_record(int(camera.width), int(camera.height), near_thresh, far_thresh, cull_mask_padding, mh_dist,
                        background=background_rgb.contiguous(), adam_plan=adam_plan, **options)
     return fr, _Preprocess.apply(
@@ -1150,7 +1181,7 @@ def _begin_frame(gaussians, sh, camera_T_world, camera, near_thresh, far_thresh,
 
 def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
               use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None, slab_sync=None,
-              frame_hook=None, adam_plan=None, antialiased=False, absgrad=False, camera_model="pinhole"):
+              frame_hook=None, adam_plan=None, antialiased=False, absgrad=False, camera_model="pinhole", filter3d=None):
     """tile_rows=(row0, row1) restricts binning and rendering to those tile rows; slab_sync(flat) is
     called on the flat [9 V] render-gradient slab in the backward (grad_sync is the generic
     per-tensor form used by the reference-shaped path): the hooks gaussian_splatting_amd.sharded
@@ -1180,18 +1211,23 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
     like antialiased=True, with which and with absgrad=True it combines, natively or on the Python orchestration, with
     the depth cut, depth segments and longest-first order under their usual policies; tile_rows, the hooks, adam_plan,
     per-pixel SH (its rays are pinhole rays), non-fp32 or CPU tensors raise RuntimeError before a kernel is enqueued,
-    and so does any other camera_model string.  "pinhole" (the default) is exactly the frame without the keyword."""
+    and so does any other camera_model string.  "pinhole" (the default) is exactly the frame without the keyword.
+    filter3d: float32 [N] on the Gaussians' device, the world-space variances phi >= 0 of Mip-Splatting's 3D smoothing
+    filter (filter3d_rate and filter3d_from_rate make them from the training cameras).  Every Gaussian is
+    rendered with Sigma + phi I and with its opacity times sqrt(prod_k s_k^2 / (s_k^2 + phi)), and the factor is
+    differentiated towards scale and opacity; the filter itself is a constant (a tensor that requires a gradient is
+    refused) and has to be recomputed after any step that changes N.  Served like antialiased=True -- its other half --
+    with which, with absgrad and with camera_model it combines, natively or on the Python orchestration; refused by name
+    where that is.  None (the default) is exactly the frame without the keyword; a row with phi = 0 carries that frame's
+    values."""
     hooks = return_aux or grad_sync or slab_sync or frame_hook
     raster_mode = _raster_mode(antialiased, camera_model)
-    if camera_model == "fisheye":
-        _refuse('rasterize(camera_model="fisheye")', gaussians, camera_T_world, camera, use_sh_precompute,
-                background_rgb, (tile_rows is not None, hooks), adam_plan)
-    if absgrad:
-        _refuse("rasterize(absgrad=True)", gaussians, camera_T_world, camera, use_sh_precompute, background_rgb,
-                (tile_rows is not None, hooks), adam_plan)
-    if antialiased:
-        _refuse("rasterize(antialiased=True)", gaussians, camera_T_world, camera, use_sh_precompute, background_rgb,
-                (tile_rows is not None, hooks), adam_plan)
+    # the options that are served on whole single-GPU fp32 frames only: one refusal, named after those in use
+    options = [name for name, on in (("filter3d=", filter3d is not None), ('camera_model="fisheye"', camera_model == "fisheye"),
+                                     ("absgrad=True", absgrad), ("antialiased=True", antialiased)) if on]
+    if options:
+        _refuse(f"rasterize({', '.join(options)})", gaussians, camera_T_world, camera, use_sh_precompute, background_rgb,
+                (tile_rows is not None, hooks), adam_plan, filter3d)
     if adam_plan is not None:
         _require(not hooks and tile_rows is None, "the fused optimizer step serves whole single-GPU frames without hooks")
         _require(supported(gaussians, camera_T_world, camera, use_sh_precompute),
@@ -1208,7 +1244,7 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
                                            cull_mask_padding, mh_dist, use_sh_precompute, background_rgb,
                                            tile_rows=tile_rows, grad_sync=grad_sync)
     g = gaussians
-    validate(g, camera_T_world, camera, background_rgb)
+    validate(g, camera_T_world, camera, background_rgb, filter3d)
     nat = native() if not (hooks or absgrad) else None
     if nat is not None:
         nat.set_modes(bool(SORT_PREFIX), bool(EARLY_RENDER))
@@ -1221,13 +1257,13 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
                                       mh_dist, background_rgb, adam_plan)
         return nat.rasterize(g.xyz, g.quaternion, g.scale, g.opacity, g.rgb, g.sh, camera_T_world, camera.K,
                              int(camera.width), int(camera.height), near_thresh, far_thresh, cull_mask_padding, mh_dist,
-                             background_rgb, row0, row1, raster_mode)
+                             background_rgb, row0, row1, raster_mode, filter3d)
     # (refused and validated above; the depth cut only without hooks; the pose a constant on multi-GPU frames)
     fr, (uv, conic, opacity, rgb) = _begin_frame(
         g, g.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist, background_rgb,
         adam_plan=adam_plan, tile_rows=tile_rows, sort_prefix=_hip.GS_SORT_PREFIX if (SORT_PREFIX and not return_aux) else 0,
         pose_grad=not (grad_sync or slab_sync), antialiased=antialiased, may_cut=not hooks, slab_sync=slab_sync,
-        absgrad=absgrad, camera_model=camera_model)
+        absgrad=absgrad, camera_model=camera_model, filter3d=filter3d)
     if absgrad:   # (a row even when nothing is visible: an empty tensor has no address to hand to the entry)
         fr.uv_absgrad = torch.zeros(max(uv.shape[0], 1), 2, dtype=torch.float32, device=uv.device)
     if frame_hook is not None:   # multi-GPU cost-balanced bands: the band's tile ranges
@@ -1244,7 +1280,7 @@ def rasterize(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_m
 
 def rasterize_rgbd(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
                    use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None, slab_sync=None,
-                   frame_hook=None, adam_plan=None, antialiased=False, camera_model="pinhole"):
+                   frame_hook=None, adam_plan=None, antialiased=False, camera_model="pinhole", filter3d=None):
     """rasterize() with a differentiable depth map and accumulated opacity:
 
         image, depth, alpha, culling_mask, uv = rasterize_rgbd(...)
@@ -1257,12 +1293,12 @@ def rasterize_rgbd(gaussians, camera_T_world, camera, near_thresh, far_thresh, c
     Whole single-GPU fp32 frames in the SH-precompute colour mode, Python orchestration, depth cut off: anything
     else raises RuntimeError (the trailing keyword arguments exist only to say so).  antialiased: as rasterize()'s --
     the maps' weights then carry the antialiased opacity too.  camera_model: as rasterize()'s; depth stays the camera-frame
-    z, not the distance along the ray."""
+    z, not the distance along the ray.  filter3d: as rasterize()'s."""
     fr, (uv, conic, opacity, rgb, z) = _begin_frame(
         gaussians, gaussians.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
         background_rgb, "rasterize_rgbd", use_sh_precompute,
         (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), adam_plan=adam_plan,
-        antialiased=antialiased, z_out=True, camera_model=camera_model)
+        antialiased=antialiased, z_out=True, camera_model=camera_model, filter3d=filter3d)
     image, depth, alpha = _Render.apply(uv, conic, opacity, rgb, z, fr, _DepthMap)
     return image, depth, alpha, fr.culling_mask, uv
 
@@ -1270,7 +1306,7 @@ def rasterize_rgbd(gaussians, camera_T_world, camera, near_thresh, far_thresh, c
 def rasterize_distortion(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
                          use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None,
                          slab_sync=None, frame_hook=None, adam_plan=None, antialiased=False,
-                         camera_model="pinhole"):
+                         camera_model="pinhole", filter3d=None):
     """rasterize_rgbd() with the depth-distortion map of the same walk:
 
         image, depth, alpha, distortion, culling_mask, uv = rasterize_distortion(...)
@@ -1283,13 +1319,13 @@ def rasterize_distortion(gaussians, camera_T_world, camera, near_thresh, far_thr
     parameters and, when it requires one, to camera_T_world; the maps' backward is their true derivative, one kernel
     for the three of them in place of rasterize_rgbd's (DESIGN.md "Depth distortion").  An output without a gradient
     costs nothing.  Whole single-GPU fp32 frames in the SH-precompute colour mode, Python orchestration, depth cut off:
-    anything else raises RuntimeError (the trailing keyword arguments exist only to say so).  antialiased, camera_model: as
-    rasterize()'s."""
+    anything else raises RuntimeError (the trailing keyword arguments exist only to say so).  antialiased, camera_model,
+    filter3d: as rasterize()'s."""
     fr, (uv, conic, opacity, rgb, z) = _begin_frame(
         gaussians, gaussians.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
         background_rgb, "rasterize_distortion", use_sh_precompute,
         (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), adam_plan=adam_plan,
-        antialiased=antialiased, z_out=True, camera_model=camera_model)
+        antialiased=antialiased, z_out=True, camera_model=camera_model, filter3d=filter3d)
     image, depth, alpha, distortion = _Render.apply(uv, conic, opacity, rgb, z, fr, _DistortionMap)
     return image, depth, alpha, distortion, fr.culling_mask, uv
 
@@ -1297,7 +1333,7 @@ def rasterize_distortion(gaussians, camera_T_world, camera, near_thresh, far_thr
 def rasterize_features(gaussians, features, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
                        use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None,
                        slab_sync=None, frame_hook=None, adam_plan=None, antialiased=False,
-                       camera_model="pinhole"):
+                       camera_model="pinhole", filter3d=None):
     """rasterize() with a map of caller-supplied per-Gaussian feature vectors and the accumulated opacity:
 
         image, feature_map, alpha, culling_mask, uv = rasterize_features(gaussians, features, ...)
@@ -1310,12 +1346,12 @@ def rasterize_features(gaussians, features, camera_T_world, camera, near_thresh,
     Gaussians' parameters and, when it requires one, to camera_T_world (through the slab; features have no direct
     pose term); their backward is the true derivative (DESIGN.md "Feature maps").  Whole single-GPU fp32 frames in the
     SH-precompute colour mode, Python orchestration, depth cut off: anything else raises RuntimeError (the trailing
-    keyword arguments exist only to say so).  antialiased, camera_model: as rasterize()'s."""
+    keyword arguments exist only to say so).  antialiased, camera_model, filter3d: as rasterize()'s."""
     fr, (uv, conic, opacity, rgb) = _begin_frame(
         gaussians, gaussians.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
         background_rgb, "rasterize_features", use_sh_precompute,
         (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), features, adam_plan,
-        antialiased=antialiased, camera_model=camera_model)
+        antialiased=antialiased, camera_model=camera_model, filter3d=filter3d)
     feat = _GatherRows.apply(features, fr.vis_idx.long()).contiguous()
     image, feature_map, alpha = _Render.apply(uv, conic, opacity, rgb, feat, fr, _FeatureMap)
     return image, feature_map, alpha, fr.culling_mask, uv
@@ -1364,7 +1400,7 @@ class ContributionStats:
 def rasterize_contributions(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
                             use_sh_precompute, background_rgb, stats=None, antialiased=False, tile_rows=None,
                             return_aux=False, grad_sync=None, slab_sync=None, frame_hook=None, adam_plan=None,
-                            camera_model="pinhole"):
+                            camera_model="pinhole", filter3d=None):
     """rasterize() without gradients, with the per-Gaussian contribution statistics of the frame:
 
         image, stats, culling_mask = rasterize_contributions(gaussians, ...)                # a new record
@@ -1377,8 +1413,8 @@ def rasterize_contributions(gaussians, camera_T_world, camera, near_thresh, far_
     (gs_render_contributions with row_index = the frame's visible indices): no [V] temporary, no scatter.  Runs under
     torch.no_grad(); nothing returned carries a gradient.  Whole single-GPU fp32 frames in the SH-precompute colour
     mode, Python orchestration, depth cut off: anything else raises RuntimeError before a kernel is enqueued (the
-    trailing keyword arguments exist only to say so).  A stats of another N raises too.  antialiased, camera_model: as
-    rasterize()'s."""
+    trailing keyword arguments exist only to say so).  A stats of another N raises too.  antialiased, camera_model,
+    filter3d: as rasterize()'s."""
     with torch.no_grad():
         n = int(gaussians.xyz.shape[0])
         if stats is not None:
@@ -1388,7 +1424,7 @@ def rasterize_contributions(gaussians, camera_T_world, camera, near_thresh, far_
             gaussians, gaussians.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
             background_rgb, "rasterize_contributions", use_sh_precompute,
             (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), adam_plan=adam_plan,
-            antialiased=antialiased, camera_model=camera_model)
+            antialiased=antialiased, camera_model=camera_model, filter3d=filter3d)
         if stats is None:
             stats = ContributionStats.zeros(n, gaussians.xyz.device)
         else:
@@ -1400,3 +1436,69 @@ def rasterize_contributions(gaussians, camera_T_world, camera, near_thresh, far_
                                   stats.weight_sum, stats.weight_max, stats.pixel_count)
         stats.frames += 1
         return image.detach(), stats, fr.culling_mask
+
+
+# ---------------------------------------------------------------------------------------------------
+# 3D smoothing filter: the rate kernel, the filter from the rate, the baked export
+# ---------------------------------------------------------------------------------------------------
+def filter3d_rate(xyz, cameras_T_world, Ks, sizes, near_thresh=0.2, pad_fraction=0.15, camera_model="pinhole", out=None):
+    """-> rate [N] float32: for every Gaussian the finest sampling rate, in pixels per world unit, of the cameras that see
+    it (gs_filter3d_rate: one launch over all C cameras, xyz read once); 0 where no camera does.  cameras_T_world [C, 4, 4],
+    Ks [C, 3, 3] float32 on xyz's device; sizes: (W, H) for all cameras, or an int tensor [C, 2].  A camera sees a
+    Gaussian when z > near_thresh and uv lies inside the image padded by pad_fraction of its size on each side; its rate
+    is max(fx, fy) / z, for camera_model="fisheye" max(fx, fy) / |xyz_cam| (the radial rate).  out: a rate to raise in
+    place, so that calls over subsets of the cameras compose exactly.  The defaults are Mip-Splatting's."""
+    _require(camera_model in CAMERA_MODELS, f"camera_model must be one of {' / '.join(repr(m) for m in CAMERA_MODELS)}, "
+                                            f"got {camera_model!r}")
+    _require(torch.is_tensor(xyz) and xyz.is_cuda and xyz.dtype == torch.float32 and xyz.dim() == 2 and xyz.shape[1] == 3,
+             "filter3d_rate: xyz must be float32 [N, 3] on the GPU (no fp64, no CPU path)")
+    dev, N = xyz.device, int(xyz.shape[0])
+    _require(torch.is_tensor(cameras_T_world) and cameras_T_world.dim() == 3 and tuple(cameras_T_world.shape[1:]) == (4, 4),
+             "filter3d_rate: cameras_T_world must be [C, 4, 4]")
+    C = int(cameras_T_world.shape[0])
+    _require(torch.is_tensor(Ks) and tuple(Ks.shape) == (C, 3, 3), f"filter3d_rate: Ks must be [{C}, 3, 3], one per camera")
+    for name, t in (("cameras_T_world", cameras_T_world), ("Ks", Ks)):
+        _require(t.dtype == torch.float32 and t.device == dev, f"filter3d_rate: {name} must be float32 on xyz's device")
+    if torch.is_tensor(sizes):
+        _require(tuple(sizes.shape) == (C, 2) and not sizes.is_floating_point(),
+                 f"filter3d_rate: sizes must be (W, H) or an int tensor [{C}, 2]")
+        sizes = sizes.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        W, H = (int(s) for s in sizes)
+        sizes = torch.tensor([[W, H]], dtype=torch.int32, device=dev).repeat(C, 1)
+    if out is None:
+        out = torch.zeros(N, dtype=torch.float32, device=dev)
+    else:
+        _require(torch.is_tensor(out) and out.dtype == torch.float32 and out.device == dev and tuple(out.shape) == (N,)
+                 and out.is_contiguous() and not out.requires_grad,
+                 f"filter3d_rate: out must be a contiguous float32 [{N}] on xyz's device without a gradient")
+    mode = _hip.GS_RASTER_FISHEYE if camera_model == "fisheye" else _hip.GS_RASTER_CLASSIC
+    with torch.no_grad():
+        _hip.call("gs_filter3d_rate", _p(xyz.contiguous()), _p(cameras_T_world.contiguous()), _p(Ks.contiguous()), _p(sizes),
+                  C, N, near_thresh, pad_fraction, mode, _p(out), _stream())
+    return out
+
+
+def filter3d_from_rate(rate, variance=0.2):
+    """-> phi [N] = variance / rate^2, the world-space variance of a `variance` px^2 low-pass at the Gaussian's finest
+    sampling rate (Mip-Splatting: 0.2).  The rows no camera saw (rate == 0) take the largest phi of the rows that were
+    seen; all zero when none was.  No host read."""
+    seen = rate > 0
+    lowest = torch.where(seen, rate, torch.full_like(rate, float("inf"))).amin() if rate.numel() else rate.new_zeros(())
+    r = torch.where(seen, rate, lowest)          # (nothing seen: inf everywhere -> phi = 0)
+    return variance / (r * r)
+
+
+def bake_filter3d(gaussians, filter3d):
+    """-> Gaussians with the filter folded into the parameters, for export to a renderer without one:
+    scale' = 0.5 log(s^2 + phi), opacity' = logit(sigmoid(o) comp3) with comp3 = sqrt(prod_k s_k^2 / (s_k^2 + phi)); the
+    other tensors are shared.  A classic frame of the result shows the filtered scene.  Plain torch on the tensors'
+    device, differentiable; not for the training frame (rasterize(filter3d=) keeps the parameters unfiltered)."""
+    from .splat_py.structs import Gaussians
+    g = gaussians
+    phi = filter3d.to(g.scale.dtype).reshape(-1, 1)
+    s2 = torch.exp(g.scale) ** 2
+    d = s2 + phi
+    comp3 = torch.sqrt(torch.prod(s2 / d, dim=1, keepdim=True))
+    opa3 = torch.sigmoid(g.opacity) * comp3
+    return Gaussians(g.xyz, g.rgb, torch.log(opa3) - torch.log1p(-opa3), 0.5 * torch.log(d), g.quaternion, g.sh)

@@ -352,12 +352,83 @@ int gs_pose_backward_mode(const void* xyz, const void* quaternion, const void* s
                           const void* K, const int32_t* rank, const void* opacity_act, const void* grad_slab, int v_base,
                           int N, void* workspace, void* grad_camera_T_world, int raster_mode, void* stream);
 
+/* ---- 3D smoothing filter (fp32, ABI 20; the 3D half of Mip-Splatting, no reference counterpart) ----------------
+ * GS_RASTER_ANTIALIASED keeps a splat smaller than a pixel from adding light when the camera moves away; the other half
+ * is a per-Gaussian low-pass of the world-space covariance, sized by the finest rate at which any training camera
+ * samples the Gaussian, so that a scene does not grow needles when the camera moves closer.  filter3d [N] float32 holds
+ * phi >= 0, a variance in world units; it is a constant of the frame and carries no gradient.  Arithmetic (fp32, no
+ * contraction, IEEE divide and square root; one definition, csrc/pg_math.h filter3d_sigma / filter3d_terms_of /
+ * filter3d_bwd_of), with s_k = exp(scale_k):
+ *     Sigma_eff = Sigma + phi I          (the three diagonal entries of Sigma_world gain phi: R diag(s^2 + phi) R^T)
+ *     rho3  = ((s_0^2 / (s_0^2 + phi)) (s_1^2 / (s_1^2 + phi))) (s_2^2 / (s_2^2 + phi))
+ *     comp3 = rho3 > 0 ? sqrt(rho3) : 0                            (a NaN compares false: 0)
+ *     opa3  = opacity_act * comp3
+ *   forward   everything downstream reads Sigma_eff and opa3 where it read Sigma and the sigmoid: conic, bin_records, the
+ *             packed record's a, b, c, det; with GS_RASTER_ANTIALIASED comp is taken from the filtered conic and
+ *             packed[3] = opa3 * comp; the cutoff radius is evaluated on the final values.  A row with comp3 == 0 gets
+ *             packed[2] = -1 and never contributes.  opacity_act stays the sigmoid; uv, xyz_camera_frame, rgb_render, the
+ *             culling mask, rank and vis_idx do not depend on phi.
+ *   backward  with g = column 3 of the slab row (GS_RASTER_ANTIALIASED: after the fold of "antialiased opacity", which
+ *             takes opa3 in the place of y) and y = opacity_act:
+ *                 grad_opacity_logit = g comp3 (1 - y) y
+ *                 grad_scale[k]     += g opa3 phi / (s_k^2 + phi)
+ *             and the slab's conic columns reach quaternion and scale as dL/dSigma_eff = dL/dSigma, through the
+ *             unfiltered scale, unchanged.  No epsilon; a comp3 == 0 row gets opacity gradient 0 and no scale term.
+ *             gs_pose_backward_filtered forms the same Sigma_eff and, under the fold, the same opa3.  A filter can make
+ *             a splat millions of pixels wide: with a filter the fold's three conic terms are formed beyond
+ *             det_d > 1e18 as g_rho (c0 - rho c) / det_d, g_rho b (rho - 1) / det_d, g_rho (a0 - rho a) / det_d, whose
+ *             products stay inside fp32's range (det_d det_d does not); below, the expressions above, bit for bit.
+ *             This widens the range, it does not remove the limit: from conic ~ 1e19 px^2 on det_0 = a0 c0 - b b and
+ *             det_d themselves are infinite and comp = sqrt(inf / inf) is not a number, with or without a filter.
+ * With phi == 0 every expression is exact, so such a row carries the values of the call without a filter, forward and
+ * backward.
+ * gs_preprocess_forward_filtered / gs_preprocess_backward_filtered / gs_pose_backward_filtered: the arguments of the
+ * _mode entries with filter3d in front of raster_mode.  filter3d == NULL launches exactly what the _mode entry launches;
+ * the filter is selected by the pointer, not by a raster_mode bit (raster_mode stays GS_RASTER_ANTIALIASED |
+ * GS_RASTER_FISHEYE, anything else GS_EINVAL as there).  Whole frames only: a tile-row band with a filter is GS_EINVAL
+ * (message names filter3d).  The backward entries take slices like the _mode ones: filter3d then points at the slice's
+ * first row, as xyz, quaternion, scale and rank do.
+ *
+ * gs_filter3d_rate: rate[g] = max(rate[g], max over the cameras k that see Gaussian g of f_k / depth), the sampling
+ * rate in pixels per world unit.  camera_T_world [C,4,4], K [C,3,3] float32, sizes [C,2] int32 = (W, H) per camera.  With
+ * c = camera_T_world_k xyz_g and (u, v) the model's own projection (GS_RASTER_CLASSIC: the pinhole one; GS_RASTER_FISHEYE:
+ * the equidistant one above), camera k sees g when z > near_thresh and -pad_fraction W < u < W + pad_fraction W,
+ * -pad_fraction H < v < H + pad_fraction H; f = max(fx, fy); depth = z (pinhole) or |c| (fisheye: the radial rate, which
+ * understates the tangential one by theta / sin(theta)).  rate is read and written: a row no camera sees keeps its
+ * value and calls over subsets of the cameras compose exactly (start from zeros).  One launch, one thread per Gaussian;
+ * xyz is read once.  C == 0 or N == 0 returns GS_OK without a launch; a raster_mode that is neither value, a negative
+ * count or a NULL pointer is GS_EINVAL and writes nothing.  The filter is phi = variance / rate^2 (Mip-Splatting:
+ * variance 0.2 px^2; fused.filter3d_from_rate). */
+int gs_preprocess_forward_filtered(const void* xyz, const void* quaternion, const void* scale,
+                                   const void* opacity, const void* rgb, const void* sh, int n_sh,
+                                   const void* camera_T_world, const void* K, int N, int W, int H,
+                                   float near_thresh, float far_thresh, float cull_mask_padding,
+                                   float mh_dist, int band_row0, int band_row1,
+                                   int32_t* workspace, void* camera_center, int32_t* visible_count,
+                                   uint8_t* culling_mask, int32_t* rank, int32_t* vis_idx, void* uv,
+                                   void* xyz_camera_frame, void* conic, void* opacity_act, void* rgb_render,
+                                   void* packed, void* bin_records, int32_t* cut_workspace, int32_t* depth_hist,
+                                   int sample_stride, const void* filter3d, int raster_mode, void* stream);
+int gs_preprocess_backward_filtered(const void* xyz, const void* quaternion, const void* scale, int n_sh,
+                                    const void* camera_T_world, const void* K, const void* camera_center,
+                                    const int32_t* rank, const void* opacity_act, const void* grad_slab,
+                                    int v_base, int N, void* grad_xyz, void* grad_quaternion,
+                                    void* grad_scale, void* grad_opacity_logit, void* grad_rgb_param,
+                                    void* grad_sh, const void* filter3d, int raster_mode, void* stream);
+int gs_pose_backward_filtered(const void* xyz, const void* quaternion, const void* scale, const void* camera_T_world,
+                              const void* K, const int32_t* rank, const void* opacity_act, const void* grad_slab,
+                              int v_base, int N, void* workspace, void* grad_camera_T_world, const void* filter3d,
+                              int raster_mode, void* stream);
+int gs_filter3d_rate(const void* xyz, const void* camera_T_world, const void* K, const int32_t* sizes, int C, int N,
+                     float near_thresh, float pad_fraction, int raster_mode, void* rate, void* stream);
+
 /* ---- the classic per-Gaussian entries: one-line forwards, kept for callers outside the package ----
  *   gs_preprocess_forward      -> gs_preprocess_forward_cut with bin_records, cut_workspace, depth_hist NULL, sample_stride 0
  *   gs_preprocess_forward_cut  -> gs_preprocess_forward_mode with GS_RASTER_CLASSIC
  *   gs_preprocess_backward     -> gs_preprocess_backward_mode with GS_RASTER_CLASSIC
  *   gs_pose_backward           -> gs_pose_backward_mode with opacity_act NULL and GS_RASTER_CLASSIC
- * The package's own callers (fused.py, csrc/frame_hip.cpp) call the _mode entries in every mode. */
+ * The _mode entries forward in the same way to the _filtered ones (ABI 20) with filter3d NULL; the package's own callers
+ * (fused.py, csrc/frame_hip.cpp) call those in every mode. */
 int gs_preprocess_forward(const void* xyz, const void* quaternion, const void* scale,
                           const void* opacity, const void* rgb, const void* sh, int n_sh,
                           const void* camera_T_world, const void* K, int N, int W, int H,
