@@ -34,6 +34,11 @@ filter3d= on the entry points is Mip-Splatting's 3D smoothing filter (DESIGN.md 
 that the per-Gaussian stage adds to the covariance and compensates in the opacity, forward and backward
 (gs_preprocess_forward_filtered and its two backward twins).  filter3d_rate / filter3d_from_rate make the filter from the
 training cameras (gs_filter3d_rate), bake_filter3d folds it into the parameters for export.
+
+rasterize_normals is the feature frame with the channels filled in for the normal-consistency regulariser:
+_GaussianNormals (gs_gaussian_normals / gs_gaussian_normals_backward) forms the visible Gaussians' normals, the feature
+walk composites (n_x, n_y, n_z, z) into a normal map and the depth map.  depth_to_normal (_DepthNormal: gs_depth_normal /
+gs_depth_normal_backward) is the other side of that loss, the normal of a rendered depth map.
 """
 import os
 from types import SimpleNamespace
@@ -119,6 +124,7 @@ def last_flags(clear=False):
 _keep_slab = False
 _last_slab = None
 _last_grad_z = None   # rasterize_rgbd frames: dL/dz [V] of the visible Gaussians, kept with the slab
+_last_grad_normals = None   # rasterize_normals frames: dL/dn [V, 3] of the visible Gaussians' normals, kept with the slab
 _slab_slot = None   # the native module holding the slot, fixed by keep_last_slab(True)
 
 
@@ -127,8 +133,8 @@ def keep_last_slab(on):
     latest per-Gaussian backward.  The render backward's summation order differs from run to run, so a gradient
     derived from the slab (camera_T_world's) can only be checked against the slab it was computed from.  Every call
     drops what was kept."""
-    global _keep_slab, _last_slab, _slab_slot, _last_grad_z
-    _keep_slab, _last_slab, _last_grad_z = bool(on), None, None
+    global _keep_slab, _last_slab, _slab_slot, _last_grad_z, _last_grad_normals
+    _keep_slab, _last_slab, _last_grad_z, _last_grad_normals = bool(on), None, None, None
     if _native_mod is not None:
         _native_mod.keep_last_slab(False)
     _slab_slot = native() if on else None
@@ -146,6 +152,12 @@ def last_grad_z():
     """dL/dz [V] (z = xyz_camera_frame[:, 2]) that the latest rasterize_rgbd backward since keep_last_slab(True) handed
     to the per-Gaussian node next to the slab; None if that frame's depth went unused or there was none"""
     return _last_grad_z
+
+
+def last_grad_normals():
+    """dL/dn [V, 3] that the latest rasterize_normals backward since keep_last_slab(True) handed to the normals' node
+    (what gs_gaussian_normals_backward and the pose's rotation term were computed from); None if there was none"""
+    return _last_grad_normals
 
 
 def _note_slab(slab, V):
@@ -755,6 +767,43 @@ def contributions_forward(packed, ranges, sorted_g, nsp, height, width, row_inde
               nty, _p(weight_sum), _p(weight_max), _p(pixel_count), _stream())
 
 
+def gaussian_normals_forward(quaternion, scale, camera_T_world, vis_idx, xyz_cam):
+    """-> normals [V, 3] of the visible Gaussians in the camera frame, facing the camera (gs_gaussian_normals): column
+    argmin(log-scale) of the rotation of the normalised quaternion, rotated by the pose; vis_idx int32 [V], xyz_cam [V, 3]
+    as the per-Gaussian stage left them"""
+    V = int(vis_idx.shape[0])
+    normals = torch.empty(V, 3, dtype=torch.float32, device=quaternion.device)
+    _hip.call("gs_gaussian_normals", _p(quaternion), _p(scale), _p(camera_T_world), _p(vis_idx), _p(xyz_cam), V,
+              _p(normals), _stream())
+    return normals
+
+
+def gaussian_normals_backward(quaternion, scale, camera_T_world, rank, xyz_cam, grad_normals):
+    """-> grad_quaternion [N, 4], every row written, culled rows zero (gs_gaussian_normals_backward); rank int32 [N]"""
+    N, V = int(quaternion.shape[0]), int(grad_normals.shape[0])
+    grad_q = torch.empty(N, 4, dtype=torch.float32, device=quaternion.device)
+    _hip.call("gs_gaussian_normals_backward", _p(quaternion), _p(scale), _p(camera_T_world), _p(rank), _p(xyz_cam),
+              _p(grad_normals), V, N, _p(grad_q), _stream())
+    return grad_q
+
+
+def depth_normal_forward(depth, alpha, K, min_alpha, raster_mode):
+    """-> normal [H, W, 3] of the depth map depth / alpha, zero where invalid (gs_depth_normal)"""
+    H, W = int(depth.shape[0]), int(depth.shape[1])
+    normal = torch.empty(H, W, 3, dtype=torch.float32, device=depth.device)
+    _hip.call("gs_depth_normal", _p(depth), _p(alpha), _p(K), W, H, float(min_alpha), raster_mode, _p(normal), _stream())
+    return normal
+
+
+def depth_normal_backward(depth, alpha, K, grad_normal, min_alpha, raster_mode):
+    """-> grad_depth, grad_alpha [H, W], written for every pixel (gs_depth_normal_backward); one allocation"""
+    H, W = int(depth.shape[0]), int(depth.shape[1])
+    buf = torch.empty(2, H, W, dtype=torch.float32, device=depth.device)
+    _hip.call("gs_depth_normal_backward", _p(depth), _p(alpha), _p(K), _p(grad_normal), W, H, float(min_alpha),
+              raster_mode, _p(buf[0]), _p(buf[1]), _stream())
+    return buf[0], buf[1]
+
+
 def _as_slab(g_uv, g_conic, g_opa, g_rgb, V, dev):
     """the four render gradients as one [V, 9] slab: the slab they are views of when they come
     straight from _Render.backward, a packed copy otherwise (outputs nobody consumed count as 0)"""
@@ -805,7 +854,8 @@ def _frame_record(width, height, near_thresh, far_thresh, cull_mask_padding, mh_
         may_cut=may_cut,
         slab_sync=slab_sync, absgrad=bool(absgrad), uv_absgrad=None,
         # after _Preprocess.forward (xyz_cam and vis_idx: the V visible rows)
-        packed=None, xyz_cam=None, culling_mask=None, ranges=None, sorted_g=None, vis_idx=None, keys=None, cut=None,
+        packed=None, xyz_cam=None, culling_mask=None, ranges=None, sorted_g=None, vis_idx=None, rank=None, keys=None,
+        cut=None,
         rendered=None)   # (image, nsp, fw, cost, seg) when _Preprocess.forward already enqueued _Render's kernels
 
 
@@ -845,7 +895,7 @@ class _Preprocess(torch.autograd.Function):
             fr.rendered = pre
         V = f.V
         fr.packed, fr.xyz_cam, fr.culling_mask, fr.ranges = f.packed, f.xyz_cam[:V], f.culling_mask, f.ranges
-        fr.sorted_g, fr.vis_idx, fr.keys, fr.cut = f.sorted_g, f.vis_idx[:V], f.keys, f.cut
+        fr.sorted_g, fr.vis_idx, fr.rank, fr.keys, fr.cut = f.sorted_g, f.vis_idx[:V], f.rank, f.keys, f.cut
         ctx.save_for_backward(xyz, quaternion, scale, camera_T_world, K)
         ctx.set_materialize_grads(False)   # no zero tensor for an output nobody consumed
         ctx.fr = fr
@@ -1000,6 +1050,54 @@ class _GatherRows(torch.autograd.Function):
     def backward(ctx, grad):
         (index,) = ctx.saved_tensors
         return torch.zeros(ctx.shape, dtype=grad.dtype, device=grad.device).index_copy_(0, index, grad), None
+
+
+class _GaussianNormals(torch.autograd.Function):
+    """quaternion, scale, pose, the frame record (after _Preprocess.forward) -> normals [V, 3] of the visible Gaussians.
+    The axis choice and the flip are constants: scale gets no gradient, and neither does xyz (the record's xyz_cam is read
+    for the flip's sign only).  The pose's direct term, n_c = W n_w, is plumbing on the visible rows like the z term of
+    _Preprocess.backward: dL/dW = sum_v g_v (x) (+-n_w,v), and with W a rotation +-n_w,v = W^T n_c,v, the rows of
+    normals @ W; the sum is taken in float64."""
+
+    @staticmethod
+    def forward(ctx, quaternion, scale, camera_T_world, fr):
+        normals = gaussian_normals_forward(quaternion, scale, camera_T_world, fr.vis_idx, fr.xyz_cam)
+        ctx.save_for_backward(quaternion, scale, camera_T_world, normals)
+        ctx.fr = fr
+        return normals
+
+    @staticmethod
+    def backward(ctx, grad):
+        quaternion, scale, camera_T_world, normals = ctx.saved_tensors
+        fr = ctx.fr
+        grad = grad.contiguous()
+        if _keep_slab:
+            global _last_grad_normals
+            _last_grad_normals = grad
+        g_q = gaussian_normals_backward(quaternion, scale, camera_T_world, fr.rank, fr.xyz_cam, grad) \
+            if ctx.needs_input_grad[0] else None
+        g_pose = None
+        if ctx.needs_input_grad[2]:
+            g_pose = torch.zeros_like(camera_T_world)
+            if grad.shape[0] > 0:
+                g_pose[:3, :3] = (grad.double().t() @ (normals.double() @ camera_T_world[:3, :3].double())).float()
+        return g_q, None, g_pose, None
+
+
+class _DepthNormal(torch.autograd.Function):
+    """depth, alpha [H, W], K -> the depth map's normal [H, W, 3]; the validity decisions are constants"""
+
+    @staticmethod
+    def forward(ctx, depth, alpha, K, min_alpha, raster_mode):
+        ctx.save_for_backward(depth, alpha, K)
+        ctx.options = (min_alpha, raster_mode)
+        return depth_normal_forward(depth, alpha, K, min_alpha, raster_mode)
+
+    @staticmethod
+    def backward(ctx, grad):
+        depth, alpha, K = ctx.saved_tensors
+        g_depth, g_alpha = depth_normal_backward(depth, alpha, K, grad.contiguous(), *ctx.options)
+        return g_depth, g_alpha, None, None, None
 
 
 class _RenderSH(torch.autograd.Function):
@@ -1355,6 +1453,68 @@ def rasterize_features(gaussians, features, camera_T_world, camera, near_thresh,
     feat = _GatherRows.apply(features, fr.vis_idx.long()).contiguous()
     image, feature_map, alpha = _Render.apply(uv, conic, opacity, rgb, feat, fr, _FeatureMap)
     return image, feature_map, alpha, fr.culling_mask, uv
+
+
+def rasterize_normals(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+                      use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None,
+                      slab_sync=None, frame_hook=None, adam_plan=None, antialiased=False,
+                      camera_model="pinhole", filter3d=None):
+    """rasterize() with the two maps the normal-consistency regulariser of 2DGS reads, from one frame:
+
+        image, depth, alpha, normal_map, culling_mask, uv = rasterize_normals(...)
+
+    Each visible Gaussian's normal is the axis of its smallest log-scale (ties: the lowest index), rotated by its
+    normalised quaternion and by the pose, and negated where it points away from the camera (n . xyz_cam > 0); the
+    feature walk composites (n_x, n_y, n_z, z) with the frame's weights w_k = alpha_k T_k.  image, culling_mask and uv are
+    those of rasterize(), depth [H, W] = sum w z and alpha [H, W] = sum w those of rasterize_rgbd() on the same inputs,
+    bit for bit.  normal_map [H, W, 3] = sum w n is NOT normalised (2DGS's rend_normal); no background term.  All four
+    maps carry gradients to the Gaussians' parameters -- z by rasterize_rgbd's route, the normals to the quaternion
+    through gs_gaussian_normals_backward (the axis choice and the flip are constants: scale and xyz get nothing from
+    them) -- and, when it requires one, to camera_T_world, the normals' rotation term included.
+    depth_to_normal gives the other side of the loss, train_ops.normal_consistency_loss the loss itself.  Served like
+    rasterize_features: whole single-GPU fp32 frames in the SH-precompute colour mode, Python orchestration, depth cut
+    off; anything else raises RuntimeError before a kernel is enqueued (the trailing keyword arguments exist only to
+    say so).  adam_plan is refused too: the fused optimizer step moves the quaternion inside the per-Gaussian backward,
+    and the normals' quaternion gradient would arrive after it.  antialiased, camera_model, filter3d: as rasterize()'s
+    (the normal itself does not depend on the projection model)."""
+    _require(adam_plan is None, "rasterize_normals does not take the fused optimizer step (adam_plan): it steps the "
+                                "quaternion inside the per-Gaussian backward, before the normals' gradient reaches it")
+    g = gaussians
+    fr, (uv, conic, opacity, rgb, z) = _begin_frame(
+        g, g.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+        background_rgb, "rasterize_normals", use_sh_precompute,
+        (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), adam_plan=adam_plan,
+        antialiased=antialiased, z_out=True, camera_model=camera_model, filter3d=filter3d)
+    normals = _GaussianNormals.apply(g.quaternion.contiguous(), g.scale.contiguous(), camera_T_world.contiguous(), fr)
+    feat = torch.cat((normals, z[:, None]), dim=1)
+    image, feature_map, alpha = _Render.apply(uv, conic, opacity, rgb, feat, fr, _FeatureMap)
+    return image, feature_map[..., 3], alpha, feature_map[..., :3], fr.culling_mask, uv
+
+
+def depth_to_normal(depth, alpha, camera, camera_model="pinhole", min_alpha=0.0):
+    """-> normal [H, W, 3] float32: the unit normal of the surface the depth map d = depth / alpha describes, from the
+    central differences of the back-projected points, n = normalize((P(x, y+1) - P(x, y-1)) x (P(x+1, y) - P(x-1, y)))
+    (2DGS's depth_to_normal orientation: towards the camera, like rasterize_normals' normals).  depth, alpha: float32
+    [H, W] on the GPU, unnormalised as rasterize_rgbd / rasterize_normals / rasterize_distortion return them; camera.K the
+    frame's intrinsics; camera_model the frame's ("fisheye": P = d (tan(theta) / theta a, 1), a ray at or beyond 90
+    degrees is invalid).  A pixel is valid when it is off the image's border, it and its four neighbours have
+    alpha > min_alpha (>= 0) and a valid ray, and the cross product is not zero; invalid pixels are (0, 0, 0).
+    Differentiable in depth and alpha with the validity held constant (gs_depth_normal / gs_depth_normal_backward;
+    DESIGN.md 7l).  Anything else raises RuntimeError."""
+    _require(camera_model in CAMERA_MODELS, f"camera_model must be one of {' / '.join(repr(m) for m in CAMERA_MODELS)}, "
+                                            f"got {camera_model!r}")
+    for name, t in (("depth", depth), ("alpha", alpha)):
+        _require(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2,
+                 f"depth_to_normal: {name} must be float32 [H, W] on the GPU (no fp64, no CPU path)")
+    _require(alpha.shape == depth.shape and alpha.device == depth.device,
+             f"depth_to_normal: alpha must match depth, got {list(alpha.shape)} and {list(depth.shape)}")
+    K = camera.K
+    _require(torch.is_tensor(K) and K.dtype == torch.float32 and K.device == depth.device and tuple(K.shape) == (3, 3),
+             "depth_to_normal: camera.K must be float32 [3, 3] on the maps' device")
+    min_alpha = float(min_alpha)
+    _require(min_alpha >= 0.0, f"depth_to_normal: min_alpha must be a number >= 0, got {min_alpha}")
+    mode = _hip.GS_RASTER_FISHEYE if camera_model == "fisheye" else _hip.GS_RASTER_CLASSIC
+    return _DepthNormal.apply(depth.contiguous(), alpha.contiguous(), K.contiguous(), min_alpha, mode)
 
 
 class ContributionStats:

@@ -13,6 +13,8 @@
     SelectiveAdam             Adam whose step(culling_mask=...) steps only the Gaussians the frame saw (the
                               `sparse_adam` / SelectiveAdam of other trainers): a culled row's parameters and
                               moments are neither read nor written; one HIP launch (gs_adam_step_rows)
+    normal_consistency_loss   2DGS's normal-consistency regulariser over fused.rasterize_normals' maps and
+                              fused.depth_to_normal (plain torch over the kernel's output: not a hot path)
     accumulate_grad_stats     trainer.py:378-385 (densification statistics) in one launch, without
                               the boolean-mask index_put and its host sync
 
@@ -417,3 +419,23 @@ def ssim_l1_loss(image, target, ssim_frac=0.2, return_terms=False):
         raise RuntimeError("ssim_l1_loss: target must match image")
     loss, terms = _SsimL1Loss.apply(image.contiguous(), target.contiguous(), ssim_frac)
     return (loss, terms) if return_terms else loss
+
+
+def normal_consistency_loss(normal_map, depth, alpha, camera, camera_model="pinhole", min_alpha=0.0):
+    """The normal-consistency regulariser of 2DGS over the maps of fused.rasterize_normals:
+
+        mean over the valid pixels of  alpha.detach() - sum_c normal_map[..., c] * n_d[..., c]
+
+    with n_d = fused.depth_to_normal(depth, alpha, camera, camera_model, min_alpha) and a pixel valid where n_d exists:
+    2DGS's 1 - N . (alpha n_d) for its unnormalised N, restricted to the pixels that have a depth normal.  -> a 0-d
+    tensor, differentiable in normal_map, depth and alpha; a frame without a valid pixel gives a zero that still carries
+    the graph.  Composed in PyTorch over the kernel's output: a handful of elementwise launches and two reductions per
+    frame, not a hot path; no host read."""
+    from . import fused
+    if not (torch.is_tensor(normal_map) and normal_map.dim() == 3 and normal_map.shape[2] == 3
+            and normal_map.shape[:2] == depth.shape):
+        raise RuntimeError("normal_consistency_loss: normal_map must be [H, W, 3] over depth's [H, W]")
+    n_d = fused.depth_to_normal(depth, alpha, camera, camera_model, min_alpha)
+    valid = (n_d.detach() != 0).any(dim=2)
+    per_pixel = alpha.detach() - (normal_map * n_d).sum(dim=2)
+    return torch.where(valid, per_pixel, torch.zeros_like(per_pixel)).sum() / valid.sum().clamp(min=1)

@@ -422,6 +422,56 @@ int gs_pose_backward_filtered(const void* xyz, const void* quaternion, const voi
 int gs_filter3d_rate(const void* xyz, const void* camera_T_world, const void* K, const int32_t* sizes, int C, int N,
                      float near_thresh, float pad_fraction, int raster_mode, void* rate, void* stream);
 
+/* ---- Normals (ABI 21; no reference counterpart) -------------------------------------------------------------------
+ * What the normal-consistency regulariser of 2DGS needs around gs_render_features (channels n_x, n_y, n_z, z): the
+ * visible Gaussians' normals, and the normal of the rendered depth map.  fp32, no contraction, IEEE divide and square
+ * root; no scratch, no atomics, no workspace.
+ *
+ * gs_gaussian_normals: for each visible row v < V, with i = vis_idx[v] the Gaussian's dense row:
+ *     qhat = quaternion[i] / |quaternion[i]|                      (csrc/pg_math.h sigma_world_of's normalisation)
+ *     R    = quat_to_rot(qhat)
+ *     a    = the index of the smallest of scale[i, 0:3], the log-scales themselves; on a tie the lowest index
+ *     n_c  = W R[:, a]       with W the rotation of camera_T_world (rows 0..2, columns 0..2)
+ *     normals[v] = n_c . xyz_camera_frame[v] > 0 ? -n_c : n_c     (faces the camera; an exact 0 is not flipped)
+ *   The normal does not depend on the projection model: there is no raster_mode.  normals [V,3] is written for the V
+ *   rows and nothing behind them.  V == 0 returns GS_OK without a launch.
+ * gs_gaussian_normals_backward: grad_normals [V,3] -> grad_quaternion [N,4], through W, the rotation and the
+ *   normalisation, with the axis and the flip held constant (the normal is piecewise constant in scale and xyz: they
+ *   get no gradient).  One thread per Gaussian of the N through rank (rank[i] = the visible row of Gaussian i, negative
+ *   when culled, as gs_preprocess_backward reads it; whole frames: no v_base): every one of the N rows is WRITTEN,
+ *   culled rows as zeros.  N == 0 returns GS_OK without a launch.
+ *
+ * gs_depth_normal: the normal of the surface a rendered depth map describes.  depth, alpha [H,W] as gs_render_zalpha
+ *   writes them (sum w z, sum w), d = depth / alpha, K float32 [3,3] on the device.  Pixel (x, y) has the renderer's
+ *   integer coordinate, no half-pixel offset, and back-projects to
+ *       GS_RASTER_CLASSIC   P = d ((x - cx) / fx, (y - cy) / fy, 1)
+ *       GS_RASTER_FISHEYE   a = ((x - cx) / fx, (y - cy) / fy), theta = |a|,  P = d (tan(theta) / theta a, 1)
+ *                           tan(theta) / theta from +, *, / alone (csrc/normals.hip tan_over_theta; no library call, so
+ *                           the tests' float32 restatement repeats it): up to theta = pi / 4 the quotient of the series
+ *                           of sin(theta) / theta and cos(theta) -- no division by theta, 1 at the axis -- beyond it
+ *                           the same series at pi / 2 - theta; within 2.6e-7 relative.  theta >= pi / 2 (in float32:
+ *                           not below the float above pi / 2) is an invalid ray
+ *       n = normalize((P(x, y + 1) - P(x, y - 1)) x (P(x + 1, y) - P(x - 1, y)))
+ *   2DGS's depth_to_normal orientation: towards the camera, like the Gaussians' normals.  A pixel is valid iff it is
+ *   not on the image's border, it and its four neighbours have alpha > min_alpha and, under the fisheye model, a valid
+ *   ray, and the cross product's squared norm is > 0 (a NaN compares false).  normal [H,W,3] is written for every pixel,
+ *   (0, 0, 0) where invalid.  min_alpha must be >= 0 (so that d is formed only where alpha > 0).
+ * gs_depth_normal_backward: grad_normal [H,W,3] -> grad_depth, grad_alpha [H,W], both written for every pixel (not
+ *   accumulated), with d d / d depth = 1 / alpha, d d / d alpha = -depth / alpha^2 and the validity decisions constants.
+ *   A gather: each pixel sums, in a fixed order, the terms of the up to four valid centres whose stencil holds it;
+ *   two runs are bit-equal.
+ * Both: raster_mode other than the two values, a negative size, a min_alpha that is negative or not a number, or a NULL
+ * pointer is GS_EINVAL and writes nothing; W == 0 or H == 0 returns GS_OK without a launch. */
+int gs_gaussian_normals(const void* quaternion, const void* scale, const void* camera_T_world, const int32_t* vis_idx,
+                        const void* xyz_camera_frame, int V, void* normals, void* stream);
+int gs_gaussian_normals_backward(const void* quaternion, const void* scale, const void* camera_T_world,
+                                 const int32_t* rank, const void* xyz_camera_frame, const void* grad_normals, int V, int N,
+                                 void* grad_quaternion, void* stream);
+int gs_depth_normal(const void* depth, const void* alpha, const void* K, int W, int H, float min_alpha, int raster_mode,
+                    void* normal, void* stream);
+int gs_depth_normal_backward(const void* depth, const void* alpha, const void* K, const void* grad_normal, int W, int H,
+                             float min_alpha, int raster_mode, void* grad_depth, void* grad_alpha, void* stream);
+
 /* ---- the classic per-Gaussian entries: one-line forwards, kept for callers outside the package ----
  *   gs_preprocess_forward      -> gs_preprocess_forward_cut with bin_records, cut_workspace, depth_hist NULL, sample_stride 0
  *   gs_preprocess_forward_cut  -> gs_preprocess_forward_mode with GS_RASTER_CLASSIC
