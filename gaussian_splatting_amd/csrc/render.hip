@@ -1352,17 +1352,21 @@ __device__ __forceinline__ void flush_sum_slots(float* s_acc, const float* s_geo
         float a[SV];
 #pragma unroll
         for (int j = 0; j < SV; j++) a[j] = 0;
+        bool any_hit = false;
 #pragma unroll
         for (int w4 = 0; w4 < 4; w4++) {
             if ((s_hit[w4][tid >> 6] >> (tid & 63)) & 1ull) {
+                any_hit = true;
                 const float* sl = s_acc + (w4 * RCHUNK + tid) * SV;
 #pragma unroll
                 for (int j = 0; j < SV; j++) a[j] += sl[j];
             }
         }
+        // (a splat no wave hit keeps its zeros unscaled: 1 / det = inf of a record whose determinant cancelled to 0
+        // would make them NaN; see render_bwd_walk.inc)
         const float* rec = s_geom + tid * GS_PACKED_WIDTH;
         const float ca = rec[4], cb = rec[5], cc = rec[6];
-        const float k = -0.5f * rec[3] * rec[8];
+        const float k = any_hit ? -0.5f * rec[3] * rec[8] : 0.0f;
         const float Mu = a[4], Mv = a[5];
         a[4] = -2.0f * k * (cc * Mu - cb * Mv);
         a[5] = -2.0f * k * (ca * Mv - cb * Mu);
@@ -1409,7 +1413,7 @@ __device__ __forceinline__ void flush_sum_slots(float* s_acc, const float* s_geo
 //           blocks, so that no instruction of the nine sums depends on them; 0 in lanes that do not contribute
 //   wave    reduce2_to_slot into the wave's own pair per staged splat (s_abs [wave][splat][2], 2 KB; reduce9_to_slot
 //           and the nine-word slots stay as they are), in the visits that write the nine-word slot (s_hit serves both)
-//   flush   thread = splat adds the pairs of the waves that wrote, multiplies by opacity / det (rec[3] rec[8] = |-2k|
+//   flush   thread = splat adds the pairs of the waves that wrote, multiplies by opacity |1 / det| (rec[3] |rec[8]| = |-2k|
 //           of the nine sums' flush) and parks the pair in wave 0's; a second short pass, thread = value, sends one
 //           global atomic per value per (splat, tile) to g_uv_abs[g, 2]; rows of two zeros stay untouched
 template <typename T, int N_SH>

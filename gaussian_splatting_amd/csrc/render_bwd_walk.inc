@@ -293,18 +293,23 @@
             float a[SV];
 #pragma unroll
             for (int j = 0; j < SV; j++) a[j] = 0;
+            bool any_hit = false;
 #pragma unroll
             for (int w4 = 0; w4 < 4; w4++) {
                 if ((s_hit[w4][tid >> 6] >> (tid & 63)) & 1ull) {
+                    any_hit = true;
                     const float* sl = s_acc + (w4 * RCHUNK + tid) * SV;
 #pragma unroll
                     for (int j = 0; j < SV; j++) a[j] += sl[j];
                 }
             }
-            // sums of (w, w du, w dv) and of the per-pixel conic terms -> gradients (see the loop)
+            // sums of (w, w du, w dv) and of the per-pixel conic terms -> gradients (see the loop).  A splat no wave
+            // hit keeps its zeros unscaled: a record whose fp32 determinant cancelled to 0 carries 1 / det = inf (and
+            // r2 = inf: it is staged in every tile), nobody can hit it (mh = q * inf never passes the alpha test), and
+            // 0 * inf would flush NaN where the reference leaves its zeros.  A splat that was hit has a finite 1 / det.
             const float* rec = s_geom + tid * GS_PACKED_WIDTH;
             const float ca = rec[4], cb = rec[5], cc = rec[6];
-            const float k = -0.5f * rec[3] * rec[8];
+            const float k = any_hit ? -0.5f * rec[3] * rec[8] : 0.0f;
             const float Mu = a[4], Mv = a[5];
             a[4] = -2.0f * k * (cc * Mu - cb * Mv);
             a[5] = -2.0f * k * (ca * Mv - cb * Mu);
@@ -316,7 +321,7 @@
             for (int j = 0; j < SV; j++) row[j] = a[j];
 #if GS_BWD_ABS
             {
-                // the pair: the same waves' slots in the same order, times opacity / det (both positive)
+                // the pair: the same waves' slots in the same order, times opacity |1 / det|
                 float eu = 0, ev = 0;
 #pragma unroll
                 for (int w4 = 0; w4 < 4; w4++) {
@@ -325,7 +330,9 @@
                         ev += s_abs[(w4 * RCHUNK + tid) * 2 + 1];
                     }
                 }
-                const float od = rec[3] * rec[8];
+                // (as k above: zeros stay zeros; |1 / det|: a record whose fp32 determinant came out negative is
+                // taken where form / det > 0, and these are sums of magnitudes)
+                const float od = any_hit ? rec[3] * fabsf(rec[8]) : 0.0f;
                 s_abs[tid * 2 + 0] = eu * od;
                 s_abs[tid * 2 + 1] = ev * od;
             }

@@ -904,7 +904,8 @@ void render_tiles_backward(const T* uvs, const T* opacity, const T* rgb, const T
                                     for (int ch = 0; ch < 3; ch++)
                                         L[n_sh * ch + s] += std::fabs((double)Y[s] * grl[ch]);
                                 const double gm = 0.5 * (double)norm_prob * std::fabs((double)opacity[g]) * ga;
-                                const double u = u_diff, v = v_diff, rd = rdet;
+                                // (|1 / det|: a record whose fp32 determinant came out negative is walked like any other)
+                                const double u = u_diff, v = v_diff, rd = std::fabs((double)rdet);
                                 const double cfm = (std::fabs((double)a) * v * v + 2 * std::fabs((double)b * u * v) +
                                                     std::fabs((double)c) * u * u) * rd * rd;
                                 L[C + 0] += (double)norm_prob * ga;

@@ -290,6 +290,129 @@ def general_camera_scene(seed, N, W=None, H=None, deg=0, kind="landscape", stres
                            mh=mh, rows=rows, kind=kind, seed=seed)
 
 
+# ---- a scene whose extreme needles have a degenerate fp32 record determinant, by construction -------------------------
+DET_CLASSES = ("zero", "neg", "noisy")
+N_NEEDLES, N_CONTROLS, N_ANGLES = 48, 8, 64
+
+
+def rot_to_quat(R):
+    """(w, x, y, z) of rotation matrices R [M, 3, 3] (quat_to_rot's convention), float64"""
+    r = lambda i, j: R[:, i, j]
+    # the four rows of 4 q q^T from the matrix' entries; the one with the largest diagonal element is well conditioned
+    cands = torch.stack([
+        torch.stack([1 + r(0, 0) + r(1, 1) + r(2, 2), r(2, 1) - r(1, 2), r(0, 2) - r(2, 0), r(1, 0) - r(0, 1)], dim=1),
+        torch.stack([r(2, 1) - r(1, 2), 1 + r(0, 0) - r(1, 1) - r(2, 2), r(0, 1) + r(1, 0), r(0, 2) + r(2, 0)], dim=1),
+        torch.stack([r(0, 2) - r(2, 0), r(0, 1) + r(1, 0), 1 - r(0, 0) + r(1, 1) - r(2, 2), r(1, 2) + r(2, 1)], dim=1),
+        torch.stack([r(1, 0) - r(0, 1), r(0, 2) + r(2, 0), r(1, 2) + r(2, 1), 1 - r(0, 0) - r(1, 1) + r(2, 2)], dim=1)],
+        dim=1)                                                        # [M, 4 candidates, 4]
+    best = torch.diagonal(cands, dim1=1, dim2=2).argmax(dim=1)
+    q = cands[torch.arange(R.shape[0]), best]
+    q = q / q.norm(dim=1, keepdim=True)
+    assert float((quat_to_rot(q) - R).abs().max()) < 1e-6   # (R comes from the fp32 pose: orthonormal to 1e-7)
+    return q
+
+
+def needle_rows(sc, angles_deg):
+    """the constructed Gaussians for in-plane angles angles_deg [M] (row m is slot m % (N_NEEDLES + N_CONTROLS)) ->
+    xyz, quaternion, log_scale, logit [M, ...] float64.  Slot i < N_NEEDLES: a needle (even i: scales long, short,
+    short) or a disc seen edge-on (odd i: long, short, long along the view axis) with log10 of the ratio stepped from
+    3.5 to 4 and the long axis 1e4 pixels wide (a, c >= 1e7 at 25 .. 65 degrees); the other slots: controls, ratio 1e2.
+    Centres on a grid over the middle 80 % of the image at depths 6 .. 16: every cull plane is far away."""
+    M = angles_deg.numel()
+    slot = torch.arange(M) % (N_NEEDLES + N_CONTROLS)
+    T, K = sc.T.double(), sc.cam.K.double()
+    A, t = T[:3, :3], T[:3, 3]
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    col, row = (slot % 8).double(), (slot // 8).double()
+    px = sc.W * (0.1 + 0.8 * (col + 0.37) / 8)
+    py = sc.H * (0.1 + 0.8 * (row + 0.61) / 7)
+    z = 6.0 + 10.0 * ((slot * 37) % (N_NEEDLES + N_CONTROLS)).double() / (N_NEEDLES + N_CONTROLS)
+    cam_pts = torch.stack([(px - cx) * z / fx, (py - cy) * z / fy, z], dim=1)
+    xyz = (cam_pts - t) @ A            # A^T (c - t)
+    phi = torch.deg2rad(angles_deg.double())
+    zero, one = torch.zeros(M, dtype=torch.float64), torch.ones(M, dtype=torch.float64)
+    Rz = torch.stack([torch.cos(phi), -torch.sin(phi), zero, torch.sin(phi), torch.cos(phi), zero, zero, zero, one],
+                     dim=1).view(M, 3, 3)
+    q = rot_to_quat(A.T @ Rz)          # columns: the Gaussian's axes in the world
+    is_needle = slot < N_NEEDLES
+    ratio = torch.where(is_needle, 10.0 ** (3.5 + 0.5 * slot.double() / (N_NEEDLES - 1)), torch.full_like(z, 1e2))
+    s_long = 1e4 * z / fx
+    s_short = s_long / ratio
+    disc = is_needle & (slot % 2 == 1)
+    log_s = torch.log(torch.stack([s_long, s_short, torch.where(disc, s_long, s_short)], dim=1))
+    logit = torch.where(is_needle, zero, -3.0 * one)[:, None]
+    return xyz, q, log_s, logit
+
+
+def det_classes(conic):
+    """class of the fp32 render record of conic [V, 3] (fp32): "zero" det == 0, "neg" det < 0, "noisy" det equal to one
+    ulp of a c while the exact a c - b^2 of the same a, b, c is 0.3 .. 3 ulps (and not that ulp), else "plain"; the
+    record's arithmetic: a = conic0 + 1/4, b = conic1 / 2, c = conic2 + 1/4, det = fl(fl(a c) - fl(b b))"""
+    k = conic.detach().cpu().float().numpy()
+    a, b, c = k[:, 0] + np.float32(0.25), k[:, 1] * np.float32(0.5), k[:, 2] + np.float32(0.25)
+    ac = a * c
+    det = ac - b * b
+    exact = a.astype(np.float64) * c.astype(np.float64) - b.astype(np.float64) ** 2
+    ulp = np.spacing(np.abs(ac)).astype(np.float64)
+    out = np.full(len(det), "plain", dtype=object)
+    out[(det == ulp) & (exact >= 0.3 * ulp) & (exact <= 3 * ulp) & (exact != ulp)] = "noisy"
+    out[det < 0] = "neg"
+    out[det == 0] = "zero"
+    return out
+
+
+def fp32_oracle_conic(sc):
+    """-> (keep [N] bool, conic [V, 3]) of the fp32 oracle chain: the default of degenerate_needle_scene's search"""
+    st = oracle_stages(sc, torch.float32)
+    return st["keep"], st["conic"]
+
+
+def _with_rows(base, rows):
+    xyz, q, log_s, logit = (x.float() for x in rows)
+    g = base.g
+    M = xyz.shape[0]
+    gen = torch.Generator().manual_seed(9)
+    rgb = (torch.rand(M, 3, generator=gen, dtype=torch.float64) / SH_0).float()
+    out = SimpleNamespace(**vars(base))
+    out.g = Gaussians(torch.cat([g.xyz, xyz]).contiguous(), torch.cat([g.rgb, rgb]).contiguous(),
+                      torch.cat([g.opacity, logit]).contiguous(), torch.cat([g.scale, log_s]).contiguous(),
+                      torch.cat([g.quaternion, q]).contiguous(), None)
+    return out
+
+
+def degenerate_needle_scene(seed=171, N=2000, conic_of=fp32_oracle_conic):
+    """general_camera_scene(seed, N, kind="odd", stress=False)'s camera and cluster, degree 0, plus N_NEEDLES extreme
+    needles and discs and N_CONTROLS well-conditioned controls (needle_rows) as the last rows.  Each needle's in-plane
+    angle is 25 + 40 i / 47 degrees plus j * 0.01, j < N_ANGLES, and j is chosen by a search: all candidates go through
+    conic_of (scene -> keep, conic of the visible rows; the fp32 oracle chain, or a kernel's own stage), slot i takes
+    the first j whose record has class DET_CLASSES[i % 3], or j = 0.  Nothing random decides class membership.
+    -> the scene, with .rows = {class: Gaussian indices}, .controls, .needles"""
+    base = general_camera_scene(seed, N, kind="odd", stress=False)
+    S = N_NEEDLES + N_CONTROLS
+    slot = torch.arange(S)
+    base_angle = torch.where(slot < N_NEEDLES, 25.0 + 40.0 * slot.double() / (N_NEEDLES - 1), torch.full((S,), 45.0, dtype=torch.float64))
+    cand_angles = (base_angle[None, :] + 0.01 * torch.arange(N_ANGLES, dtype=torch.float64)[:, None]).reshape(-1)
+    cand = _with_rows(base, needle_rows(base, cand_angles))
+    keep, conic = conic_of(cand)
+    assert bool(keep[N:].all()), "a constructed row is culled"
+    vis_rank = torch.cumsum(keep.long(), 0) - 1
+    cls = det_classes(conic)[vis_rank[N:].numpy()].reshape(N_ANGLES, S)
+    chosen = torch.zeros(S, dtype=torch.long)
+    for i in range(N_NEEDLES):
+        hits = np.nonzero(cls[:, i] == DET_CLASSES[i % 3])[0]
+        chosen[i] = int(hits[0]) if len(hits) else 0
+    sc = _with_rows(base, needle_rows(base, base_angle + 0.01 * chosen.double()))
+    keep, conic = conic_of(sc)
+    final = det_classes(conic)[(torch.cumsum(keep.long(), 0) - 1)[N:].numpy()]
+    assert all(final[i] == cls[int(chosen[i]), i] for i in range(S)), "a row's class depends on the other rows"
+    sc.rows = {c: N + torch.tensor([i for i in range(N_NEEDLES) if final[i] == c], dtype=torch.long) for c in DET_CLASSES}
+    sc.needles = N + torch.arange(N_NEEDLES)
+    sc.controls = N + N_NEEDLES + torch.arange(N_CONTROLS)
+    sc.control_classes = list(final[N_NEEDLES:])
+    sc.deg = 0
+    return sc
+
+
 def to_device(sc, device):
     """the scene's Gaussians, camera and pose on `device` (fresh tensors)"""
     d = lambda x: None if x is None else x.detach().to(device).contiguous().clone()
