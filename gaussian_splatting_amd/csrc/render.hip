@@ -57,7 +57,9 @@
 // that holds what a family has of its own: where the channel values come from and where their sums and gradients go.
 // The depth distortion (k_render_distortion_fwd / _bwd) is the depth map's walk with two more sums: its forward is a
 // policy of render_map_fwd, its backward a policy of render_map_bwd (DistortionBwd, whose c_k needs w_k: the c() hook
-// is handed what forms it).
+// is handed what forms it).  The median depth (k_render_median_fwd) is the depth map's forward with a (z, index) pair
+// that every contributor in front of which T is still above one half overwrites: the add() hook is handed T; its
+// backward (k_median_depth_bwd) is a scatter without a walk.
 //
 // Numerics.  The fp32 forward is bit-identical to the CPU restatement: same operation order and
 // operand precisions as render.cu (including its double-literal promotions), the IEEE quotient (formed
@@ -2085,7 +2087,8 @@ constexpr int MAP_BWD_CHUNK = 64;    // of the backward walk: one mask word, one
 //   N                                               the number of channel sums per pixel
 //   stage(sorted, first, cnt, tid, s_geom, s_idx)   the chunk's channel values into LDS, beside the records (s_idx: the
 //                                                   Gaussian indices stage_chunk kept, nullptr in the forward)
-//   add(M, w, rec, i)                               staged entry i (rec: its record) enters the sums with weight w
+//   add(M, w, rec, i, T)                            staged entry i (rec: its record) enters the sums with weight w;
+//                                                   T: the transmittance in front of it (only MedianFwd reads it)
 //   store(M, p)                                     the sums to the map
 template <class Ch>
 __device__ __forceinline__ void render_map_fwd(
@@ -2133,7 +2136,7 @@ __device__ __forceinline__ void render_map_fwd(
                 const ZalphaVisit v = zalpha_alpha(g0, g1, rec[8], pu, pv, k < nsp);
                 if (v.contrib) {
                     const float w = v.alpha * T;
-                    ch.add(M, w, rec, i);
+                    ch.add(M, w, rec, i, T);
                     A += w;
                     T = __builtin_fmaf(-v.alpha, T, T);   // T (1 - alpha), one rounding
                 }
@@ -2298,7 +2301,7 @@ struct DepthChannel {
 struct DepthFwd : DepthChannel {
     float* __restrict__ depth;
     static constexpr int N = 1;
-    __device__ __forceinline__ void add(float (&D)[1], float w, const float* rec, int) const {
+    __device__ __forceinline__ void add(float (&D)[1], float w, const float* rec, int, float) const {
         D[0] = __builtin_fmaf(w, rec[9], D[0]);
     }
     __device__ __forceinline__ void store(const float (&D)[1], size_t p) const { depth[p] = D[0]; }
@@ -2365,7 +2368,7 @@ struct DistortionFwd : DepthChannel {
     float* __restrict__ depth;
     float* __restrict__ distortion;
     static constexpr int N = 3;   // D | X | A
-    __device__ __forceinline__ void add(float (&M)[3], float w, const float* rec, int) const {
+    __device__ __forceinline__ void add(float (&M)[3], float w, const float* rec, int, float) const {
         const float z = rec[9];
         M[1] = __builtin_fmaf(w, __builtin_fmaf(z, M[2], -M[0]), M[1]);
         M[0] = __builtin_fmaf(w, z, M[0]);
@@ -2457,6 +2460,94 @@ __global__ __launch_bounds__(RB) void k_render_distortion_bwd(
 }
 
 // ---------------------------------------------------------------------------------------------------
+// median depth (2DGS's depth_ratio = 1), fp32: the z of the entry at which T falls through 0.5
+// ---------------------------------------------------------------------------------------------------
+// With alpha_k, the contribute decision and T_k (the transmittance in front of entry k) of the depth kernels above (the
+// same walk: depth, alpha and T_end come out with k_render_zalpha_fwd's bits), the MEDIAN ENTRY of a pixel is its last
+// contributing entry with T_k > 0.5f -- the entry during which T falls to 0.5 or below, or the last contributor if it
+// never does (2DGS: `if (T > 0.5) median = depth`, evaluated before the blend).
+//   median_depth[p] = z of that entry's Gaussian, not weighted, not normalised (0 without a contributor)
+//   median_index[p] = that Gaussian's sorted_gaussians value (-1 without a contributor)
+// The forward is render_map_fwd with three walk locals: D as DepthFwd's, the median z, and the BITS of the median
+// Gaussian's index + 1 (0, the locals' initial value, is "none": the store subtracts the 1).  The index of a staged
+// entry is not in LDS in the forward (s_idx is nullptr there), so stage() puts it, + 1, beside z: word 10 of the
+// record, the second colour word, which like word 9 nobody here reads as a colour.  The pair is only ever copied (LDS
+// -> register -> select -> store): no float instruction sees the index bits.
+struct MedianFwd : DepthChannel {
+    float* __restrict__ depth;
+    float* __restrict__ median_depth;
+    int* __restrict__ median_index;
+    static constexpr int N = 3;   // D | z of the median entry | bits of (its Gaussian + 1)
+    __device__ __forceinline__ void stage(const int* __restrict__ sorted, int first, int cnt, int tid, float* s_geom,
+                                          const int* s_idx) const {
+        if (tid < cnt) {
+            const int g = s_idx != nullptr ? s_idx[tid] : sorted[first + tid];   // (what this thread staged)
+            s_geom[tid * GS_PACKED_WIDTH + 9] = xyz_cam[(size_t)g * 3 + 2];
+            s_geom[tid * GS_PACKED_WIDTH + 10] = __int_as_float(g + 1);
+        }
+    }
+    __device__ __forceinline__ void add(float (&M)[3], float w, const float* rec, int, float T) const {
+        const float z = rec[9];
+        M[0] = __builtin_fmaf(w, z, M[0]);
+        if (T > 0.5f) {   // T in front of the entry: every contributor up to the crossing overwrites the pair
+            M[1] = z;
+            M[2] = rec[10];
+        }
+    }
+    __device__ __forceinline__ void store(const float (&M)[3], size_t p) const {
+        depth[p] = M[0];
+        median_depth[p] = M[1];
+        median_index[p] = __float_as_int(M[2]) - 1;
+    }
+};
+
+__global__ __launch_bounds__(RB) void k_render_median_fwd(
+    const float* __restrict__ packed, const float* __restrict__ xyz_cam, const int* __restrict__ ranges,
+    const int* __restrict__ sorted, const int* __restrict__ nsp_in, int W, int H, int ntx, int tile0, int nt,
+    float* __restrict__ median_depth, int* __restrict__ median_index, float* __restrict__ depth,
+    float* __restrict__ alpha_out, float* __restrict__ t_out) {
+    __shared__ alignas(16) float s_geom[MAP_FWD_CHUNK * GS_PACKED_WIDTH];
+    __shared__ unsigned long long s_mask[4][MAP_FWD_CHUNK / 64];
+    __shared__ int s_max[4];
+    MedianFwd ch{{xyz_cam}, depth, median_depth, median_index};
+    render_map_fwd(ch, packed, ranges, sorted, nsp_in, W, H, ntx, tile0, nt, alpha_out, t_out, s_geom, s_mask, s_max);
+}
+
+// dL/dz of the median depth, the choice of entry held constant: grad_z[median_index[p]] += grad_median_depth[p].  No
+// list walk: a scatter, one workgroup per tile with the walks' pixel mapping (a wave = an 8 x 8 patch, whose pixels
+// mostly share a few Gaussians).  The wave loops over the distinct indices it holds -- the first pending lane's index,
+// the ballot of its matches, their sum -- and one lane issues ONE atomic per (wave, distinct Gaussian): a lane-per-pixel
+// atomic onto one large foreground Gaussian is the one-row contention that runs an order of magnitude slower.
+// Pixels outside the image and pixels without a contributor (-1) add nothing.
+__global__ __launch_bounds__(RB) void k_median_depth_bwd(const int* __restrict__ median_index,
+                                                         const float* __restrict__ g_median, int W, int H, int ntx,
+                                                         int tile0, int nt, float* __restrict__ grad_z) {
+    const int t_local = tile_of_block(blockIdx.x, nt);
+    if (t_local >= nt) return;
+    const int tile = tile0 + t_local;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const PixelMap px = pixel_of_thread(tile % ntx, tile / ntx, tid);
+    int g = -1;
+    float x = 0.0f;
+    if (px.u < W && px.v < H) {
+        const size_t p = (size_t)px.v * W + px.u;
+        g = median_index[p];
+        if (g >= 0) x = g_median[p];
+    }
+    unsigned long long todo = ballot(g >= 0);
+    while (todo) {   // wave-uniform
+        const int leader = __builtin_ctzll(todo);
+        const int gl = __builtin_amdgcn_readlane(g, leader);
+        const bool mine = g == gl;
+        float s = mine ? x : 0.0f;
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+        if (lane == leader) global_add(grad_z + gl, s);
+        todo &= ~ballot(mine);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // per-Gaussian feature vectors composited with the frame's weights (no reference counterpart), fp32
 // ---------------------------------------------------------------------------------------------------
 // render_map_fwd / render_map_bwd with C <= 32 caller-supplied channels in place of the one channel z:
@@ -2514,7 +2605,7 @@ template <int CP>
 struct FeaturesFwd : FeatureRows<CP> {
     float* __restrict__ fmap;
     static constexpr int N = CP;
-    __device__ __forceinline__ void add(float (&F)[CP], float w, const float*, int i) const {
+    __device__ __forceinline__ void add(float (&F)[CP], float w, const float*, int i, float) const {
         const Vec4<float>* f4 = reinterpret_cast<const Vec4<float>*>(this->s_feat + i * CP);
 #pragma unroll
         for (int c4 = 0; c4 < CP / 4; c4++) {
@@ -3467,6 +3558,36 @@ int gs_render_distortion_backward(const void* packed, const void* xyz_camera_fra
         (const float*)grad_depth, (const float*)grad_alpha, W, H, t.ntx, t.tile0, t.nt, (float*)grad_slab,
         (float*)grad_z);
     return check_launch("render_distortion_backward");
+}
+
+int gs_render_median_depth(const void* packed, const void* xyz_camera_frame, const int32_t* tile_ranges,
+                           const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel, int W, int H,
+                           int tile_row0, int tile_row1, void* median_depth, int32_t* median_index, void* depth,
+                           void* alpha, void* transmittance, void* stream) {
+    MapTiles t;
+    if (int e = map_entry_tiles("render_median_depth", false, 1, packed, tile_ranges, num_splats_per_pixel,
+                                transmittance, depth, alpha, W, H, tile_row0, tile_row1, &t))
+        return e;
+    GS_REQUIRE(median_depth != nullptr && median_index != nullptr, "render_median_depth: an output is NULL");
+    if (t.nt == 0) return GS_OK;
+    k_render_median_fwd<<<render_grid(t.nt), RB, 0, (hipStream_t)stream>>>(
+        (const float*)packed, (const float*)xyz_camera_frame, tile_ranges, sorted_gaussians, num_splats_per_pixel, W, H,
+        t.ntx, t.tile0, t.nt, (float*)median_depth, median_index, (float*)depth, (float*)alpha, (float*)transmittance);
+    return check_launch("render_median_depth");
+}
+
+int gs_median_depth_backward(const int32_t* median_index, const void* grad_median_depth, int W, int H,
+                             int tile_row0, int tile_row1, void* grad_z, void* stream) {
+    GS_REQUIRE(W > 0 && H > 0, "image must be non-empty");
+    GS_REQUIRE(median_index != nullptr, "median_depth_backward: median_index is NULL");
+    if (int e = check_rows(H, tile_row0, tile_row1)) return e;
+    const int ntx = (W + 15) / 16;
+    const int nt = (tile_row1 - tile_row0) * ntx;
+    if (nt == 0 || grad_median_depth == nullptr) return GS_OK;   // nothing to add
+    GS_REQUIRE(grad_z != nullptr, "median_depth_backward: grad_z is NULL");
+    k_median_depth_bwd<<<render_grid(nt), RB, 0, (hipStream_t)stream>>>(
+        median_index, (const float*)grad_median_depth, W, H, ntx, tile_row0 * ntx, nt, (float*)grad_z);
+    return check_launch("median_depth_backward");
 }
 
 int gs_render_features(const void* packed, const void* features, int n_channels, const int32_t* tile_ranges,

@@ -734,6 +734,26 @@ def distortion_backward(packed, xyz_cam, ranges, sorted_g, nsp, t_end, depth, al
               _p(depth), _p(alpha), _p(gx), _p(gd), _p(ga), width, height, 0, nty, _p(slab), _p(grad_z), _stream())
 
 
+def median_depth_forward(packed, xyz_cam, ranges, sorted_g, nsp, height, width):
+    """-> (depth, median_depth, median_index), alpha, T_end, each [H, W] (gs_render_median_depth): zalpha_forward's three
+    maps, bit for bit, and from the same walk the z and the index (int32, among the visible Gaussians; -1: no
+    contributor) of the entry at which the transmittance falls through 0.5; two allocations"""
+    nty = _tile_grid(width, height)[1]
+    buf = torch.empty(4, height, width, dtype=torch.float32, device=packed.device)
+    index = torch.empty(height, width, dtype=torch.int32, device=packed.device)
+    _hip.call("gs_render_median_depth", _p(packed), _p(xyz_cam), _p(ranges), _p(sorted_g), _p(nsp), width, height, 0,
+              nty, _p(buf[3]), _p(index), _p(buf[0]), _p(buf[1]), _p(buf[2]), _stream())
+    return (buf[0], buf[3], index), buf[1], buf[2]
+
+
+def median_depth_backward(median_index, grad_median_depth, height, width, grad_z):
+    """adds grad_median_depth [H, W] to grad_z at median_index (gs_median_depth_backward): the choice of entry is held
+    constant, nothing goes to the slab; a None grad adds nothing"""
+    nty = _tile_grid(width, height)[1]
+    gm = grad_median_depth.contiguous() if grad_median_depth is not None else None
+    _hip.call("gs_median_depth_backward", _p(median_index), _p(gm), width, height, 0, nty, _p(grad_z), _stream())
+
+
 def features_forward(packed, feat, ranges, sorted_g, nsp, height, width):
     """-> feature_map [H, W, C], alpha, T_end [H, W] (gs_render_features) for the visible Gaussians' feature rows
     feat [V, C] on the lists of the frame whose colour forward left nsp; one allocation"""
@@ -957,6 +977,27 @@ class _DistortionMap(_DepthMap):
     _DepthMap's way"""
     forward, backward = staticmethod(distortion_forward), staticmethod(distortion_backward)
     extra = True    # forward -> ((depth, distortion), alpha, T_end); backward(..., t_end, depth, alpha, g_dist, g_depth, ...)
+    keep = staticmethod(lambda depth, alpha, distortion: (depth, alpha))   # the totals its backward reads
+
+
+class _MedianDepthMap(_DepthMap):
+    """_Render's map policy of rasterize_median_depth (MedianFwd, k_median_depth_bwd): _DepthMap with two more outputs,
+    median_depth (differentiable in z alone) and median_index (int32, marked non-differentiable), from
+    gs_render_median_depth IN PLACE of gs_render_zalpha.  The backward is two independent launches into the same slab
+    and dL/dz tail: gs_render_zalpha_backward if depth or alpha has a gradient, gs_median_depth_backward if
+    median_depth has one"""
+    forward = staticmethod(median_depth_forward)
+    extra = True    # forward -> ((depth, median_depth, median_index), alpha, T_end)
+    keep = staticmethod(lambda depth, alpha, median_depth, median_index: (median_index,))
+
+    @staticmethod
+    def backward(packed, xyz_cam, ranges, sorted_g, nsp, t_end, median_index, grad_median, grad_index, grad_depth,
+                 grad_alpha, height, width, slab, grad_z):
+        if grad_depth is not None or grad_alpha is not None:
+            zalpha_backward(packed, xyz_cam, ranges, sorted_g, nsp, t_end, grad_depth, grad_alpha, height, width, slab,
+                            grad_z)
+        if grad_median is not None:
+            median_depth_backward(median_index, grad_median, height, width, grad_z)
 
 
 class _FeatureMap:
@@ -977,7 +1018,7 @@ class _FeatureMap:
 
 class _Render(torch.autograd.Function):
     """uv, conic, opacity, rgb, the map policy's channels (None without one), the frame record, the policy -> image,
-    or (image, map, alpha) with a policy (+ its extra map when it declares one): its kernels run on the lists and the
+    or (image, map, alpha) with a policy (+ its extra maps when it declares some): its kernels run on the lists and the
     splat counts the colour forward left.
     One backward for all outputs: the prologue clears the slab (and the policy's tail), the colour backward runs if
     the image has a gradient, the policy's if its map or alpha has one, and _Preprocess gets the one slab plus the
@@ -996,10 +1037,11 @@ class _Render(torch.autograd.Function):
             fmap, alpha, t_end = policy.forward(fr.packed, source, fr.ranges, fr.sorted_g, nsp, fr.height, fr.width)
             saved += (source, t_end)
             out = (image, fmap, alpha)
-            if policy.extra:   # (map, extra map): a fourth output, and a backward that reads the forward's totals
-                fmap, extra = fmap
-                saved += (fmap, alpha)
-                out = (image, fmap, alpha, extra)
+            if policy.extra:   # (map, extra maps...): further outputs, and a backward that reads what keep() names
+                fmap, *extras = fmap
+                saved += policy.keep(fmap, alpha, *extras)
+                ctx.mark_non_differentiable(*(e for e in extras if not e.is_floating_point()))
+                out = (image, fmap, alpha, *extras)
         ctx.save_for_backward(*saved)
         ctx.set_materialize_grads(False)
         ctx.fr, ctx.policy, ctx.V = fr, policy, uv.shape[0]   # (fr.cut: flags, complete ranges, overflow lists)
@@ -1009,10 +1051,10 @@ class _Render(torch.autograd.Function):
         return out
 
     @staticmethod
-    def backward(ctx, grad_image, grad_map=None, grad_alpha=None, grad_extra=None):
+    def backward(ctx, grad_image, grad_map=None, grad_alpha=None, *grad_extra):
         packed, rgb, ranges, sorted_g, background_rgb, nsp, fw, cost, seg, *mapped = ctx.saved_tensors
         fr, policy, V = ctx.fr, ctx.policy, ctx.V
-        if grad_image is None and grad_map is None and grad_alpha is None and grad_extra is None:
+        if grad_image is None and grad_map is None and grad_alpha is None and all(g is None for g in grad_extra):
             return (None,) * len(ctx.needs_input_grad)
         n_tail = policy.tail(V) if policy is not None else 0
         out = render_backward(packed, rgb, ranges, sorted_g, background_rgb, nsp, fw,
@@ -1022,8 +1064,8 @@ class _Render(torch.autograd.Function):
         slab, tail = out if n_tail else (out, None)
         g_channels = None
         if policy is not None:
-            source, t_end, *totals = mapped   # (totals: the map and alpha of the forward, for a policy with an extra map)
-            maps = (grad_extra, grad_map) if policy.extra else (grad_map,)
+            source, t_end, *totals = mapped   # (totals: what the policy's keep() named of the forward's outputs)
+            maps = (*grad_extra, grad_map) if policy.extra else (grad_map,)
             into, g_channels = policy.channel_grad(source, V, tail, next((m for m in maps if m is not None), None),
                                                    ctx.needs_input_grad[4])
             # (nothing visible: nothing to add, and an empty slab has no address)
@@ -1428,6 +1470,42 @@ def rasterize_distortion(gaussians, camera_T_world, camera, near_thresh, far_thr
     return image, depth, alpha, distortion, fr.culling_mask, uv
 
 
+def rasterize_median_depth(gaussians, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+                           use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None,
+                           slab_sync=None, frame_hook=None, adam_plan=None, antialiased=False,
+                           camera_model="pinhole", filter3d=None):
+    """rasterize_rgbd() with the median depth of the same walk (2DGS's depth_ratio = 1, gsplat's median depth):
+
+        image, depth, alpha, median_depth, median_index, culling_mask, uv = rasterize_median_depth(...)
+
+    image, culling_mask and uv are those of rasterize(), depth and alpha those of rasterize_rgbd() on the same inputs,
+    bit for bit.  The median entry of a pixel is the last contributing list entry in front of which the transmittance
+    is still above 0.5: the entry during which T falls to 0.5 or below, or the last contributor where it never falls
+    that far (2DGS's `if (T > 0.5) median = depth`).  median_depth [H, W] is the camera-frame z of that
+    entry's Gaussian -- not weighted, not normalised, always a splat's own z where the expected depth / alpha lies
+    between the surfaces at a semi-transparent edge -- and 0 where the pixel has no contributor.  median_index [H, W]
+    int32 is that Gaussian's row in the caller's dense numbering, -1 where the pixel has no contributor; it carries no
+    gradient.  A caller who wants only the pixels whose transmittance did cross 0.5 masks with alpha >= 0.5; the valid
+    pixels are median_index >= 0.  median_depth is differentiated with the choice of entry held constant: its
+    gradient reaches xyz (and camera_T_world when it requires one) through z alone, nothing goes to uv, conic or
+    opacity.  image, depth and alpha keep rasterize_rgbd's gradients; an output without a gradient costs no launch.
+    The 2DGS blend is ratio * median_depth + (1 - ratio) * depth / alpha in the caller;
+    train_ops.normal_consistency_loss(..., depth=median_depth, depth_alpha=(median_index >= 0).float()) takes the
+    median depth's normals.  Whole single-GPU fp32 frames in the SH-precompute colour mode, Python orchestration,
+    depth cut off: anything else raises RuntimeError (the trailing keyword arguments exist only to say so).
+    antialiased, camera_model, filter3d: as rasterize()'s; median_depth stays the camera-frame z, not the distance along
+    the ray."""
+    fr, (uv, conic, opacity, rgb, z) = _begin_frame(
+        gaussians, gaussians.sh, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
+        background_rgb, "rasterize_median_depth", use_sh_precompute,
+        (tile_rows is not None, return_aux, grad_sync, slab_sync, frame_hook), adam_plan=adam_plan,
+        antialiased=antialiased, z_out=True, camera_model=camera_model, filter3d=filter3d)
+    image, depth, alpha, median_depth, median_index = _Render.apply(uv, conic, opacity, rgb, z, fr, _MedianDepthMap)
+    # visible -> dense numbering in one gather: -1 picks the sentinel behind the last visible row
+    dense = torch.cat((fr.vis_idx, fr.vis_idx.new_full((1,), -1)))[median_index.long()]
+    return image, depth, alpha, median_depth, dense, fr.culling_mask, uv
+
+
 def rasterize_features(gaussians, features, camera_T_world, camera, near_thresh, far_thresh, cull_mask_padding, mh_dist,
                        use_sh_precompute, background_rgb, tile_rows=None, return_aux=False, grad_sync=None,
                        slab_sync=None, frame_hook=None, adam_plan=None, antialiased=False,
@@ -1495,7 +1573,9 @@ def depth_to_normal(depth, alpha, camera, camera_model="pinhole", min_alpha=0.0)
     """-> normal [H, W, 3] float32: the unit normal of the surface the depth map d = depth / alpha describes, from the
     central differences of the back-projected points, n = normalize((P(x, y+1) - P(x, y-1)) x (P(x+1, y) - P(x-1, y)))
     (2DGS's depth_to_normal orientation: towards the camera, like rasterize_normals' normals).  depth, alpha: float32
-    [H, W] on the GPU, unnormalised as rasterize_rgbd / rasterize_normals / rasterize_distortion return them; camera.K the
+    [H, W] on the GPU, unnormalised as rasterize_rgbd / rasterize_normals / rasterize_distortion return them (a map that
+    is a depth already, such as rasterize_median_depth's median_depth, goes in with alpha = its 0 / 1 validity,
+    (median_index >= 0).float(): the quotient is the map itself); camera.K the
     frame's intrinsics; camera_model the frame's ("fisheye": P = d (tan(theta) / theta a, 1), a ray at or beyond 90
     degrees is invalid).  A pixel is valid when it is off the image's border, it and its four neighbours have
     alpha > min_alpha (>= 0) and a valid ray, and the cross product is not zero; invalid pixels are (0, 0, 0).

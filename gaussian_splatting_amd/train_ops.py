@@ -421,21 +421,25 @@ def ssim_l1_loss(image, target, ssim_frac=0.2, return_terms=False):
     return (loss, terms) if return_terms else loss
 
 
-def normal_consistency_loss(normal_map, depth, alpha, camera, camera_model="pinhole", min_alpha=0.0):
+def normal_consistency_loss(normal_map, depth, alpha, camera, camera_model="pinhole", min_alpha=0.0, depth_alpha=None):
     """The normal-consistency regulariser of 2DGS over the maps of fused.rasterize_normals:
 
         mean over the valid pixels of  alpha.detach() - sum_c normal_map[..., c] * n_d[..., c]
 
-    with n_d = fused.depth_to_normal(depth, alpha, camera, camera_model, min_alpha) and a pixel valid where n_d exists:
+    with n_d = fused.depth_to_normal(depth, depth_alpha, camera, camera_model, min_alpha) and a pixel valid where n_d exists:
     2DGS's 1 - N . (alpha n_d) for its unnormalised N, restricted to the pixels that have a depth normal.  -> a 0-d
     tensor, differentiable in normal_map, depth and alpha; a frame without a valid pixel gives a zero that still carries
     the graph.  Composed in PyTorch over the kernel's output: a handful of elementwise launches and two reductions per
-    frame, not a hot path; no host read."""
+    frame, not a hot path; no host read.
+    depth_alpha: the map depth is divided by and validated against inside depth_to_normal.  None (the default) is alpha:
+    depth is then the unnormalised sum w z, and the result has the bits it had before the keyword existed.  With the
+    median depth of fused.rasterize_median_depth, which is a depth already, pass depth=median_depth and
+    depth_alpha=(median_index >= 0).float(); alpha stays the frame's accumulated opacity in the loss term."""
     from . import fused
     if not (torch.is_tensor(normal_map) and normal_map.dim() == 3 and normal_map.shape[2] == 3
             and normal_map.shape[:2] == depth.shape):
         raise RuntimeError("normal_consistency_loss: normal_map must be [H, W, 3] over depth's [H, W]")
-    n_d = fused.depth_to_normal(depth, alpha, camera, camera_model, min_alpha)
+    n_d = fused.depth_to_normal(depth, alpha if depth_alpha is None else depth_alpha, camera, camera_model, min_alpha)
     valid = (n_d.detach() != 0).any(dim=2)
     per_pixel = alpha.detach() - (normal_map * n_d).sum(dim=2)
     return torch.where(valid, per_pixel, torch.zeros_like(per_pixel)).sum() / valid.sum().clamp(min=1)

@@ -733,6 +733,34 @@ int gs_render_distortion_backward(const void* packed, const void* xyz_camera_fra
                                   const void* grad_distortion, const void* grad_depth, const void* grad_alpha, int W,
                                   int H, int tile_row0, int tile_row1, void* grad_slab, void* grad_z, void* stream);
 
+/* Median depth of a rendered frame (ABI 22; 2DGS's depth_ratio = 1, gsplat's median depth), fp32, together with the
+ * depth and alpha maps.  With alpha_k, the contribute decision and T_k (the transmittance in front of entry k) exactly
+ * as gs_render_zalpha forms them (the same code; T <- fma(-alpha, T, T) on contributors only), the MEDIAN ENTRY of
+ * pixel p is the last contributing entry k < num_splats_per_pixel[p] with T_k > 0.5f (strict, fp32, the walk's own T):
+ * the entry during which T falls to 0.5 or below, or the last contributor if it never falls that far (2DGS's rule,
+ * `if (T > 0.5) median = depth`, evaluated before the blend).  The entries are taken in LIST order.
+ *   median_depth[p] = xyz_camera_frame[g, 2] of the median entry's Gaussian g: not weighted, not normalised; 0 where
+ *                     the pixel has no contributor
+ *   median_index[p] = g, a sorted_gaussians value (an index among the frame's visible Gaussians); -1 where the pixel
+ *                     has no contributor
+ * One walk: it stands in place of gs_render_zalpha, and depth, alpha and transmittance are bit-equal to that call's.
+ *   outputs   median_depth[H,W], median_index[H,W] (int32), depth[H,W], alpha[H,W], transmittance[H,W]: written for
+ *             every pixel of the tile rows [tile_row0, tile_row1), untouched elsewhere.  Empty lists (V == 0) give
+ *             0, -1, 0, 0, 1.  A NULL output is GS_EINVAL. */
+int gs_render_median_depth(const void* packed, const void* xyz_camera_frame, const int32_t* tile_ranges,
+                           const int32_t* sorted_gaussians, const int32_t* num_splats_per_pixel, int W, int H,
+                           int tile_row0, int tile_row1, void* median_depth, int32_t* median_index, void* depth,
+                           void* alpha, void* transmittance, void* stream);
+/* Backward of median_depth, the choice of entry held constant: grad_z[median_index[p]] += grad_median_depth[p] for every
+ * pixel p of the tile rows with median_index[p] >= 0.  Nothing goes to the slab (uv, conic, opacity), and no lists or
+ * records are read; the gradients of depth and alpha take gs_render_zalpha_backward.
+ *   median_index        [H,W], what gs_render_median_depth wrote: every value is -1 or a row of grad_z
+ *   grad_median_depth   [H,W]; NULL = all zeros: nothing is launched
+ *   grad_z              float[V], accumulated (gs_z_backward takes it on); the caller zeroes it.  Rows no pixel selects
+ *                       are not touched.  One atomic per (8 x 8 pixel patch, distinct Gaussian in it). */
+int gs_median_depth_backward(const int32_t* median_index, const void* grad_median_depth, int W, int H,
+                             int tile_row0, int tile_row1, void* grad_z, void* stream);
+
 /* Per-Gaussian feature vectors composited with the frame's weights (ABI 12; no reference counterpart), fp32.  With
  * alpha_k, the contribute decision, T_k and w_k = alpha_k T_k exactly as gs_render_zalpha forms them (the same code),
  * for pixel p and the list entries k < num_splats_per_pixel[p]:
