@@ -1104,6 +1104,41 @@ int gs_mcmc_add_noise(void* xyz, const void* quaternion, const void* scale, cons
                       const void* noise /*[N,3]*/, int N, float step, float gate_k, float gate_x0,
                       void* stream);
 
+/* ---- Bilateral-grid colour correction (ABI 23; no reference counterpart) ------------------------------------------
+ * Per-image appearance compensation between the rendered image and the loss ("Bilateral Guided Radiance Field
+ * Processing"; gaussian_splatting_amd/bilagrid.py).  All tensors fp32.
+ *   grid  [12, L, Hg, Wg]   channel 4r + j is entry (r, j) of a 3x4 affine A;  L, Hg, Wg >= 1
+ *   image [H, W, 3]         the rasterizer's layout;  H, W >= 1
+ * Pixel (px, py) samples the grid at gx = (px + 0.5) / W (Wg - 1), gy = (py + 0.5) / H (Hg - 1) and
+ * gz = clamp(0.299 R + 0.587 G + 0.114 B, 0, 1) (L - 1), trilinearly: per axis of n nodes i0 = min(floor(g),
+ * max(n - 2, 0)), i1 = min(i0 + 1, n - 1), f = g - i0, interpolated as a0 + f (a1 - a0) (x, then y, then z), and
+ *   out[p, r] = A[r,0] R + A[r,1] G + A[r,2] B + A[r,3].
+ * The xy cell is computed in integers, i0 = (2 px + 1)(Wg - 1) div (2 W), and f is one division of exact integers.
+ * A grid whose every node is the identity affine returns the image's bits.  This is grid_sample(mode="bilinear",
+ * align_corners=True, padding_mode="border") over (gx, gy, gz), followed by the affine.
+ * Limits: H, W < 2^23, W Wg and H Hg < 2^30, 12 L Hg Wg < 2^31; otherwise GS_EINVAL. */
+int gs_bilagrid_slice(const void* grid, const void* image, int H, int W, int L, int Hg, int Wg, void* out,
+                      void* stream);
+/* Its backward for grad_out [H, W, 3]; either output may be NULL and is then skipped.
+ *   grad_grid[4r + j, z, y, x] = sum over the pixels of w_z w_y w_x grad_out[p, r] (R, G, B, 1)[j]
+ *   grad_image[p, j]           = sum_r A[r,j] grad_out[p,r] + (0.299, 0.587, 0.114)[j] dz(p)
+ *   dz(p) = (L - 1) sum_r grad_out[p,r] ((dA/dgz)[r,:3] . rgb + (dA/dgz)[r,3]), dA/dgz the z-lerp's a1 - a0 interpolated
+ *           in x and y; dz = 0 where the luma is <= 0 or >= 1 and for L = 1 (the border clamp's derivative)
+ * grad_grid is reduced without atomics: partial sums per chunk of the pixels of one xy cell go to `workspace`
+ * (gs_bilagrid_workspace_bytes(H, W, L, Hg, Wg) bytes; required iff grad_grid is not NULL) and a second launch sums
+ * them per node in index order.  Two calls on the same inputs return the same bits; every element of grad_grid is
+ * written, nodes that no pixel reaches as exact zeros. */
+size_t gs_bilagrid_workspace_bytes(int H, int W, int L, int Hg, int Wg);
+int gs_bilagrid_slice_backward(const void* grid, const void* image, const void* grad_out, int H, int W, int L, int Hg,
+                               int Wg, void* workspace, void* grad_image, void* grad_grid, void* stream);
+/* Total variation of grids [n_grids, 12, L, Hg, Wg]: the sum over the three grid axes of two or more nodes of the
+ * mean of (G[.. i + 1 ..] - G[.. i ..])^2 over all adjacent pairs of that axis (all grids, all channels); an axis of
+ * one node contributes zero.  tv_out: float[1]; grad_grids: d tv / d grids in the grids' layout, or NULL.
+ * workspace: gs_bilagrid_tv_workspace_bytes bytes of fp64 per-workgroup partial sums, reduced in a fixed order. */
+size_t gs_bilagrid_tv_workspace_bytes(int64_t n_grids, int L, int Hg, int Wg);
+int gs_bilagrid_tv(const void* grids, int64_t n_grids, int L, int Hg, int Wg, void* workspace, void* tv_out,
+                   void* grad_grids, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
