@@ -1139,6 +1139,70 @@ size_t gs_bilagrid_tv_workspace_bytes(int64_t n_grids, int L, int Hg, int Wg);
 int gs_bilagrid_tv(const void* grids, int64_t n_grids, int L, int Hg, int Wg, void* workspace, void* tv_out,
                    void* grad_grids, void* stream);
 
+/* ---- TSDF fusion and mesh extraction (ABI 24; no reference counterpart) -------------------------------------------
+ * Depth maps to a triangle mesh (gaussian_splatting_amd/mesh.py): fuse rendered depth maps into a
+ * truncated signed distance volume, then triangulate a level set of it.  fp32, no contraction, IEEE divide and square
+ * root; no atomics, no scratch.
+ *
+ * The volume has nx x ny x nz nodes; node (i, j, k) sits at origin + voxel_size (i, j, k) in world coordinates (each
+ * coordinate origin_a + voxel_size * (float)index).  Arrays put x fastest: n = (k ny + j) nx + i, in 64 bits.
+ *     tsdf   [nz, ny, nx]      fresh: 1        weight [nz, ny, nx]   fresh: 0        color [nz, ny, nx, 3] or NULL   fresh: 0
+ * Limits: ny <= 262140, nz <= 65535 (the launch grid), else GS_EINVAL.
+ *
+ * gs_tsdf_integrate fuses C views of one size (W, H) in one launch: depth [C, H, W] is the camera-frame z
+ * (gs_render_median_depth's, or depth / alpha), image [C, H, W, 3] or NULL, camera_T_world [C, 4, 4] and K [C, 3, 3] as
+ * gs_filter3d_rate takes them.  A pixel is invalid where its depth is <= 0, not finite or > depth_max.  For the node at p
+ * the views are taken in the order c = 0 .. C - 1:
+ *     pc = camera_T_world_c p                       (csrc/pg_math.h to_camera); skip unless pc.z > near_thresh
+ *     (u, v) = the model's own projection           (GS_RASTER_CLASSIC: fx x / z + cx; GS_RASTER_FISHEYE: the equidistant one)
+ *     px = floor(u + 0.5), py = floor(v + 0.5)      the renderer's integer pixel coordinate, no half-pixel offset; skip
+ *                                                   outside [0, W) x [0, H)
+ *     d = depth[c, py, px]                          skip if invalid
+ *     sdf = (d - pc.z) * (|pc| / pc.z)              |pc| = sqrt(x x + y y + z z): the signed distance ALONG THE RAY, so the
+ *                                                   band has one metric width at every view angle; skip unless
+ *                                                   sdf >= -sdf_trunc
+ *     t = min(1, sdf / sdf_trunc),  W1 = W + 1,  tsdf = (tsdf W + t) / W1,  each colour channel likewise with the
+ *     pixel's colour,  W = min(W1, max_weight)
+ * A node that no view updates is not written: it keeps every bit.  One call with C views gives the bits of C calls with
+ * one view each in the same order (the state is carried in fp32 registers).  Giving exactly one of image and color, a
+ * raster_mode that is neither value, a negative count, sdf_trunc or max_weight not > 0, a parameter that is not a number
+ * or a NULL pointer is GS_EINVAL and writes nothing; C == 0, an empty image or an empty volume returns GS_OK without a
+ * launch.  depth_max may be infinite. */
+int gs_tsdf_integrate(const void* depth, const void* image, const void* camera_T_world, const void* K, int C, int W, int H,
+                      int raster_mode, float near_thresh, float sdf_trunc, float max_weight, float depth_max,
+                      float origin_x, float origin_y, float origin_z, float voxel_size, int nx, int ny, int nz, void* tsdf,
+                      void* weight, void* color, void* stream);
+/* Marching tetrahedra on the Kuhn split of each cell, in two passes with a scan by the caller between them.
+ * Cell (i, j, k), i < nx - 1, j < ny - 1, k < nz - 1, has the 8 corner nodes (i..i+1, j..j+1, k..k+1) and the linear index
+ * of its low corner.  It is ACTIVE iff all 8 corners have weight >= min_weight (> 0).  A corner is INSIDE iff
+ * f = tsdf - level < 0.  Tetrahedron q = 0..5 of a cell is {v0, v1, v2, v3} = {000, e_a, e_a + e_b, 111} with (a, b, c) =
+ * xyz, xzy, yxz, yzx, zxy, zyx.  Every tetrahedron edge points in one of the directions e = 0..6: (1,0,0) (0,1,0) (0,0,1)
+ * (1,1,0) (1,0,1) (0,1,1) (1,1,1), and is owned by its lower node.
+ *   Vertices: edge (n, e) carries one iff it lies in at least one active cell and its ends differ in sign.  With a the
+ *     owning node and b the other end, s = f_a / (f_a - f_b), position = origin + voxel_size ((i, j, k) + s dir_e), colour =
+ *     color_a + s (color_b - color_a).  Vertices are numbered in ascending (n, e).
+ *   Faces: a tetrahedron of an active cell with 1 or 3 corners inside gives one triangle through its three cut edges, one
+ *     with 2 inside (p < q in tetrahedron order, r < s outside) the quad pr, ps, qs, qr as the two triangles (pr, ps, qs) and
+ *     (pr, qs, qr): the quad is split along the diagonal pr - qs.  Every triangle is wound so that its normal points
+ *     towards positive tsdf (free space, the cameras); which corner of a triangle comes first is not specified.  Faces are
+ *     int32 triples of vertex numbers, ordered by (cell, q, triangle).  The mesh is watertight wherever active cells meet.
+ * gs_tsdf_extract_count writes, per node n: edge_mask [N] uint8 (bit e: edge (n, e) carries a vertex), vert_count [N]
+ *   int32 (its popcount) and face_count [N] int32 (the triangles of cell n; 0 for a node that is no cell's low corner).
+ *   workspace: gs_tsdf_extract_workspace_bytes(nx, ny, nz) bytes (one activity byte per cell).
+ * gs_tsdf_extract_emit takes vert_offset and face_offset [N] int32, the EXCLUSIVE prefix sums of the two counts (the caller
+ *   has checked that the totals are <= 2^31 - 1), and writes vertices [Nv, 3], colors [Nv, 3] (iff color is given; exactly
+ *   one of the two is GS_EINVAL) and faces [Nf, 3].  Each vertex is computed once; a vertex id is found as vert_offset[owner] +
+ *   popcount(edge_mask[owner] & ((1 << e) - 1)).  No atomics: two calls on the same volume return the same bits.
+ * Both: a negative size or one over the limits, min_weight not > 0, a parameter that is not a number or a NULL pointer is
+ * GS_EINVAL and writes nothing; an empty volume returns GS_OK without a launch. */
+size_t gs_tsdf_extract_workspace_bytes(int nx, int ny, int nz);
+int gs_tsdf_extract_count(const void* tsdf, const void* weight, int nx, int ny, int nz, float level, float min_weight,
+                          void* workspace, void* edge_mask, int32_t* vert_count, int32_t* face_count, void* stream);
+int gs_tsdf_extract_emit(const void* tsdf, const void* color, const void* edge_mask, const int32_t* vert_offset,
+                         const int32_t* face_offset, const int32_t* face_count, int nx, int ny, int nz, float level,
+                         float origin_x, float origin_y, float origin_z, float voxel_size, void* vertices, void* colors,
+                         int32_t* faces, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
